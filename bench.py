@@ -12,7 +12,22 @@ N==W broadcast), x0-space MSE, grad-norm clip 1.0, AdamW, EMA.  One 
 optimisation step (degrade -> shift -> U-Net fwd -> loss -> U-Net bwd -> [all-reduce] -> clip+AdamW+EMA)
 on a batch that is already resident in HBM.  One JSON line on stdout (rank 0).
 
-Extra objects in that line:
+A plain run does only what the headline figure needs: set up, `--warmup` steps, `--steps` timed steps (`value`, `ms_per_step`),
+one more step's outputs when `--dump-outputs DIR` is given (below), the line.  `--full` adds everything below (the spread
+windows, the roofline replay, the CPU baseline child, the 1000-step sampler with its parity sample, the cfg3 / cfg4 / cfg5 legs);
+the `--no-*` flags still take single legs out of a `--full` run, and the flags that ask for a measurement by name (`--windows K`,
+`--config`, `--cut-graph`) run it in either mode.
+
+`--dump-outputs DIR` (after the timed steps, before anything else runs) restores the seeded state the first step started from
+(weights, AdamW moments and step count, EMA shadow and step count, device RNG offset), runs one more step of the timed path
+through the same captured graph, and writes what that step computed, float32 unless said otherwise, rank 0: loss.npy (float64,
+[1]), t.npy (the step's timesteps, [N]), shift.npy and x_in.npy (the shift and the U-Net input, NCHW), pred.npy (the U-Net
+prediction, NCHW), params.npy and ema.npy (the weights and the EMA shadow after the update, in the reference's key order and
+shapes, flattened and concatenated, sampled at DUMP_SAMPLE fixed positions drawn from a generator seeded with DUMP_SEED).  The inputs of that step (batch, state, RNG offset) depend on the arguments only, so runs and builds can be compared
+file by file.  (The last timed step itself would not do: the bf16 step sums bias and GroupNorm-affine gradients with float atomics,
+and over many steps AdamW carries their rounding into the weights.)
+
+Extra objects in the `--full` line:
   roofline     the contraction kernel family (every `mdm_gemm` launch of the step -- `conv_halo_kernel` / `conv_lin2_kernel` /
                `wgrad_lin_kernel` / `gemm_ring_kernel`: conv fwd/dgrad/wgrad, 1x1 convs, attention products --
                and the batched split-K sum of the weight gradients): algorithmic FLOPs of those launches / their HIP-event
@@ -231,6 +246,52 @@ def time_steps(step, used, warmup, steps):
     return 1e3 * (time.perf_counter() - t0) / steps
 
 
+DUMP_SAMPLE, DUMP_SEED = 1 << 22, 2024      # 2 x 16 MB of sampled weights; the rest of a dump is < 2 MB at the default batch
+
+
+class StepState:
+    """Everything one step reads and writes besides the batch: fp32 weights, AdamW moments and step count, EMA shadow and step
+    count, the device Philox offset.  `restore()` copies a snapshot back IN PLACE (the captured graph holds these buffers)."""
+
+    def __init__(self, model, optim, ema, sched):
+        self.model, self.optim, self.ema, self.rng = model, optim, ema, sched.dev_rng.dev
+        torch.cuda.synchronize()
+        self.bufs = [(t, t.clone()) for t in (model.store.P, optim.m, optim.v, self.rng) + ((ema.shadow,) if ema is not None else ())]
+        self.t, self.ema_step = optim.t, (ema.optimization_step if ema is not None else None)
+
+    def restore(self):
+        torch.cuda.synchronize()
+        for live, saved in self.bufs:
+            live.copy_(saved)
+        self.optim.t = self.t
+        if self.ema is not None:
+            self.ema.optimization_step = self.ema_step
+        self.model.store.sync_shadow()          # bf16 / transposed / split shadows follow the restored fp32 weights
+        torch.cuda.synchronize()
+
+
+def dump_outputs(out_dir, step, model, ema, loss):
+    """The dumped step's outputs as DIR/<name>.npy (see the module docstring).  Synchronises; nothing here is timed."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    nchw = lambda a: a.data.float().cpu()[..., :model.cout].permute(0, 3, 1, 2).contiguous()
+    arrays = {"loss": np.array([loss], dtype=np.float64), "t": model.t_in.float().cpu(),
+              "shift": step.s.cpu(), "x_in": step.x_in.cpu(), "pred": nchw(model.y_out)}
+    order = model.reference_param_order()
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = None
+    for name, src in [("params", None)] + ([("ema", ema.shadow)] if ema is not None else []):
+        flat = torch.cat([v.reshape(-1) for v in model.store.state_dict(order=order, src=src).values()])
+        if idx is None:
+            idx = torch.randint(flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=g).sort().values
+        arrays[name] = flat[idx]
+    for name, a in arrays.items():
+        a = a.numpy() if isinstance(a, torch.Tensor) else a
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    return sorted(arrays)
+
+
 def family_roofline(_lib, step, model, optim, ema, dt, reps=3):
     """HIP events around every contraction launch of the step (see `roofline` in the module docstring) ->
     (TFLOP/s, ms per step in the family, launches per step, event-pair cost in ms)."""
@@ -341,8 +402,13 @@ def main():
     ap.add_argument("--bucket-mb", type=float, default=None, help="gradient bucket size of the all-reduce (N > 1; default 32)")
     ap.add_argument("--reserve-cus", type=int, default=0,
                     help="N > 1: build the persistent weight-gradient launch for CUs - R workgroups so that RCCL's kernels find free CUs beside it")
-    ap.add_argument("--windows", type=int, default=4, help="further timed windows of --steps steps behind the headline one (spread: min / median / max)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cfg3 / cfg4 / cfg5 legs of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: windows, roofline, CPU baseline, sampler, cfg3 / cfg4 / cfg5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run one step of the timed path from the seeded initial state and write its outputs as DIR/<name>.npy")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="further timed windows of --steps steps behind the headline one (spread: min / median / max; default 4 with --full, else 0)")
+    ap.add_argument("--no-extras", action="store_true", help="skip the cfg3 / cfg4 / cfg5 legs of the --full run")
     ap.add_argument("--config", action="append", default=[], choices=["cfg3", "cfg4", "cfg5"],
                     help="also measure this BASELINE.json configuration (reported under `extras`; the headline stays cfg2)")
     ap.add_argument("--cut-graph", action="store_true", help="also time the data-parallel (cut) form of the step graph on this one GPU")
@@ -351,6 +417,10 @@ def main():
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--parity-out", default=None, help=argparse.SUPPRESS)
     opt_ = ap.parse_args()
+    if opt_.steps < 1 or opt_.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if opt_.windows is None:
+        opt_.windows = 4 if opt_.full else 0
     if opt_.cpu_baseline_only:           # child process of the cpu_baseline leg: CPU only, never touches the GPU
         print(json.dumps(cpu_baseline(parity_out=opt_.parity_out)))
         return
@@ -413,6 +483,9 @@ def main():
     step.x0.copy_(torch.rand(N, 3, 32, 32, generator=g) * 2 - 1)          # synthetic batch, resident in HBM
 
     log(f"model built: {model.num_parameters()} params, {len(model.forward_plan.calls)} fwd / {len(model.backward_plan.calls)} bwd launches")
+    # --dump-outputs: the seeded state before the first step, so that the dumped step starts from the same inputs on every run (the
+    # bf16 step sums some gradients with float atomics: over many steps AdamW carries their rounding into the weights)
+    initial = StepState(model, optim, ema, sched) if opt_.dump_outputs else None
 
     def barrier():
         if world > 1 or rehearse:
@@ -441,6 +514,15 @@ def main():
     ms_per_step = 1e3 * elapsed / opt_.steps
     value = N * world * opt_.steps / elapsed
     comm_rep = step.comm_report() if comm is not None else None          # exposed wait of the headline region's steps
+    if initial is not None:
+        # one more step of the timed path (same captured graph, every rank), from the restored seeded state
+        initial.restore()
+        barrier()
+        step.run_device(None, used)
+        barrier()
+        if rank == 0:
+            dumped = dump_outputs(opt_.dump_outputs, step, model, ema, float(step.loss))
+            log(f"outputs of one step of the timed path from the seeded state written to {opt_.dump_outputs}: {', '.join(dumped)}")
     # ---- spread: the same K steps again, `--windows` times, each bracketed like the headline region (which stays the `value`)
     wins = [ms_per_step]
     for _ in range(max(0, opt_.windows)):
@@ -464,7 +546,7 @@ def main():
     # ---- roofline of the contraction kernel family: HIP events around every launch, on the launch stream
     roofline = None
     step_hbm = None
-    if rank == 0 and not opt_.no_roofline:
+    if rank == 0 and opt_.full and not opt_.no_roofline:
         st = torch.cuda.current_stream().cuda_stream
         with _lib.Recording() as front:
             step._emit_device_front()
@@ -530,7 +612,7 @@ def main():
     cpu = None
     parity_file = None
     ref = None
-    if rank == 0 and world == 1 and not opt_.no_cpu_baseline:
+    if rank == 0 and world == 1 and opt_.full and not opt_.no_cpu_baseline:
         import subprocess
         import tempfile
 
@@ -558,7 +640,7 @@ def main():
 
     # ---- 1k-step sampler wall-clock (single GPU: samples are independent, no collective; N>1 shards sample_num)
     sampler = None
-    if rank == 0 and world == 1 and not opt_.no_sampler:
+    if rank == 0 and world == 1 and opt_.full and not opt_.no_sampler:
         sampler = {}
         pparams = parity_params(model.reference_shapes())
         # "f32_split": fp32 storage and accumulation, the 3x3 convolutions' products on the bf16 matrix pipe as hi / lo pairs
@@ -622,9 +704,9 @@ def main():
     if rank == 0 and world == 1 and opt_.cut_graph:
         extras["cut_graph"] = bench_cut_graph(mdm, TrainStep, model, sched, args, optim, ema, used, opt_, ms_per_step)
     if rank == 0 and world == 1:
-        # the other BASELINE configurations ride in the DEFAULT line (a few seconds each) so that the driver times them too;
+        # the other BASELINE configurations ride in the --full line (a few seconds each);
         # `--config` asks for one explicitly (cfg5 then also runs the exact-fp32 250-step sampler), `--no-extras` skips them
-        names = list(opt_.config) if opt_.config else ([] if (opt_.no_extras or opt_.no_sampler) else ["cfg3", "cfg4", "cfg5"])
+        names = list(opt_.config) if opt_.config else ([] if (not opt_.full or opt_.no_extras or opt_.no_sampler) else ["cfg3", "cfg4", "cfg5"])
         for name in names:
             log(f"extra configuration {name}")
             try:

@@ -2,7 +2,7 @@
 # do the grouped weight-gradient kernels (side stream) run next to the chain kernels?  kernel-trace timestamps say.
 export TMPDIR=/tmp; R=$PWD; OUT=$R/gpurun_out/ovl; rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/run -- python3 $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-sampler $@ > $OUT/bench.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/run -- python3 $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-sampler $@ > $OUT/bench.log 2>&1
 cd $R
 python3 - <<'PY'
 import csv, glob, os

@@ -33,7 +33,7 @@ def collect(kind):
     return acc, steps
 
 
-res = {"command": "rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-sampler (one run per counter set)",
+res = {"command": "rocprofv3 --kernel-trace --pmc <counters> -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-sampler (one run per counter set)",
        "correction": "FETCH_SIZE x2 on gfx950 (MI355X_MICROARCH.md, HBM); WRITE_SIZE as reported; KiB -> bytes x1024",
        "mfma_busy_formula": "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs * 256 CUs * 4 SIMDs), summed over the family's dispatches",
        "families": {}}

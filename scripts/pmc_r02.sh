@@ -2,9 +2,9 @@
 # Round-2 profile of the train step: rocprofv3 kernel-trace stats + PMC passes (each in its own run, kernel-trace only,
 # as MI355X_MICROARCH.md "rocprofv3 PMC slots" / "HBM" prescribe) -> gpurun_out/pmc2/{kernel_stats.csv, pmc.json}
 export TMPDIR=/tmp; R=$PWD; OUT=$R/gpurun_out/pmc2; rm -rf $OUT; mkdir -p $OUT
-ARGS="--steps 6 --warmup 2 --no-cpu-baseline --no-sampler"
+ARGS="--full --steps 6 --warmup 2 --no-cpu-baseline --no-sampler"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-sampler > $OUT/stats.json 2> $OUT/stats.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-sampler > $OUT/stats.json 2> $OUT/stats.err || exit 1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $R/bench.py $ARGS > $OUT/fetch.json 2> $OUT/fetch.err || exit 1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $R/bench.py $ARGS > $OUT/write.json 2> $OUT/write.err || exit 1
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE --output-format csv -d $OUT/sq -- python3 $R/bench.py $ARGS > $OUT/sq.json 2> $OUT/sq.err || exit 1

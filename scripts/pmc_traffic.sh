@@ -4,10 +4,10 @@
 # half of a wide coalesced read stream, so it is doubled).  Also a kernel-trace --stats summary.
 export TMPDIR=/tmp; R=$PWD; OUT=$R/gpurun_out/traffic; rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-ARGS="--steps 6 --warmup 2 --no-cpu-baseline --no-sampler"
+ARGS="--full --steps 6 --warmup 2 --no-cpu-baseline --no-sampler"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 $R/bench.py $ARGS > $OUT/fetch.json 2> $OUT/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/write -- python3 $R/bench.py $ARGS > $OUT/write.json 2> $OUT/write.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 12 --warmup 4 --no-cpu-baseline --no-sampler > $OUT/stats.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 12 --warmup 4 --no-cpu-baseline --no-sampler > $OUT/stats.json 2> $OUT/stats.err
 cp $(ls -t $OUT/stats/*/*kernel_stats.csv | head -1) $OUT/kernel_stats.csv
 cd $R
 python3 - <<'PY'
@@ -33,7 +33,7 @@ out = {"kernel_family": "conv_halo / conv_lin2 / wgrad_lin / gemm_ring / gemm_bf
        "fetch_KiB_raw_per_launch": f / nf, "write_KiB_per_launch": w / nw, "launches_counted": [nf, nw],
        "hbm_bytes_per_launch": (2.0 * f / nf + w / nw) * 1024.0,
        "correction": "FETCH_SIZE x2 on gfx950 (MI355X_MICROARCH.md, HBM); WRITE_SIZE as reported; KiB -> bytes x1024",
-       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-sampler"}
+       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-sampler"}
 json.dump(out, open("gpurun_out/traffic/pmc_traffic.json", "w"), indent=1)
 print(json.dumps(out))
 PY

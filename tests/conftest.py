@@ -3,6 +3,11 @@ import sys
 
 import pytest
 
+# The CPU oracle is compared with the reference's fp32 outputs at fp32 rounding: oneDNN must not run its fp32 convolutions and
+# matmuls in a reduced-precision math mode (bf16 / tf32) that a machine's environment may select by default.  Set before torch
+# initialises oneDNN; the tests' subprocesses (gloo ranks, bench.py) inherit it.
+os.environ["ONEDNN_DEFAULT_FPMATH_MODE"] = "STRICT"
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "masked-diffusion-model_amd")
 for p in (ROOT, PKG):

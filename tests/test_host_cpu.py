@@ -260,6 +260,13 @@ def test_bench_refuses_a_job_size_other_than_gpus():
     assert r.returncode != 0 and "--gpus 2 but WORLD_SIZE=3" in r.stderr and not r.stdout.strip()
 
 
+def test_bench_has_full_and_dump_outputs_and_refuses_zero_steps():
+    r = _run_bench(["--help"], {})
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stdout[-2000:]
+    r = _run_bench(["--steps", "0"], {})
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr and not r.stdout.strip(), r.stderr[-2000:]
+
+
 def test_bench_gpus_n_starts_n_ranks_itself():
     """No GPU here: both ranks must come up (through torch.distributed.run) and each fail loudly at the
     no-CPU-fallback check -- proof that `python bench.py --gpus 2` is not a one-rank no-op any more."""
