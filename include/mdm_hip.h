@@ -137,6 +137,12 @@ int mdm_gemm_plan(const mdm_gemm_desc* desc_host, int* splitk_out, int64_t* ws_b
 int mdm_gemm_can_fuse_gn_bwd(const mdm_gemm_desc* desc_host, int G);
 /* the same question for the gnf_* epilogue of a bf16 3x3 forward convolution */
 int mdm_gemm_can_fuse_gn_fwd(const mdm_gemm_desc* desc_host, int G);
+/* Route record (tests): the kernel and second stage ("+tapsplit" epilogue, "+splitk" reduce) the last mdm_gemm, mdm_gemm_pair
+ * ("pair:two launches" when it ran two mdm_gemm) or mdm_wgrad_group_launch call on THIS host thread launched, e.g.
+ * "halo<256,6,NSB,64,f32,split>", "lin2<64,64>+tapsplit"; "none" before the first call or when validation failed.  Host-side only. */
+const char* mdm_gemm_last_route(void);
+/* every route name mdm_gemm_last_route can return: fills up to `cap` of them into out (may be NULL), returns how many there are */
+int mdm_gemm_route_names(const char** out, int cap);
 
 /* ------------------------------------------------------------------------- *
  * A GROUP of weight gradients in ONE launch (autograd's conv2d weight gradient, unet6.py:232-235).

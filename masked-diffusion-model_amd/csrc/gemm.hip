@@ -3813,21 +3813,22 @@ static int halo_tile_f32(const mdm_gemm_desc& d) {
 }
 
 // conv_halo_mixed_kernel: whole rounds of 256-pixel tiles, the remainder as 128-pixel tiles -- taken when the remainder is at most one
-// round of small tiles (otherwise two short rounds cost more than the one long round they replace).  0 = plain launch.
+// round of small tiles (otherwise two short rounds cost more than the one long round they replace).  kNotTaken = plain launch.
 #ifndef MDM_SPLIT_BN128
 #define MDM_SPLIT_BN128 160         // 128-channel split tiles when the layer has at least this many of them (0: never)
 #endif
 #ifndef MDM_SPLIT_MIXED
 #define MDM_SPLIT_MIXED 1
 #endif
+constexpr int kNotTaken = 1;       // "this launcher does not apply" (positive: every error code, hip_fail's -2 included, is negative)
 static int launch_halo_mixed(const mdm_gemm_desc& d, hipStream_t s) {
     const int tn = d.N / 64;
     const int64_t tiles = (int64_t)(d.M / 256) * tn;
     const int64_t big_m = (tiles / 256) * 256 / tn;                // M tiles of 256 pixels in whole rounds (all their channel tiles)
     const int64_t rest = (d.M / 256 - big_m) * 2 * tn;             // 128-pixel tiles behind them
-    if (!MDM_SPLIT_MIXED || d.OW != 32 || d.OH % 8 || big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return -2;
+    if (!MDM_SPLIT_MIXED || d.OW != 32 || d.OH % 8 || big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return kNotTaken;
     const int npa = halo_pieces(256, d.OH, d.OW), npb = halo_pieces(128, d.OH, d.OW);
-    if (npa > 48 || npb > 32) return -2;
+    if (npa > 48 || npb > 32) return kNotTaken;
     int bytes = std::max(2 * npa * 1024 + 2 * 3 * 64 * 128 + 1024, 2 * npb * 1024 + 3 * 3 * 64 * 128 + 1024);
     bytes = std::max(bytes, 256 * 64 * 4);
     MDM_REQUIRE(bytes <= 160 * 1024, "conv_halo_mixed: tile does not fit (%d bytes)", bytes);
@@ -4095,8 +4096,71 @@ static int check_fused_gn(const mdm_gemm_desc& d) {
     return 0;
 }
 
+// ---- route record (mdm_gemm_last_route): which kernel and which second stage the last call on this host thread launched.
+// One table: X(enum, kernel name, second stages it can take: T = tap-split epilogue, K = split-K reduce).  A route is
+// kernel * 3 + stage; the names of all three stages exist, mdm_gemm_route_names lists the ones the mask allows.
+enum RouteStage { S_NONE = 0, S_TAPSPLIT = 1, S_SPLITK = 2 };
+constexpr int TSPLIT = 1 << S_TAPSPLIT, KSPLIT = 1 << S_SPLITK;
+#define MDM_GEMM_ROUTES(X)                                                                                                      \
+    X(R_SKINNY_F32, "linear_skinny_f32", 0) X(R_TN_SKINNY_F32, "tn_skinny_f32", 0)                                              \
+    X(R_LIN_SPLIT_128, "lin_split<128>", 0) X(R_LIN_SPLIT_64, "lin_split<64>", 0)                                               \
+    X(R_HS_256_4_32, "halo<256,4,2,32,f32,split>", 0) X(R_HS_256_6_32, "halo<256,6,2,32,f32,split>", 0)                         \
+    X(R_HS_256_4_128, "halo<256,4,4,128,f32,split>", 0) X(R_HS_256_6_128, "halo<256,6,4,128,f32,split>", 0)                     \
+    X(R_HS_MIXED, "halo_mixed<256|128,f32,split>", 0)                                                                           \
+    X(R_HS_256_4, "halo<256,4,NSB,64,f32,split>", 0) X(R_HS_256_6, "halo<256,6,NSB,64,f32,split>", 0)                           \
+    X(R_HS_128_3, "halo<128,3,3,64,f32,split>", 0) X(R_HS_128_4, "halo<128,4,3,64,f32,split>", 0)                               \
+    X(R_HS_128_6, "halo<128,6,3,64,f32,split>", 0)                                                                              \
+    X(R_HS_64_2_32, "halo<64,2,3,32,f32,split>", 0) X(R_HS_64_3_32, "halo<64,3,3,32,f32,split>", 0)                             \
+    X(R_HS_64_2_64, "halo<64,2,3,64,f32,split>", 0) X(R_HS_64_3_64, "halo<64,3,3,64,f32,split>", 0)                             \
+    X(R_HF_256_4, "halo<256,4,2,64,f32>", 0) X(R_HF_256_6, "halo<256,6,2,64,f32>", 0)                                           \
+    X(R_HF_128_3, "halo<128,3,3,64,f32>", 0) X(R_HF_128_4, "halo<128,4,3,64,f32>", 0)                                           \
+    X(R_HF_128_6, "halo<128,6,3,64,f32>", 0)                                                                                    \
+    X(R_HF_64_2_32, "halo<64,2,3,32,f32>", 0) X(R_HF_64_3_32, "halo<64,3,3,32,f32>", 0)                                         \
+    X(R_HF_64_2_64, "halo<64,2,3,64,f32>", 0) X(R_HF_64_3_64, "halo<64,3,3,64,f32>", 0)                                         \
+    X(R_F32_128, "f32_mfma<128>", KSPLIT) X(R_F32_128_SPLIT, "f32_mfma<128,split>", KSPLIT) X(R_F32_64, "f32_mfma<64>", KSPLIT) \
+    X(R_THIN_1, "conv_thin_k<1>", 0) X(R_THIN_2, "conv_thin_k<2>", 0) X(R_THIN_4, "conv_thin_k<4>", 0)                          \
+    X(R_THIN_8, "conv_thin_k<8>", 0)                                                                                            \
+    X(R_H256_4, "halo<256,4,NSB,64>", 0) X(R_H256_6, "halo<256,6,NSB,64>", 0)                                                   \
+    X(R_H128_3, "halo<128,3,3,64>", 0) X(R_H128_4, "halo<128,4,3,64>", 0) X(R_H128_6, "halo<128,6,3,64>", 0)                    \
+    X(R_H64_2_32, "halo<64,2,3,32>", 0) X(R_H64_3_32, "halo<64,3,3,32>", 0)                                                     \
+    X(R_H64_2_64, "halo<64,2,3,64>", 0) X(R_H64_3_64, "halo<64,3,3,64>", 0)                                                     \
+    X(R_SMALL_4, "conv_small<4,64,32>", 0) X(R_SMALL_5, "conv_small<5,64,32>", 0)                                               \
+    X(R_SMALL_3, "conv_small<3,32,16>", 0)                                                                                      \
+    X(R_LIN2_128, "lin2<128,128>", 0) X(R_LIN2_64x128, "lin2<64,128>", TSPLIT) X(R_LIN2_64, "lin2<64,64>", TSPLIT)              \
+    X(R_WGRAD_LIN_128, "wgrad_lin<128>", KSPLIT) X(R_WGRAD_LIN_64, "wgrad_lin<64>", KSPLIT)                                     \
+    X(R_RING_128, "ring<128>", KSPLIT) X(R_RING_64, "ring<64>", TSPLIT | KSPLIT)                                                \
+    X(R_BF16_128, "bf16<128>", KSPLIT) X(R_BF16_64, "bf16<64>", KSPLIT)                                                         \
+    X(R_PAIR_SMALL_4, "pair_small<4>", 0) X(R_PAIR_SMALL_5, "pair_small<5>", 0)                                                 \
+    X(R_PAIR_SMALL_3, "pair_small<3,32,16>", 0)                                                                                 \
+    X(R_PAIR_64_2, "pair<halo<64,2,3,32>,lin2<64,64>>", 0) X(R_PAIR_64_3, "pair<halo<64,3,3,32>,lin2<64,64>>", 0)               \
+    X(R_PAIR_128_L64x128, "pair<halo<128,3,3,64>,lin2<64,128>>", 0)                                                             \
+    X(R_PAIR_128_L64, "pair<halo<128,3,3,64>,lin2<64,64>>", 0)                                                                  \
+    X(R_PAIR_256_L128, "pair<halo<256,6,NSB,64>,lin2<128,128>>", 0)                                                             \
+    X(R_PAIR_TWO, "pair:two launches", 0)                                                                                       \
+    X(R_WGROUP, "wgrad_group", KSPLIT) X(R_WGROUP_TAPS, "wgrad_taps_group", KSPLIT)
+enum GemmRoute {
+#define MDM_ROUTE_ENUM(e, n, m) e,
+    MDM_GEMM_ROUTES(MDM_ROUTE_ENUM)
+#undef MDM_ROUTE_ENUM
+    R_COUNT
+};
+static const char* const kRouteName[R_COUNT * 3] = {
+#define MDM_ROUTE_NAME(e, n, m) n, n "+tapsplit", n "+splitk",
+    MDM_GEMM_ROUTES(MDM_ROUTE_NAME)
+#undef MDM_ROUTE_NAME
+};
+static const int kRouteStages[R_COUNT] = {
+#define MDM_ROUTE_MASK(e, n, m) 1 | (m),
+    MDM_GEMM_ROUTES(MDM_ROUTE_MASK)
+#undef MDM_ROUTE_MASK
+};
+static thread_local int g_route = -1;
+static inline int route(GemmRoute r) { g_route = 3 * r; return 0; }
+static inline void route_stage(RouteStage st) { if (g_route >= 0) g_route = g_route / 3 * 3 + st; }
+
 static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
     Resolved r;
+    g_route = -1;
     if (int rc = resolve(dh, false, r)) return rc;
     const mdm_gemm_desc& d = r.d;
     const bool big = r.big;
@@ -4107,6 +4171,7 @@ static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
     int rc = 0;
     if (d.dtype == MDM_F32 && d.layout == 0 && !d.conv && d.M <= 32 && d.K % 64 == 0 && d.K <= 512 && d.splitk <= 1 &&
         d.batch == 1 && !d.rowvec && !d.resid && !d.acc0 && d.N0 == d.N && d.lda % 4 == 0 && d.ldb % 4 == 0) {
+        route(R_SKINNY_F32);
         static bool configured = false;
         const int bytes = 32 * (d.K > 16 * 17 ? d.K : 16 * 17) * 4;
         if (!configured) {
@@ -4118,6 +4183,7 @@ static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
     } else if (d.dtype == MDM_F32 && d.layout == 2 && !d.conv && d.batch == 1 && d.K <= 128 && d.splitk <= 1 && d.N0 == d.N && !d.D1 &&
                d.M % 4 == 0 && d.N % 4 == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 && d.ldd0 % 4 == 0 && !d.bias && !d.rowvec && !d.resid) {
         // weight gradient of a linear layer over a batch-sized reduction (the time-embedding path)
+        route(R_TN_SKINNY_F32);
         const int bytes = d.K * 128 * 4;
         static int configured = 0;
         if (configured < bytes) {
@@ -4126,9 +4192,10 @@ static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
         }
         hipLaunchKernelGGL(tn_skinny_f32_kernel, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 64))), dim3(256), bytes, s, d);
     } else if (const int lsb = lin_split_tile(d)) {
-        rc = lsb == 128 ? launch_lin_split<128>(d, s) : launch_lin_split<64>(d, s);
+        rc = lsb == 128 ? route(R_LIN_SPLIT_128) + launch_lin_split<128>(d, s) : route(R_LIN_SPLIT_64) + launch_lin_split<64>(d, s);
     } else if (halo_small_n_split(d)) {
-        rc = (halo_pieces(256, d.OH, d.OW) + 7) / 8 <= 4 ? launch_halo<256, 4, 2, 32, float, true>(d, s) : launch_halo<256, 6, 2, 32, float, true>(d, s);
+        rc = (halo_pieces(256, d.OH, d.OW) + 7) / 8 <= 4 ? route(R_HS_256_4_32) + launch_halo<256, 4, 2, 32, float, true>(d, s)
+                                                          : route(R_HS_256_6_32) + launch_halo<256, 6, 2, 32, float, true>(d, s);
     } else if (const int hb32_exact = halo_tile_f32(d)) {
         // exact-fp32 3x3 convolutions on the halo kernel (forward, folded upsample, transposed shadow): MFMA-bound
         const int hb32 = hb32_exact;
@@ -4142,72 +4209,81 @@ static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
             // 12 for 24; half as many tiles, so a 16x16 layer at sample_num = 100 is ONE round of workgroups instead of 1.56 in two
             if (hb32 == 256 && MDM_SPLIT_BN128 && d.N % 128 == 0 && (d.OW == 16 || d.OW == 32) &&
                 (int64_t)(d.M / 256) * (d.N / 128) >= MDM_SPLIT_BN128) {
-                rc = npw <= 4 ? launch_halo<256, 4, 4, 128, float, true, 1>(d, s) : launch_halo<256, 6, 4, 128, float, true, 1>(d, s);
+                rc = npw <= 4 ? route(R_HS_256_4_128) + launch_halo<256, 4, 4, 128, float, true, 1>(d, s)
+                               : route(R_HS_256_6_128) + launch_halo<256, 6, 4, 128, float, true, 1>(d, s);
             } else
-            if (hb32 == 256 && (rc = launch_halo_mixed(d, s)) != -2) { /* whole rounds of 256-pixel tiles + a short round of 128-pixel ones */ }
-            else if (hb32 == 256) rc = npw <= 4 ? launch_halo<256, 4, MDM_SPLIT_NSB256, 64, float, true>(d, s) : launch_halo<256, 6, MDM_SPLIT_NSB256, 64, float, true>(d, s);
-            else if (hb32 == 128) rc = npw <= 3 ? launch_halo<128, 3, 3, 64, float, true>(d, s) : npw <= 4 ? launch_halo<128, 4, 3, 64, float, true>(d, s)
-                                                                                             : launch_halo<128, 6, 3, 64, float, true>(d, s);
+            if (hb32 == 256 && (rc = launch_halo_mixed(d, s)) != kNotTaken) { route(R_HS_MIXED); /* whole rounds of 256-pixel tiles + a short round of 128-pixel ones */ }
+            else if (hb32 == 256) rc = npw <= 4 ? route(R_HS_256_4) + launch_halo<256, 4, MDM_SPLIT_NSB256, 64, float, true>(d, s)
+                                                 : route(R_HS_256_6) + launch_halo<256, 6, MDM_SPLIT_NSB256, 64, float, true>(d, s);
+            else if (hb32 == 128) rc = npw <= 3 ? route(R_HS_128_3) + launch_halo<128, 3, 3, 64, float, true>(d, s)
+                                     : npw <= 4 ? route(R_HS_128_4) + launch_halo<128, 4, 3, 64, float, true>(d, s)
+                                                : route(R_HS_128_6) + launch_halo<128, 6, 3, 64, float, true>(d, s);
             else if ((int64_t)(d.M / 64) * (d.N / 64) < kBigMinTiles && d.N % 32 == 0)
-                rc = npw <= 2 ? launch_halo<64, 2, 3, 32, float, true>(d, s) : launch_halo<64, 3, 3, 32, float, true>(d, s);
-            else rc = npw <= 2 ? launch_halo<64, 2, 3, 64, float, true>(d, s) : launch_halo<64, 3, 3, 64, float, true>(d, s);
+                rc = npw <= 2 ? route(R_HS_64_2_32) + launch_halo<64, 2, 3, 32, float, true>(d, s) : route(R_HS_64_3_32) + launch_halo<64, 3, 3, 32, float, true>(d, s);
+            else rc = npw <= 2 ? route(R_HS_64_2_64) + launch_halo<64, 2, 3, 64, float, true>(d, s) : route(R_HS_64_3_64) + launch_halo<64, 3, 3, 64, float, true>(d, s);
         } else
-        if (hb32 == 256) rc = npw <= 4 ? launch_halo<256, 4, 2, 64, float>(d, s) : launch_halo<256, 6, 2, 64, float>(d, s);
-        else if (hb32 == 128) rc = npw <= 3 ? launch_halo<128, 3, 3, 64, float>(d, s) : npw <= 4 ? launch_halo<128, 4, 3, 64, float>(d, s)
-                                                                                         : launch_halo<128, 6, 3, 64, float>(d, s);
+        if (hb32 == 256) rc = npw <= 4 ? route(R_HF_256_4) + launch_halo<256, 4, 2, 64, float>(d, s) : route(R_HF_256_6) + launch_halo<256, 6, 2, 64, float>(d, s);
+        else if (hb32 == 128) rc = npw <= 3 ? route(R_HF_128_3) + launch_halo<128, 3, 3, 64, float>(d, s)
+                                 : npw <= 4 ? route(R_HF_128_4) + launch_halo<128, 4, 3, 64, float>(d, s)
+                                            : route(R_HF_128_6) + launch_halo<128, 6, 3, 64, float>(d, s);
         else if ((int64_t)(d.M / 64) * (d.N / 64) < kBigMinTiles && d.N % 32 == 0)       // 4x4 maps: 32-channel tiles, twice the workgroups
-            rc = npw <= 2 ? launch_halo<64, 2, 3, 32, float>(d, s) : launch_halo<64, 3, 3, 32, float>(d, s);
-        else rc = npw <= 2 ? launch_halo<64, 2, 3, 64, float>(d, s) : launch_halo<64, 3, 3, 64, float>(d, s);
+            rc = npw <= 2 ? route(R_HF_64_2_32) + launch_halo<64, 2, 3, 32, float>(d, s) : route(R_HF_64_3_32) + launch_halo<64, 3, 3, 32, float>(d, s);
+        else rc = npw <= 2 ? route(R_HF_64_2_64) + launch_halo<64, 2, 3, 64, float>(d, s) : route(R_HF_64_3_64) + launch_halo<64, 3, 3, 64, float>(d, s);
     } else if (d.dtype == MDM_F32) {
         // exact-fp32 MFMA kernel; 128 x 128 tiles when that still gives about one workgroup per CU
         const bool big32 = d.M >= 128 && d.N >= 128 && (int64_t)cdiv(d.M, 128) * cdiv(d.N, 128) * grid.z >= kBigMinTiles;
-        rc = big32 ? launch_f32_mfma<128, 128>(d, dim3((unsigned)((int64_t)cdiv(d.M, 128) * cdiv(d.N, 128)), 1, grid.z), s)
-                   : launch_f32_mfma<64, 64>(d, grid, s);
+        rc = big32 ? route(d.layout == 0 && d.f32_split ? R_F32_128_SPLIT : R_F32_128) +
+                         launch_f32_mfma<128, 128>(d, dim3((unsigned)((int64_t)cdiv(d.M, 128) * cdiv(d.N, 128)), 1, grid.z), s)
+                   : route(R_F32_64) + launch_f32_mfma<64, 64>(d, grid, s);
     } else if (thin_conv(d)) {
         // the 8-channel ends of the U-Net: the first convolution and the data gradient of the last
         const unsigned nb = (unsigned)std::min(cdiv(cdiv(d.M, 16), 4), 1024);
         switch (cdiv(d.N, 16)) {
-            case 1: hipLaunchKernelGGL((conv_thin_k_kernel<1>), dim3(nb), dim3(256), 0, s, d); break;
-            case 2: hipLaunchKernelGGL((conv_thin_k_kernel<2>), dim3(nb), dim3(256), 0, s, d); break;
-            case 3: case 4: hipLaunchKernelGGL((conv_thin_k_kernel<4>), dim3(nb), dim3(256), 0, s, d); break;
-            default: hipLaunchKernelGGL((conv_thin_k_kernel<8>), dim3(nb), dim3(256), 0, s, d); break;
+            case 1: route(R_THIN_1); hipLaunchKernelGGL((conv_thin_k_kernel<1>), dim3(nb), dim3(256), 0, s, d); break;
+            case 2: route(R_THIN_2); hipLaunchKernelGGL((conv_thin_k_kernel<2>), dim3(nb), dim3(256), 0, s, d); break;
+            case 3: case 4: route(R_THIN_4); hipLaunchKernelGGL((conv_thin_k_kernel<4>), dim3(nb), dim3(256), 0, s, d); break;
+            default: route(R_THIN_8); hipLaunchKernelGGL((conv_thin_k_kernel<8>), dim3(nb), dim3(256), 0, s, d); break;
         }
     } else if (const ConvVar cv = conv_variant(d, r, grid.z)) {
         const dim3 g2((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 128)), 1, grid.z);
         switch (cv) {
-            case CV_H256_4: rc = launch_halo<256, 4, MDM_NSB256>(d, s); break;
-            case CV_H256_6: rc = launch_halo<256, 6, MDM_NSB256>(d, s); break;
-            case CV_H128_3: rc = launch_halo<128, 3, 3>(d, s); break;
-            case CV_H128_4: rc = launch_halo<128, 4, 3>(d, s); break;
-            case CV_H128_6: rc = launch_halo<128, 6, 3>(d, s); break;
-            case CV_H64_2_32: rc = launch_halo<64, 2, 3, 32>(d, s); break;
-            case CV_H64_3_32: rc = launch_halo<64, 3, 3, 32>(d, s); break;
-            case CV_H64_2_64: rc = launch_halo<64, 2, 3>(d, s); break;
-            case CV_H64_3_64: rc = launch_halo<64, 3, 3>(d, s); break;
-            case CV_S64_4: rc = launch_small<4>(d, s); break;
-            case CV_S64_5: rc = launch_small<5>(d, s); break;
-            case CV_S32_3: rc = launch_small<3, 32, 16>(d, s); break;
-            case CV_L128: rc = launch_lin2<128, 128, 3, 4, 2>(d, grid, s); break;
-            case CV_L64x128: rc = launch_lin2<64, 128, 3, 2, 4>(d, g2, s); break;
-            default: rc = launch_lin2<64, 64, 4, 4, 2>(d, grid, s); break;
+            case CV_H256_4: rc = route(R_H256_4) + launch_halo<256, 4, MDM_NSB256>(d, s); break;
+            case CV_H256_6: rc = route(R_H256_6) + launch_halo<256, 6, MDM_NSB256>(d, s); break;
+            case CV_H128_3: rc = route(R_H128_3) + launch_halo<128, 3, 3>(d, s); break;
+            case CV_H128_4: rc = route(R_H128_4) + launch_halo<128, 4, 3>(d, s); break;
+            case CV_H128_6: rc = route(R_H128_6) + launch_halo<128, 6, 3>(d, s); break;
+            case CV_H64_2_32: rc = route(R_H64_2_32) + launch_halo<64, 2, 3, 32>(d, s); break;
+            case CV_H64_3_32: rc = route(R_H64_3_32) + launch_halo<64, 3, 3, 32>(d, s); break;
+            case CV_H64_2_64: rc = route(R_H64_2_64) + launch_halo<64, 2, 3>(d, s); break;
+            case CV_H64_3_64: rc = route(R_H64_3_64) + launch_halo<64, 3, 3>(d, s); break;
+            case CV_S64_4: rc = route(R_SMALL_4) + launch_small<4>(d, s); break;
+            case CV_S64_5: rc = route(R_SMALL_5) + launch_small<5>(d, s); break;
+            case CV_S32_3: rc = route(R_SMALL_3) + launch_small<3, 32, 16>(d, s); break;
+            case CV_L128: rc = route(R_LIN2_128) + launch_lin2<128, 128, 3, 4, 2>(d, grid, s); break;
+            case CV_L64x128: rc = route(R_LIN2_64x128) + launch_lin2<64, 128, 3, 2, 4>(d, g2, s); break;
+            default: rc = route(R_LIN2_64) + launch_lin2<64, 64, 4, 4, 2>(d, grid, s); break;
         }
     } else if (wgrad_lin_eligible(d)) {
         MDM_REQUIRE((int64_t)grid.x * grid.z < (1ll << 30), "gemm: grid too large");
-        rc = big ? launch_wgrad_lin<128, 128, 3, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s)
-                 : launch_wgrad_lin<64, 64, 4, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s);
+        rc = big ? route(R_WGRAD_LIN_128) + launch_wgrad_lin<128, 128, 3, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s)
+                 : route(R_WGRAD_LIN_64) + launch_wgrad_lin<64, 64, 4, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s);
     } else if (ring_eligible(d)) {
-        rc = big ? launch_ring<128, 128, 3>(d, grid, s) : launch_ring<64, 64, 4>(d, grid, s);
+        rc = big ? route(R_RING_128) + launch_ring<128, 128, 3>(d, grid, s) : route(R_RING_64) + launch_ring<64, 64, 4>(d, grid, s);
     } else if (big) {
+        route(R_BF16_128);
         launch_bf16<128, 128>(d, grid, s);
     } else {
+        route(R_BF16_64);
         launch_bf16<64, 64>(d, grid, s);
     }
     if (rc) return rc;
     if (r.tap_split) {
+        route_stage(S_TAPSPLIT);
         const int64_t total4 = (int64_t)d.M * d.N / 4;
         int64_t nb = (total4 + 255) / 256;
         hipLaunchKernelGGL((splitk_epilogue_kernel<bf16_t>), dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, s, d);
     } else if (d.splitk > 1 && d.ws) {
+        route_stage(S_SPLITK);
         const int64_t total4 = (int64_t)r.zouter * d.M * d.N / 4;
         int64_t nb = (total4 + 255) / 256;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, s,
@@ -4284,6 +4360,18 @@ extern "C" int mdm_gemm(const mdm_gemm_desc* desc_host, void* stream) {
     return gemm_launch(desc_host, pick_stream(stream));
 }
 
+extern "C" const char* mdm_gemm_last_route(void) { return g_route >= 0 ? kRouteName[g_route] : "none"; }
+
+extern "C" int mdm_gemm_route_names(const char** out, int cap) {
+    int n = 0;
+    for (int i = 0; i < R_COUNT * 3; ++i) {
+        if (!(kRouteStages[i / 3] & (1 << (i % 3)))) continue;
+        if (out && n < cap) out[n] = kRouteName[i];
+        ++n;
+    }
+    return n;
+}
+
 // ---- two independent convolutions in one launch (conv_pair_kernel)
 template <int BM, int NPW, int BN, int NSB, int LBM, int LBN, int LNS, int LWR, int LWC>
 static int launch_pair(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int nb, hipStream_t s) {
@@ -4334,21 +4422,23 @@ extern "C" int mdm_gemm_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b
     // `b` must be a conv_lin2 launch of its own with no second stage (no split reduction), `a` a halo launch; the four pairs
     // below are the ones a unet6 step produces (4x4, 8x8, 16x16, 32x32 maps).  Anything else: two launches, same results.
     const bool b_plain = zb == 1 && !rb.tap_split && !(b.splitk > 1) && rb.tiles < (1ll << 20) && !b.gnb_x && !b.gnf_out;
-    int rc = -2;
+    int rc = kNotTaken;
+    g_route = -1;
     if (b_plain && za == 1) {
         const int nb64 = (int)rb.tiles, nb64x128 = (int)((int64_t)cdiv(b.M, 64) * cdiv(b.N, 128));
-        if (va == CV_S64_4 && vb == CV_L64) rc = launch_pair_small<4>(a, b, nb64, s);
-        else if (va == CV_S64_5 && vb == CV_L64) rc = launch_pair_small<5>(a, b, nb64, s);
-        else if (va == CV_S32_3 && vb == CV_L64) rc = launch_pair_small<3, 32, 16>(a, b, nb64, s);
-        else if (va == CV_H64_2_32 && vb == CV_L64) rc = launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
-        else if (va == CV_H64_3_32 && vb == CV_L64) rc = launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
-        else if (va == CV_H128_3 && vb == CV_L64x128) rc = launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>(a, b, nb64x128, s);
-        else if (va == CV_H128_3 && vb == CV_L64) rc = launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
-        else if (va == CV_H256_6 && vb == CV_L128) rc = launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>(a, b, nb64, s);
+        if (va == CV_S64_4 && vb == CV_L64) rc = route(R_PAIR_SMALL_4) + launch_pair_small<4>(a, b, nb64, s);
+        else if (va == CV_S64_5 && vb == CV_L64) rc = route(R_PAIR_SMALL_5) + launch_pair_small<5>(a, b, nb64, s);
+        else if (va == CV_S32_3 && vb == CV_L64) rc = route(R_PAIR_SMALL_3) + launch_pair_small<3, 32, 16>(a, b, nb64, s);
+        else if (va == CV_H64_2_32 && vb == CV_L64) rc = route(R_PAIR_64_2) + launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
+        else if (va == CV_H64_3_32 && vb == CV_L64) rc = route(R_PAIR_64_3) + launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
+        else if (va == CV_H128_3 && vb == CV_L64x128) rc = route(R_PAIR_128_L64x128) + launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>(a, b, nb64x128, s);
+        else if (va == CV_H128_3 && vb == CV_L64) rc = route(R_PAIR_128_L64) + launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
+        else if (va == CV_H256_6 && vb == CV_L128) rc = route(R_PAIR_256_L128) + launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>(a, b, nb64, s);
     }
-    if (rc == -2) {
+    if (rc == kNotTaken) {
         rc = gemm_launch(a_host, s);
         if (rc == 0) rc = gemm_launch(b_host, s);
+        route(R_PAIR_TWO);
         return rc;
     }
     if (rc) return rc;
@@ -4730,6 +4820,8 @@ extern "C" int mdm_wgrad_group_launch(void* handle, void* stream) {
         MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     }
     configured = true;
+    route(g->n_taps_items > 0 ? R_WGROUP_TAPS : R_WGROUP);
+    if (!g->reduces.empty()) route_stage(S_SPLITK);
     if (g->n_taps_items > 0) {
         const int tb = g->taps_blocks < g->n_taps_items ? g->taps_blocks : g->n_taps_items;
         hipLaunchKernelGGL(wgrad_taps_group_kernel, dim3((unsigned)tb), dim3(512), bytes, s, g->descs_dev, g->taps_items_dev, g->n_taps_items, g->slots_dev);

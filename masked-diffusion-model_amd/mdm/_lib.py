@@ -56,6 +56,8 @@ _PROTOS = {
     "mdm_gemm_plan": ([C.POINTER(GemmDesc), C.POINTER(i32), C.POINTER(i64)], i32),
     "mdm_gemm_can_fuse_gn_bwd": ([C.POINTER(GemmDesc), i32], i32),
     "mdm_gemm_can_fuse_gn_fwd": ([C.POINTER(GemmDesc), i32], i32),
+    "mdm_gemm_last_route": ([], C.c_char_p),
+    "mdm_gemm_route_names": ([C.POINTER(C.c_char_p), i32], i32),
     "mdm_groupnorm_fwd": ([i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, vp, vp], i32),
     "mdm_groupnorm_bwd": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
     "mdm_groupnorm_bwd_sums": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp], i32),
@@ -437,6 +439,20 @@ def chained(rec, device, min_len=2):
             run.append((i, descs))
     flush()
     return out
+
+
+def last_route():
+    """Kernel (and second stage) of the last mdm_gemm / mdm_gemm_pair / wgrad group launch on this thread (mdm_gemm_last_route)."""
+    return load().mdm_gemm_last_route().decode()
+
+
+def route_names():
+    """Every name last_route() can return."""
+    lib = load()
+    n = lib.mdm_gemm_route_names(None, 0)
+    arr = (C.c_char_p * n)()
+    lib.mdm_gemm_route_names(arr, n)
+    return [v.decode() for v in arr]
 
 
 def wgrad_group_accepts(**kw):
