@@ -179,6 +179,25 @@ int mdm_wgrad_group_launch(void* handle, void* stream);
 int mdm_wgrad_group_destroy(void* handle);
 
 /* ------------------------------------------------------------------------- *
+ * fp32 weight gradient with SPLIT products (autograd's conv2d weight gradient, unet6.py:232-235 backward, for fp32 training:
+ * UNet(dtype=F32, f32_products="split", grad_products="split")).  Same descriptor as a mdm_gemm weight gradient: dtype MDM_F32,
+ * layout 2, conv, out_f32, D0 = dW[tap][M = Cout][N = Cin] (+)= sum_pixels dY[p][m] x[gather(p, tap)][n] -- any geometry the gather
+ * takes (3x3 stride 1 / 2, folded x2 upsample, 1x1, one or two sources).  Both operands are fp32 activations, split in registers on
+ * their way into LDS (x = hi + lo, hi = bf16(x), lo = bf16(x - hi)); a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16
+ * with fp32 accumulation (~2^-16 relative per product instead of 2^-24).  The reduction over the pixels is split over grid z when
+ * `ws` can hold the partial slabs ([split][tap][M][N] fp32, dense destination required: ldd0 == N, dtap == M N): plain stores, then
+ * one launch sums them in split order -- no float atomics, the same bits on every run.  descriptor.splitk > 0 is honoured, 0 = choose.
+ * Plain epilogue only: no bias / dbias / rowvec / resid / D1, alpha 1 (the bias gradient stays on mdm_colsum).
+ *   mdm_conv_wgrad_split_plan   the split count and workspace bytes it would use for this descriptor.  No launch.
+ *   mdm_wgrad_split_last_route  route record (tests): "wgrad_split<128>", "wgrad_split<64>", either with "+splitk", or "none"
+ *                               (before the first call or when validation failed).  Host-side, this thread.
+ * Replaces nothing upstream (a faster form of the same contraction mdm_gemm runs exactly).
+ * ------------------------------------------------------------------------- */
+int mdm_conv_wgrad_split(const mdm_gemm_desc* desc_host, void* stream);
+int mdm_conv_wgrad_split_plan(const mdm_gemm_desc* desc_host, int* splitk_out, int64_t* ws_bytes_out);
+const char* mdm_wgrad_split_last_route(void);
+
+/* ------------------------------------------------------------------------- *
  * A CHAIN of small-map convolutions as one persistent launch.  The trunk of unet6 (4x4 and 8x8 maps: ResidualBlocks unet6.py:336-362,
  * AttentionBlock projections :296-333, the level loop :478-506) is ~130 launches of 7-16 us per step at 32 images per GPU, most of
  * each being launch boundary, prologue and drain.  A chain takes a run of consecutive mdm_gemm / mdm_gemm_pair calls whose tiles are
@@ -425,6 +444,13 @@ int mdm_transpose_shadow_bf16(const void* Pb, void* PT, const int64_t* tiles, in
  * the arrangement the split kernels make of their input rows in LDS.  Replaces nothing upstream: it is
  * how the fp32 `F.conv2d` of unet6.py:232-235 reaches the bf16 MFMA pipe at ~fp32 accuracy. */
 int mdm_split_shadow(const float* P, float* Ps, const int64_t* segs, int nseg, void* stream);
+/* The B_split shadow of the data gradient: for each filter segs[i] = {element offset, taps, Cout, Cin} (device, int64 x4; Cout % 32 == 0,
+ * offset % 4 == 0) of a [tap][Cout][Cin] filter in P, PsT[off + tap' Cin Cout + ci Cout + co] = P[off + (taps-1-tap') Cout Cin + co Cin + ci]
+ * -- taps flipped, each tap transposed to [Cin][Cout] -- in mdm_split_shadow's hi / lo arrangement over the 32-element blocks of every
+ * row of Cout.  With it the data gradient of a 3x3 stride-1 pad-1 or a 1x1 convolution is a plain FORWARD convolution of dY
+ * (layout 0, transposed = 0, Ck = Cout, N = Cin, B = B_split = this view) and runs on the split forward routes of mdm_gemm.
+ * Replaces nothing upstream: it is how autograd's conv2d data gradient (unet6.py:232-235 backward) reaches the bf16 MFMA pipe. */
+int mdm_split_shadow_t(const float* P, float* PsT, const int64_t* segs, int nseg, void* stream);
 int mdm_fill_f32(float* p, float v, int64_t n, void* stream);
 /* base[off .. off + len) = v for nseg segments segs[i] = {off, len} (device, int64 pairs; len % 4 == 0, len <= 4096, off % 4 == 0):
  * the per-step zeroing of the ACCUMULATED gradient slots only (biases, GroupNorm scales: `optimizer.zero_grad()` at

@@ -4841,6 +4841,223 @@ extern "C" int mdm_wgrad_group_destroy(void* handle) {
     return 0;
 }
 
+// ---- fp32 weight gradient with split products (mdm_conv_wgrad_split) ---------------------------------------------
+// dW[tap][m][n] (+)= sum_k dY[k][m] * x[gather(k, tap)][n], both operands fp32 activations: no precomputed shadow.  Every thread
+// loads a 4 (k) x 4 (m or n) block as four 16-byte rows, splits each value into hi = bf16(x), lo = bf16(x - hi) on its way into LDS
+// and writes, per column, its 4 consecutive k as 8 bytes of hi halves at byte 8 (k / 4) and 8 bytes of lo halves at 64 + 8 (k / 4) of
+// that column's 128-byte row -- the row image of gemm_f32_mfma_kernel's SPLIT path, so a lane group's fragment is 8 consecutive k of hi
+// (or lo) and a 32-deep slab is three v_mfma_f32_16x16x32_bf16 per fragment pair (b.hi a.lo, b.lo a.hi, b.hi a.hi; fp32 accumulate).
+// grid = (tiles, taps, splitk); split k-ranges are whole 32-slabs; a split writes its partial tile with plain stores into
+// ws[split][tap][M][N], which splitk_reduce_kernel sums in split order: no float atomics, the same bits on every run.
+namespace mdm {
+template <int BT>
+__global__ __launch_bounds__(256) void wgrad_split_kernel(mdm_gemm_desc d, int chunk) {
+    constexpr int BK = 32, LD = BK + 4;                                     // row = 32 k: 64 B hi | 64 B lo, padded to 144 B
+    constexpr int STAGE = 2 * BT * LD;                                      // A rows (m) then B rows (n)
+    constexpr int WT = BT / 2, NF = WT / 16;                                // wave tile, fragments per wave and dimension
+    constexpr int QPO = 2 * BT, NQ = 2 * QPO / 256;                         // 4x4 blocks per operand and slab; per thread
+    extern __shared__ __attribute__((aligned(16))) float wsm[];             // [2][STAGE]
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1;
+    const int tiles_n = (d.N + BT - 1) / BT;
+    const int m0 = (blockIdx.x / tiles_n) * BT, n0 = (blockIdx.x % tiles_n) * BT;
+    const int tap = blockIdx.y, ks = blockIdx.z;
+    const int ty = tap / d.KW, tx = tap - ty * d.KW;
+    const int kbeg = ks * chunk, kend = min(d.K, kbeg + chunk);
+    const int nk = kend > kbeg ? (kend - kbeg + BK - 1) / BK : 0;
+
+    float4 r[NQ][4];
+    auto load_tiles = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int q = t + 256 * i, op = q / QPO, qq = q - op * QPO;    // op: wave-uniform (0 = dY, 1 = x)
+            const int k4 = qq / (BT / 4), c = 4 * (qq - k4 * (BT / 4));
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int k = k0 + 4 * k4 + kk;
+                const float* p = nullptr;
+                if (k < kend) {
+                    if (op == 0) {
+                        if (m0 + c < d.M) p = reinterpret_cast<const float*>(d.A) + (int64_t)k * d.lda + m0 + c;
+                    } else if (n0 + c < d.N) {
+                        p = pix_chan_ptr<float>(d, gather_pix(d, decode_row(d, k), ty, tx), n0 + c);
+                    }
+                }
+                r[i][kk] = p ? *reinterpret_cast<const float4*>(p) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    };
+    auto store_tiles = [&](int buf) {
+        float* S = wsm + buf * STAGE;
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const int q = t + 256 * i, op = q / QPO, qq = q - op * QPO;
+            const int k4 = qq / (BT / 4), c = 4 * (qq - k4 * (BT / 4));
+            const float v[4][4] = {{r[i][0].x, r[i][1].x, r[i][2].x, r[i][3].x}, {r[i][0].y, r[i][1].y, r[i][2].y, r[i][3].y},
+                                   {r[i][0].z, r[i][1].z, r[i][2].z, r[i][3].z}, {r[i][0].w, r[i][1].w, r[i][2].w, r[i][3].w}};
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {                               // column c + cc: its 4 consecutive k
+                bf16_t h[4];
+                uint2 hi, lo;
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) h[kk] = f2bf(v[cc][kk]);
+                hi.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+                hi.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+                lo.x = (uint32_t)f2bf(v[cc][0] - bf2f(h[0])) | ((uint32_t)f2bf(v[cc][1] - bf2f(h[1])) << 16);
+                lo.y = (uint32_t)f2bf(v[cc][2] - bf2f(h[2])) | ((uint32_t)f2bf(v[cc][3] - bf2f(h[3])) << 16);
+                char* row = reinterpret_cast<char*>(S + (op * BT + c + cc) * LD) + 8 * k4;
+                *reinterpret_cast<uint2*>(row) = hi;
+                *reinterpret_cast<uint2*>(row + 64) = lo;
+            }
+        }
+    };
+
+    f32x4 acc[NF][NF];
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+        for (int j = 0; j < NF; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (nk > 0) {
+        load_tiles(kbeg);
+        store_tiles(0);
+        if (nk > 1) load_tiles(kbeg + BK);
+    }
+    __syncthreads();
+    const int frow = lane & 15, fb = 16 * (lane >> 4);
+    for (int it = 0; it < nk; ++it) {
+        const int cur = it & 1;
+        if (it + 1 < nk) store_tiles(cur ^ 1);
+        if (it + 2 < nk) load_tiles(kbeg + (it + 2) * BK);
+        const float* S = wsm + cur * STAGE;
+        bf16x8 ah[NF], al[NF], bh[NF], bl[NF];
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const char* p = reinterpret_cast<const char*>(S + (wr * WT + i * 16 + frow) * LD) + fb;
+            ah[i] = *reinterpret_cast<const bf16x8*>(p);
+            al[i] = *reinterpret_cast<const bf16x8*>(p + 64);
+        }
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            const char* p = reinterpret_cast<const char*>(S + (BT + wc * WT + j * 16 + frow) * LD) + fb;
+            bh[j] = *reinterpret_cast<const bf16x8*>(p);
+            bl[j] = *reinterpret_cast<const bf16x8*>(p + 64);
+        }
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < NF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], al[i], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < NF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[j], ah[i], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int j = 0; j < NF; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[j], ah[i], acc[i][j], 0, 0, 0);
+        __syncthreads();
+    }
+    // accumulator: D[m = lane & 15][n = 4 (lane >> 4) + reg]
+    const int64_t MN = (int64_t)d.M * d.N;
+#pragma unroll
+    for (int i = 0; i < NF; ++i) {
+        const int m = m0 + wr * WT + i * 16 + (lane & 15);
+        if (m >= d.M) continue;
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            const int n = n0 + wc * WT + j * 16 + 4 * (lane >> 4);
+            if (n >= d.N) continue;
+            float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
+            if (gridDim.z > 1) {
+                store4(reinterpret_cast<float*>(d.ws) + ((int64_t)ks * gridDim.y + tap) * MN + (int64_t)m * d.N + n, v);
+            } else {
+                float* p = reinterpret_cast<float*>(d.D0) + (int64_t)tap * d.dtap + (int64_t)m * d.ldd0 + n;
+                if (d.acc0) { const float4 o = load4(p); v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
+                store4(p, v);
+            }
+        }
+    }
+}
+
+static thread_local const char* g_wgrad_split_route = "none";
+
+struct WgradSplitPlan { int bt, splitk, chunk; int64_t tiles, ws_bytes; };
+static int wgrad_split_plan(const mdm_gemm_desc& d, WgradSplitPlan& p) {
+    MDM_REQUIRE(d.dtype == MDM_F32 && d.layout == 2 && d.conv && d.out_f32, "wgrad_split: needs an fp32 layout-2 convolution descriptor");
+    MDM_REQUIRE(d.batch == 1 && d.alpha == 1.0f && !d.bias && !d.rowvec && !d.resid && !d.dbias && !d.D1 && d.N0 == d.N &&
+                !d.gnb_x && !d.gnf_out, "wgrad_split: plain dW epilogue only (the bias gradient runs on mdm_colsum)");
+    MDM_REQUIRE(d.M % 4 == 0 && d.N % 4 == 0 && d.lda % 4 == 0 && d.lda >= d.M && d.ldd0 % 4 == 0 && d.ldd0 >= d.N,
+                "wgrad_split: M=%d N=%d lda=%d ldd0=%d", d.M, d.N, d.lda, d.ldd0);
+    MDM_REQUIRE(d.C0 % 4 == 0 && d.C1 % 4 == 0 && d.ld0 % 4 == 0 && (d.C1 == 0 || d.ld1 % 4 == 0) && d.ld0 >= d.C0 && d.ld1 >= d.C1,
+                "wgrad_split: source channels / pitches must be multiples of 4");
+    MDM_REQUIRE(d.K % (d.OH * d.OW) == 0, "wgrad_split: K=%d is not images x OH x OW", d.K);
+    MDM_REQUIRE(d.KH * d.KW <= 65535, "wgrad_split: too many taps");
+    p.bt = (d.M >= 128 && d.N >= 128) ? 128 : 64;
+    p.tiles = (int64_t)cdiv(d.M, p.bt) * cdiv(d.N, p.bt);
+    MDM_REQUIRE(p.tiles < (1ll << 31), "wgrad_split: grid too large");
+    const int taps = d.KH * d.KW, nslab = cdiv(d.K, 32);
+    const int64_t slab = (int64_t)taps * d.M * d.N * 4;
+    // split-K: ~two workgroups per CU over (tile, tap, split), every split >= 8 slabs of 32 pixels, within the workspace;
+    // descriptor.splitk > 0 is honoured (capped by the workspace).  Partial slabs need a dense [tap][M][N] destination.
+    const bool dense = d.ldd0 == d.N && d.dtap == (int64_t)d.M * d.N;
+    int sk = d.splitk > 0 ? d.splitk : (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(512, p.tiles * taps), nslab / 8));
+    if (sk > nslab) sk = nslab;
+    if (!dense || !d.ws || d.ws_bytes < 2 * slab) sk = 1;
+    else if ((int64_t)sk * slab > d.ws_bytes) sk = (int)(d.ws_bytes / slab);
+    if (sk > 65535) sk = 65535;
+    p.splitk = sk < 1 ? 1 : sk;
+    p.chunk = cdiv(nslab, p.splitk) * 32;
+    p.splitk = cdiv(d.K, p.chunk);                          // no empty trailing splits
+    p.ws_bytes = p.splitk > 1 ? p.splitk * slab : 0;
+    return 0;
+}
+template <int BT>
+static int launch_wgrad_split(const mdm_gemm_desc& d, const WgradSplitPlan& p, hipStream_t s) {
+    constexpr int bytes = 2 * 2 * BT * 36 * 4;
+    static bool configured = false;
+    if (!configured) {
+        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_kernel<BT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        configured = true;
+    }
+    hipLaunchKernelGGL((wgrad_split_kernel<BT>), dim3((unsigned)p.tiles, (unsigned)(d.KH * d.KW), (unsigned)p.splitk), dim3(256), bytes, s, d,
+                       p.chunk);
+    return 0;
+}
+}  // namespace mdm
+
+extern "C" int mdm_conv_wgrad_split(const mdm_gemm_desc* desc_host, void* stream) {
+    g_wgrad_split_route = "none";
+    MDM_REQUIRE(desc_host != nullptr, "wgrad_split: null descriptor");
+    mdm_gemm_desc d = *desc_host;
+    if (d.N0 == 0) d.N0 = d.N;
+    if (int rc = validate(d)) return rc;
+    WgradSplitPlan p;
+    if (int rc = wgrad_split_plan(d, p)) return rc;
+    hipStream_t s = pick_stream(stream);
+    int rc = p.bt == 128 ? launch_wgrad_split<128>(d, p, s) : launch_wgrad_split<64>(d, p, s);
+    if (rc) return rc;
+    if (p.splitk > 1) {
+        const int64_t total4 = (int64_t)d.KH * d.KW * d.M * d.N / 4;
+        const int64_t nb = (total4 + 255) / 256;
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, s, reinterpret_cast<const float*>(d.ws),
+                           p.splitk, total4, reinterpret_cast<float*>(d.D0), d.acc0);
+        g_wgrad_split_route = p.bt == 128 ? "wgrad_split<128>+splitk" : "wgrad_split<64>+splitk";
+    } else {
+        g_wgrad_split_route = p.bt == 128 ? "wgrad_split<128>" : "wgrad_split<64>";
+    }
+    return launch_status("wgrad_split launch");
+}
+extern "C" int mdm_conv_wgrad_split_plan(const mdm_gemm_desc* desc_host, int* splitk_out, int64_t* ws_bytes_out) {
+    MDM_REQUIRE(desc_host != nullptr, "wgrad_split: null descriptor");
+    mdm_gemm_desc d = *desc_host;
+    if (d.N0 == 0) d.N0 = d.N;
+    if (int rc = validate(d)) return rc;
+    WgradSplitPlan p;
+    if (int rc = wgrad_split_plan(d, p)) return rc;
+    if (splitk_out) *splitk_out = p.splitk;
+    if (ws_bytes_out) *ws_bytes_out = p.ws_bytes;
+    return 0;
+}
+extern "C" const char* mdm_wgrad_split_last_route(void) { return g_wgrad_split_route; }
+
 #ifdef MDM_STAMP
 extern "C" int mdm_debug_stamps_n(unsigned long long* out, int n_records, int reset) {      // out: n_records * 32 entries
     if (n_records < 1 || n_records > MDM_STAMP_RECS) return -1;

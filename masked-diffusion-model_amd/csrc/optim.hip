@@ -117,6 +117,32 @@ __global__ __launch_bounds__(256) void split_shadow_kernel(const float* P, float
     }
 }
 
+// The same shadow of the per-tap TRANSPOSED, tap-FLIPPED filters: PsT[off + tap' Cin Cout + ci Cout + co] holds
+// P[off + (taps - 1 - tap') Cout Cin + co Cin + ci] in split_shadow_kernel's arrangement over the 32-element blocks of a row of Cout.
+// One thread per (tap', ci, block, g): lanes walk ci, so each of its eight 4-byte loads is one coalesced row segment of the
+// [Cout][Cin] source (a 16-byte load would need four ci per lane and a transpose in registers; this runs once per optimizer step).
+// segs[i] = {element offset, taps, Cout, Cin}; blockIdx.y = filter.
+__global__ __launch_bounds__(256) void split_shadow_t_kernel(const float* P, float* PsT, const int64_t* segs) {
+    const int64_t off = segs[4 * blockIdx.y], taps = segs[4 * blockIdx.y + 1], co_n = segs[4 * blockIdx.y + 2], ci_n = segs[4 * blockIdx.y + 3];
+    const int64_t per_tap = (co_n / 8) * ci_n;                  // (block, g) pairs x ci
+    for (int64_t id = (int64_t)blockIdx.x * 256 + threadIdx.x; id < taps * per_tap; id += (int64_t)gridDim.x * 256) {
+        const int64_t tp = id / per_tap, rem = id - tp * per_tap, bg = rem / ci_n, ci = rem - bg * ci_n;
+        const int64_t co = (bg >> 2) * 32 + (bg & 3) * 4;
+        const float* src = P + off + (taps - 1 - tp) * co_n * ci_n + co * ci_n + ci;
+        uint32_t h[4], l[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float xa = src[k * ci_n], xb = src[(16 + k) * ci_n];
+            const bf16_t h0 = f2bf(xa), h1 = f2bf(xb);
+            h[k] = (uint32_t)h0 | ((uint32_t)h1 << 16);
+            l[k] = (uint32_t)f2bf(xa - bf2f(h0)) | ((uint32_t)f2bf(xb - bf2f(h1)) << 16);
+        }
+        float* dst = PsT + off + tp * co_n * ci_n + ci * co_n + co;
+        *reinterpret_cast<uint4*>(dst) = make_uint4(h[0], h[1], h[2], h[3]);
+        *reinterpret_cast<uint4*>(dst + 16) = make_uint4(l[0], l[1], l[2], l[3]);
+    }
+}
+
 __global__ void cast_bf16_kernel(const float* src, bf16_t* dst, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = f2bf(src[i]);
 }
@@ -163,6 +189,12 @@ extern "C" int mdm_split_shadow(const float* P, float* Ps, const int64_t* segs, 
     MDM_REQUIRE((((uintptr_t)P | (uintptr_t)Ps) & 15) == 0, "split_shadow: buffers must be 16-byte aligned");
     hipLaunchKernelGGL(split_shadow_kernel, dim3(64, (unsigned)nseg), dim3(256), 0, (hipStream_t)stream, P, Ps, segs);
     return launch_status("split_shadow");
+}
+extern "C" int mdm_split_shadow_t(const float* P, float* PsT, const int64_t* segs, int nseg, void* stream) {
+    MDM_REQUIRE(P && PsT && segs && nseg > 0 && nseg <= 65535, "split_shadow_t: bad arguments");
+    MDM_REQUIRE((((uintptr_t)P | (uintptr_t)PsT) & 15) == 0, "split_shadow_t: buffers must be 16-byte aligned");
+    hipLaunchKernelGGL(split_shadow_t_kernel, dim3(64, (unsigned)nseg), dim3(256), 0, (hipStream_t)stream, P, PsT, segs);
+    return launch_status("split_shadow_t");
 }
 extern "C" int mdm_cast_bf16(const float* src, void* dst, int64_t n, void* stream) {
     hipLaunchKernelGGL(cast_bf16_kernel, dim3(ogrid(n)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n);

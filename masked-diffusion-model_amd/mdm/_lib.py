@@ -104,6 +104,10 @@ _PROTOS = {
     "mdm_cast_bf16": ([vp, vp, i64, vp], i32),
     "mdm_transpose_shadow_bf16": ([vp, vp, vp, i32, vp], i32),
     "mdm_split_shadow": ([vp, vp, vp, i32, vp], i32),
+    "mdm_split_shadow_t": ([vp, vp, vp, i32, vp], i32),
+    "mdm_conv_wgrad_split": ([C.POINTER(GemmDesc), vp], i32),
+    "mdm_conv_wgrad_split_plan": ([C.POINTER(GemmDesc), C.POINTER(i32), C.POINTER(i64)], i32),
+    "mdm_wgrad_split_last_route": ([], C.c_char_p),
     "mdm_fill_f32": ([vp, f32, i64, vp], i32),
     "mdm_fill_segments_f32": ([vp, vp, i32, f32, vp], i32),
     "mdm_graph_begin": ([vp], i32),
@@ -444,6 +448,40 @@ def chained(rec, device, min_len=2):
 def last_route():
     """Kernel (and second stage) of the last mdm_gemm / mdm_gemm_pair / wgrad group launch on this thread (mdm_gemm_last_route)."""
     return load().mdm_gemm_last_route().decode()
+
+
+def wgrad_split_last_route():
+    """Kernel (and second stage) of the last mdm_conv_wgrad_split call on this thread (mdm_wgrad_split_last_route)."""
+    return load().mdm_wgrad_split_last_route().decode()
+
+
+def wgrad_split(**kw):
+    """The weight-gradient fields of a descriptor through mdm_conv_wgrad_split (split products): launch / record it."""
+    flops = kw.pop("_flops", None)
+    d = _desc(kw)
+    if _recording is not None:
+        _recording.keep.append((d, kw))
+        _recording.flops[len(_recording.calls)] = (flops if flops is not None else 2.0 * d.M * d.N * d.K, d.dtype)
+    call("mdm_conv_wgrad_split", C.byref(d), stream())
+    return d
+
+
+def wgrad_split_plan(**kw):
+    """(split count, workspace bytes) mdm_conv_wgrad_split would use for these fields; no launch."""
+    kw.pop("_flops", None)
+    d = _desc(kw)
+    sk, nb = i32(), i64()
+    check(load().mdm_conv_wgrad_split_plan(C.byref(d), C.byref(sk), C.byref(nb)), "mdm_conv_wgrad_split_plan")
+    return sk.value, nb.value
+
+
+def note(fn):
+    """Run the host callable `fn()` at this point of the launch sequence: at once, or -- inside a Recording -- every time the
+    recording is replayed or captured (host code only, nothing is enqueued)."""
+    if _recording is not None:
+        _recording.calls.append(("note", lambda st: (fn(), 0)[1], ()))
+        return
+    fn()
 
 
 def route_names():

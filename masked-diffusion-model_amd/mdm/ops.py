@@ -176,6 +176,61 @@ def conv_wgrad_ws_bytes(dt, g: ConvGeom):
     return _lib.gemm_plan(**f)[1]
 
 
+def split_grad_reason(g: ConvGeom, which):
+    """None if the `which` ("dgrad" | "wgrad") gradient of this convolution runs with split products under
+    UNet(grad_products="split"), else why it stays exact fp32.  Both need whole 32-channel blocks on either side (the
+    8-channel ends of the net stay exact); the data gradient as a forward convolution of dY through the flipped, transposed
+    shadow (mdm_split_shadow_t) exists for stride-1 3x3 "same" and 1x1 convolutions whose Cin is a whole 64-channel tile."""
+    if g.Cin % 32 or g.Cout % 32:
+        return "channels"
+    if which == "wgrad":
+        return None
+    if g.stride != 1:
+        return "stride2"
+    same3 = g.KH == 3 and g.KW == 3 and g.pad_t == g.pad_b == g.pad_l == g.pad_r == 1
+    k1 = g.KH == 1 and g.KW == 1 and g.pad_t == g.pad_b == g.pad_l == g.pad_r == 0
+    if not (same3 or k1):
+        return "geometry"
+    if g.Cin % 64:
+        return "channels"
+    M = g.N * g.VH * g.VW
+    if same3:           # the pixel tiles of the halo kernel (csrc/gemm.hip halo_tile_f32): whole rows, whole images on small maps
+        pow2 = lambda v: v > 0 and (v & (v - 1)) == 0
+        pieces = lambda bm: ((bm // (g.VH * g.VW) if bm > g.VH * g.VW else 1) * ((g.VH if bm > g.VH * g.VW else bm // g.VW) + 2) *
+                             (g.VW + 2) + 7) // 8
+        if not (pow2(g.VH) and pow2(g.VW)):
+            return "geometry"
+        if g.VW in (4, 8):
+            if g.VH != g.VW or M % 64:
+                return "geometry"
+        elif g.VW not in (16, 32, 64) or not any(bm % g.VW == 0 and g.VH % (bm // g.VW) == 0 and M % bm == 0 and pieces(bm) <= 48
+                                                 for bm in (256, 128)):
+            return "geometry"
+    elif M < 64:
+        return "geometry"
+    return None
+
+
+def conv_dgrad_split_fields(g: ConvGeom, dy, wT_split, dst0, acc0, dst1=None, acc1=0):
+    """Data gradient dst[N,VH,VW,C0|C1] (=|+=) of a convolution split_grad_reason(g, "dgrad") accepts, as the FORWARD convolution
+    of dy through the flipped, per-tap transposed split shadow wT_split[tap][Cin][Cout] (ParamStore.ws_t): layout 0, transposed 0,
+    fp32 storage, products on the split forward routes of mdm_gemm (B = B_split; an fp32 descriptor only ever reads B_split there).
+    The two-destination epilogue (N0 / D1, acc0 / acc1) writes the gradients of a concatenated input."""
+    return dict(dtype=F32, layout=0, M=g.N * g.VH * g.VW, N=g.Cin, K=g.taps * g.Cout,
+                conv=1, OH=g.VH, OW=g.VW, IH=g.OH, IW=g.OW, KH=g.KH, KW=g.KW, stride=1,
+                pad_t=g.KH - 1 - g.pad_t, pad_l=g.KW - 1 - g.pad_l, transposed=0, ups=0, C0=g.Cout, C1=0, Ck=g.Cout,
+                src0=dy, src1=None, ld0=g.Cout, ld1=0, B=wT_split, B_split=wT_split, ldb=g.Cout, wtap=g.Cout * g.Cin,
+                D0=dst0, ldd0=g.C0, D1=dst1, ldd1=g.C1, N0=g.C0, acc0=acc0, acc1=acc1, _flops=conv_flops(g))
+
+
+def conv_wgrad_split(g: ConvGeom, dy, src0, src1, dw, ws=None, acc=1, splitk=0):
+    """dw[tap][Cout][Cin] (fp32) (+)= sum_pixels dy x gathered input with split products (mdm_conv_wgrad_split).  `ws`: fp32
+    split-K workspace tensor (partial slabs, summed in a fixed order); without it the reduction is not split."""
+    f = wgrad_fields(F32, g, dy, src0, src1, dw, splitk=splitk, ws=ws, acc=acc)
+    f.pop("dbias")
+    return _lib.wgrad_split(**f)
+
+
 def wgrad_group_split(g: ConvGeom, slabs_per_item=48):
     """k-splits of a weight gradient that runs inside a group: the group fills the chip, so a layer is only cut
     into work items of ~slabs_per_item 64-pixel slabs (never below 8) -- not into as many as fill 256 CUs alone."""

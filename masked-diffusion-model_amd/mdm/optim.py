@@ -65,6 +65,7 @@ class AdamW:
              ptr(self.hp), ptr(self.sqnorm), float(max_norm), float(gmul), stream())
         st.emit_transposed_shadow()
         st.emit_split_shadow()          # fp32 stores with split products: the filters' hi / lo shadow follows the weights
+        st.emit_split_shadow_t()        # ... and so does the flipped, transposed one of split-product gradients
 
     def step(self, max_norm=0.0):
         self.hyper()

@@ -136,6 +136,31 @@ class ParamStore:
             return None
         return self.Ps[e.off:e.off + e.n].view(e.ishape)
 
+    # -- split-product gradients: the filters once more, taps flipped and each tap transposed, as hi / lo pairs (mdm_split_shadow_t)
+    def enable_split_t(self):
+        """Allocate `PsT` (same offsets as P) for every conv filter whose Cout and Cin are whole 32-channel blocks: the data
+        gradient of such a layer is a forward convolution of dY through it (ops.conv_dgrad_split_fields)."""
+        if getattr(self, "PsT", None) is not None:
+            return
+        assert self.dtype == F32, "the split shadow belongs to an fp32 store"
+        segs = [(e.off,) + tuple(e.ishape) for e in self.entries.values()
+                if e.kind in ("conv", "convlin") and e.ishape[1] % 32 == 0 and e.ishape[2] % 32 == 0]
+        self.PsT = torch.zeros(self.size, device=self.device, dtype=torch.float32)
+        self.split_t_segs = torch.tensor(segs, dtype=torch.int64, device=self.device)
+        self.emit_split_shadow_t()
+
+    def emit_split_shadow_t(self):
+        if getattr(self, "PsT", None) is not None:
+            _lib.call("mdm_split_shadow_t", _lib.ptr(self.P), _lib.ptr(self.PsT), _lib.ptr(self.split_t_segs),
+                      int(self.split_t_segs.shape[0]), _lib.stream())
+
+    def ws_t(self, name):       # [tap][Cin][Cout] view of PsT (flipped taps), or None
+        e = self.entries[name]
+        if getattr(self, "PsT", None) is None or e.kind not in ("conv", "convlin") or e.ishape[1] % 32 or e.ishape[2] % 32:
+            return None
+        taps, co, ci = e.ishape
+        return self.PsT[e.off:e.off + e.n].view(taps, ci, co)
+
     def emit_transposed_shadow(self):
         if self.PbT is not None:
             # from the bf16 shadow the optimizer (or sync_shadow's cast) has just written: a third less traffic than from P
@@ -147,6 +172,7 @@ class ParamStore:
             ops.cast_bf16(self.P, self.Pb)
             self.emit_transposed_shadow()
         self.emit_split_shadow()
+        self.emit_split_shadow_t()
 
     # -- reference state_dict interchange
     def to_internal(self, name, t):
@@ -248,7 +274,14 @@ class _Conv:
             self.fwd_desc = _lib.gemm(**self._fwd_fields())
 
     def bwd(self, pair_a=None):
-        """pair_a: descriptor fields of another conv's data gradient (the block's conv2) to launch TOGETHER with this one's."""
+        """pair_a: descriptor fields of another conv's data gradient (the block's conv2) to launch TOGETHER with this one's.
+
+        grad_products="split" (fp32 training): the data gradient of a stride-1 3x3 / 1x1 layer is a forward convolution of dY through
+        the flipped, transposed split shadow (ops.conv_dgrad_split_fields; for a folded x2 upsample at the virtual resolution, then
+        sumpool2'd as always), the weight gradient runs on mdm_conv_wgrad_split, the bias gradient stays on mdm_colsum.  Exact fp32
+        remains, by design: stride-2 data gradients; both gradients of the 8-channel ends of the net (the first and last
+        convolution: not whole 32-channel blocks); layers whose Cin is not a whole 64-channel tile (data gradient only); and
+        everything that is not a convolution -- attention, GroupNorm, the time-embedding path, the loss and the optimizer."""
         n, st, g = self.net, self.net.store, self.g
         if getattr(self, "bwd_done", False):            # a skip projection whose backward ran next to conv2's
             return
@@ -275,9 +308,14 @@ class _Conv:
                 wf["ws"] = n.wgrad_slab(sk * g.taps * g.Cout * g.Cin)
                 wf["ws_bytes"] = wf["ws"].numel() * 4
             n.pending_wgrads.append((self, wf))
+        elif n.grad_products == "split" and ops.split_grad_reason(g, "wgrad") is None:
+            ops.conv_wgrad_split(g, dy, s0.data, s1.data if s1 else None, st.g(self.name + ".weight"), ws=n.splitk_ws)
+            self._note_route("wgrad", _lib.wgrad_split_last_route)
         else:
             ops.conv_wgrad(n.dt, g, dy, s0.data, s1.data if s1 else None, st.g(self.name + ".weight"), ws=n.splitk_ws,
                            dbias=st.g(self.name + ".bias") if fuse_bias else None)
+            if n.grad_products == "split":
+                n.grad_routes.setdefault(self.name, {})["wgrad"] = "exact:" + ops.split_grad_reason(g, "wgrad")
         if r is not None and r.needs_grad:       # y = conv(..) + resid  (unet6.py:333, 362): d(resid) += dy
             if r.grad_written and not (grouped and r.pending_add is None):
                 ops.add_(n.dt, r.grad, dy)
@@ -292,8 +330,17 @@ class _Conv:
         if n.dt == BF16:
             wmat = st.wT(self.name + ".weight")
             dgrad = lambda *a: ops.conv_dgrad_t(*a, ws=n.splitk_ws)     # small maps split the taps over the grid
+        elif n.grad_products == "split" and ops.split_grad_reason(g, "dgrad") is None:
+            # a forward convolution of dY through the flipped, transposed split shadow, on the split forward routes
+            wmat = st.ws_t(self.name + ".weight")
+
+            def dgrad(dt, g_, dy_, w_, d0, a0, d1=None, a1=0):
+                _lib.gemm(**ops.conv_dgrad_split_fields(g_, dy_, w_, d0, a0, d1, a1))
+                self._note_route("dgrad", _lib.last_route)
         else:
             dgrad, wmat = ops.conv_dgrad, st.w(self.name + ".weight")
+            if n.grad_products == "split":
+                n.grad_routes.setdefault(self.name, {})["dgrad"] = "exact:" + ops.split_grad_reason(g, "dgrad")
         # conv2 of a ResidualBlock with a skip projection: the projection's whole backward runs HERE, its data gradient in
         # the same launch as this one's (both read this block's dY; they write different tensors)
         mate = getattr(self, "pair_skip_bwd", None) if (n.pair_convs and n.dt == BF16 and not g.ups) else None
@@ -336,6 +383,20 @@ class _Conv:
             g0, a0, _ = n.grad_for_write(s0)
             g1, a1, _ = n.grad_for_write(s1) if s1 is not None else (None, 0, None)
             dgrad(n.dt, g, dy, wmat, g0, a0, g1, a1)
+
+
+    def _note_route(self, which, route_fn):
+        """Record, each time the plan runs, the route the split launch just issued took (UNet.grad_products_table).  A split data
+        gradient reads only the split shadow: a route that is not a split one would compute garbage, so it is an error."""
+        routes = self.net.grad_routes.setdefault(self.name, {})
+        routes[which] = "pending"
+
+        def fn():
+            r = route_fn()
+            if "split" not in r:
+                raise RuntimeError(f"{self.name}: the split-product {which} took route {r!r}")
+            routes[which] = r
+        _lib.note(fn)
 
 
 class _Norm:
@@ -514,7 +575,15 @@ class UNet:
     `backward_plan` are `_lib.Recording`s that Trainer/Sampler splice into their own graphs."""
 
     def __init__(self, cfg, N, H, W, dtype=BF16, device=None, params=None, seed=1234, store=None, use_graph=True,
-                 group_wgrads=True, wgrad_group_bytes=None, pair_convs=True, f32_products="exact", uniform_t=False, _dry=False):
+                 group_wgrads=True, wgrad_group_bytes=None, pair_convs=True, f32_products="exact", uniform_t=False, grad_products="exact",
+                 _dry=False):
+        # grad_products="split": fp32 TRAINING with the backward's convolution products as hi / lo pairs too (data gradients through
+        # the flipped, transposed split shadow PsT on the split forward routes, weight gradients on mdm_conv_wgrad_split); fp32
+        # storage, accumulation and optimizer state.  Only with dtype=F32, f32_products="split"; "exact" (default) is today's path.
+        if grad_products not in ("exact", "split") or (grad_products == "split" and not (dtype == F32 and f32_products == "split")):
+            raise ValueError(f"grad_products={grad_products!r} needs dtype=F32 and f32_products='split' (got dtype={dtype}, "
+                             f"f32_products={f32_products!r}); the default is 'exact'")
+        self.grad_products = grad_products
         # uniform_t: the whole batch shares ONE timestep (the reverse sampler: sampler.py:137-145 passes a constant vector) -- the
         # time-embedding MLP and its 22 projections then run on one row and every image reads projection row 0.  Forward-only.
         self.uniform_t = bool(uniform_t)
@@ -544,6 +613,7 @@ class UNet:
         # instead of 2^-24; mdm_gemm_desc.B_split).  "exact" (default) is the parity path; "split" is for the reverse sampler.
         assert f32_products in ("exact", "split") and (f32_products == "exact" or dtype == F32), f32_products
         self.split_products = f32_products == "split"
+        self.grad_routes = {}               # conv name -> {"dgrad": route, "wgrad": route} (grad_products_table)
         if wgrad_group_bytes is None:
             # A group is one launch AND one gradient bucket (mdm/dist.py).  Under data parallelism ~32 MB groups let the exchange of one
             # bucket run under the backward of the next; a single process has nothing to exchange, and there one group over the whole
@@ -563,6 +633,8 @@ class UNet:
             assert store.dtype == dtype, "a shared parameter store must have the same compute dtype"
         if self.split_products:
             self.store.enable_split()
+        if self.grad_products == "split":
+            self.store.enable_split_t()
         self._set_param_marks()
         self._materialize()
         if not shared:
@@ -595,7 +667,8 @@ class UNet:
         plans = self.__dict__.setdefault("_batch_plans", {})
         if N not in plans:
             plans[N] = type(self)(self.cfg, N, self.H, self.W, dtype=self.dt, device=self.device, store=self.store, use_graph=self.use_graph,
-                                  f32_products="split" if self.split_products else "exact", uniform_t=self.uniform_t)
+                                  f32_products="split" if self.split_products else "exact", uniform_t=self.uniform_t,
+                                  grad_products=self.grad_products)
         return plans[N]
 
     def with_uniform_t(self):
@@ -606,7 +679,8 @@ class UNet:
             return self
         if getattr(self, "_uniform_twin", None) is None:
             self._uniform_twin = type(self)(self.cfg, self.N, self.H, self.W, dtype=self.dt, device=self.device, store=self.store,
-                                            use_graph=self.use_graph, f32_products="split" if self.split_products else "exact", uniform_t=True)
+                                            use_graph=self.use_graph, f32_products="split" if self.split_products else "exact", uniform_t=True,
+                                            grad_products=self.grad_products)
         self._uniform_twin.training = self.training
         return self._uniform_twin
 
@@ -921,6 +995,13 @@ class UNet:
         self.bwd_marks.append((len(_lib._recording.calls), 0))
         for a in self.acts:
             assert a.pending_add is None, a.name
+
+    def grad_products_table(self):
+        """{conv name: {"dgrad": route, "wgrad": route}} of a grad_products="split" model: the mdm_gemm route its split data gradient
+        took and the mdm_conv_wgrad_split route of its weight gradient, as of the last run of the backward plan ("pending" before the
+        first), or "exact:<reason>" (ops.split_grad_reason: "channels", "stride2", "geometry") where that gradient stays exact fp32.
+        A convolution whose input needs no gradient (the first of the net) has no "dgrad" entry.  {} for grad_products="exact"."""
+        return {k: dict(v) for k, v in self.grad_routes.items()}
 
     def census(self):
         """Leaf-op output elements of ONE forward under the counting rule of SURVEY 8(d) (every
