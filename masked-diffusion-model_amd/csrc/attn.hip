@@ -729,9 +729,6 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t* __restrict_
     else attn_bwd_dkv_body<D>(lds, qkv, o, d_o, lse, dqkv, L, scale);
 }
 
-#ifndef MDM_ATTN_DMA
-#define MDM_ATTN_DMA 1
-#endif
 template <int D>
 static int attn_launch(int which, const bf16_t* qkv, bf16_t* o, const bf16_t* d_o, float* lse, float* delta, bf16_t* dqkv,
                        int N, int L, float scale, hipStream_t s) {
@@ -745,7 +742,7 @@ static int attn_launch(int which, const bf16_t* qkv, bf16_t* o, const bf16_t* d_
     dim3 grid((unsigned)cdiv(L, 64), (unsigned)N);
     if (which == 0) {
         if constexpr (D >= 64) {
-            if (MDM_ATTN_DMA && L % 64 == 0 && L >= 256) {         // several key tiles: K / V prefetched by LDS-DMA
+            if (L % 64 == 0 && L >= 256) {         // several key tiles: K / V prefetched by LDS-DMA
                 constexpr int dma_bytes = (D <= 128 ? 3 : 2) * 2 * 64 * 2 * D;
                 static bool dma_configured = false;
                 if (!dma_configured) {
@@ -760,7 +757,7 @@ static int attn_launch(int which, const bf16_t* qkv, bf16_t* o, const bf16_t* d_
     } else {
         MDM_REQUIRE(L <= 4096, "attention backward: L=%d > 4096", L);
         if constexpr (D >= 64) {
-            if (MDM_ATTN_DMA && L % 64 == 0 && L >= 256) {
+            if (L % 64 == 0 && L >= 256) {
                 constexpr int dma_bytes = (D <= 128 ? 3 : 2) * 2 * 64 * 2 * D;
                 static bool dma_configured = false;
                 if (!dma_configured) {

@@ -26,10 +26,6 @@ typedef __attribute__((ext_vector_type(4))) short bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf4_t;
 
-#ifndef MDM_USE_TR_READ
-#define MDM_USE_TR_READ 1
-#endif
-
 // ----------------------------------------------------------------------------
 // index helpers shared by both paths
 // ----------------------------------------------------------------------------
@@ -669,7 +665,6 @@ __device__ __forceinline__ bf16x8 frag_rows(const bf16_t* tile, int row0, int ks
 template <int LDC>
 __device__ __forceinline__ bf16x8 frag_cols(const bf16_t* tile, int col0, int ks, int lane) {
     bf16x8 f;
-#if MDM_USE_TR_READ
     const int i = lane & 15;
     const int kb = ks * 32 + 8 * (lane >> 4);
     const bf16_t* p0 = tile + (kb + (i >> 2)) * LDC + col0 + 4 * (i & 3);
@@ -679,11 +674,6 @@ __device__ __forceinline__ bf16x8 frag_cols(const bf16_t* tile, int col0, int ks
     bf16x4 l4 = *reinterpret_cast<bf16x4*>(&lo), h4 = *reinterpret_cast<bf16x4*>(&hi);
     f[0] = l4[0]; f[1] = l4[1]; f[2] = l4[2]; f[3] = l4[3];
     f[4] = h4[0]; f[5] = h4[1]; f[6] = h4[2]; f[7] = h4[3];
-#else
-    const bf16_t* p = tile + (ks * 32 + 8 * (lane >> 4)) * LDC + col0 + (lane & 15);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (short)p[j * LDC];
-#endif
     return f;
 }
 
@@ -949,9 +939,6 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_
 // select without a branch: p if ok else the zero page
 __device__ __forceinline__ const void* or_zero(bool ok, const void* p, const void* zero) { return ok ? p : zero; }
 
-#ifndef MDM_RING_PARITY
-#define MDM_RING_PARITY 1          // 0: stride-2 data gradients as plain nine-tap gathers (A/B builds)
-#endif
 template <int BM, int BN, int LAYOUT, int NSTAGE, bool CONV, int NW = 4>
 __global__ __launch_bounds__(64 * NW) void gemm_ring_kernel(mdm_gemm_desc d) {
     constexpr int BK = 64;
@@ -981,7 +968,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_ring_kernel(mdm_gemm_desc d) {
     // `par`: the rows of the problem are taken in a PERMUTED order, class by class inside every image (class = the top two bits of the
     // in-image index), so that a tile is one class, walks only that class's taps, and the epilogue stores row m at the pixel it stands for.
     const int per_ = d.OH * d.OW;
-    const bool par = MDM_RING_PARITY && TAPMAJOR && d.transposed && d.stride == 2 && d.KH == 3 && d.KW == 3 && d.splitk <= 1 &&
+    const bool par = TAPMAJOR && d.transposed && d.stride == 2 && d.KH == 3 && d.KW == 3 && d.splitk <= 1 &&
                      (per_ & (per_ - 1)) == 0 && (d.OW & (d.OW - 1)) == 0 && d.OW >= 2 && (per_ >> 2) % BM == 0 && d.M % BM == 0;
     const int par_sp = par ? 31 - __clz(per_) : 2, par_c = par_sp - 2, par_h = par ? 30 - __clz(d.OW) : 0;   // log2: pixels, class size, OW / 2
     auto par_pix = [&](int row, RowPix& rp) {                       // permuted row -> (image, oy, ox)
@@ -1251,34 +1238,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_ring_kernel(mdm_gemm_desc d) {
 // of one pixel: residual, accumulate and the store are 16-byte accesses, 256 B contiguous per 16 lanes.
 // Rounding happens once, after every fp32 term is in -- same arithmetic as epilogue4.
 // ----------------------------------------------------------------------------
-// Tile stores of a convolution that runs as a phase of a CHAIN (chain_kernel instantiates the bodies with WT): WRITE-THROUGH (sc1), so
-// that the consumer workgroup of the next phase finds the bytes in memory once this workgroup's waves have drained their stores --
-// no agent-scope release (an L2 write-back: 6-8 us per hand-off with plain stores, MI355X_MICROARCH.md "publish-large").  hipcc does
-// not count an asm store (the chain drains with an explicit vmcnt(0)); `s_nop 1` keeps the data registers until the store has read them.
-typedef unsigned st4u_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store16_wt(void* p, const st4u_t& r) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(r) : "memory");
-}
-template <bool WT>
-__device__ __forceinline__ void store8_pub(bf16_t* p, const float8& v) {
-    if constexpr (WT) {
-        st4u_t r;
-        r[0] = (uint32_t)f2bf(v.lo.x) | ((uint32_t)f2bf(v.lo.y) << 16);
-        r[1] = (uint32_t)f2bf(v.lo.z) | ((uint32_t)f2bf(v.lo.w) << 16);
-        r[2] = (uint32_t)f2bf(v.hi.x) | ((uint32_t)f2bf(v.hi.y) << 16);
-        r[3] = (uint32_t)f2bf(v.hi.z) | ((uint32_t)f2bf(v.hi.w) << 16);
-        store16_wt(p, r);
-    } else store8(p, v);
-}
-template <bool WT>
-__device__ __forceinline__ void store8_pub(float* p, const float8& v) {
-    if constexpr (WT) {
-        store16_wt(p, __builtin_bit_cast(st4u_t, v.lo));
-        store16_wt(p + 4, __builtin_bit_cast(st4u_t, v.hi));
-    } else store8(p, v);
-}
-
-template <int BM, int BN, int NW, int MI, int NI, typename T = bf16_t, bool WT = false>
+template <int BM, int BN, int NW, int MI, int NI, typename T = bf16_t>
 __device__ __forceinline__ void epilogue_tile(const mdm_gemm_desc& d, char* lds, int m0, int n0, int row_w, int col_w,
                                               int lane, int t, f32x4 (&acc)[MI][NI]) {
     constexpr int PITCH = BN * 4;
@@ -1320,7 +1280,7 @@ __device__ __forceinline__ void epilogue_tile(const mdm_gemm_desc& d, char* lds,
             v.lo.x += o.lo.x; v.lo.y += o.lo.y; v.lo.z += o.lo.z; v.lo.w += o.lo.w;
             v.hi.x += o.hi.x; v.hi.y += o.hi.y; v.hi.z += o.hi.z; v.hi.w += o.hi.w;
         }
-        store8_pub<WT>(p, v);
+        store8(p, v);
     }
 }
 
@@ -1361,7 +1321,7 @@ __device__ __forceinline__ void epilogue_tile_slab(const mdm_gemm_desc& d, float
 // chunks = 512 or 256 active threads.  Same arithmetic as gn_bwd_reg_kernel (norm.hip); d(z) enters in fp32 instead of bf16.
 // LDS: [0, 16K) the fp32 tile, [16K, 80K) column-sum scratch [32 quantities][512], then small arrays.
 // ----------------------------------------------------------------------------
-template <int MI, int NI, int BN, bool WT = false>
+template <int MI, int NI, int BN>
 __device__ __forceinline__ void epilogue_tile_gnb(const mdm_gemm_desc& d, char* lds, int m0, int n0, int row_w, int col_w,
                                                   int lane, int t, f32x4 (&acc)[MI][NI]) {
     constexpr int PITCH = BN * 4, NCH = BN / 8, NCH_SH = NCH == 8 ? 3 : 2, ACTIVE = 64 * NCH;
@@ -1469,7 +1429,7 @@ __device__ __forceinline__ void epilogue_tile_gnb(const mdm_gemm_desc& d, char* 
             v.lo.x += old.lo.x; v.lo.y += old.lo.y; v.lo.z += old.lo.z; v.lo.w += old.lo.w;
             v.hi.x += old.hi.x; v.hi.y += old.hi.y; v.hi.z += old.hi.z; v.hi.w += old.hi.w;
         }
-        store8_pub<WT>(p, v);
+        store8(p, v);
     }
     if (d.gnb_sum_img || d.gnb_sum_all) {
         __syncthreads();
@@ -1499,7 +1459,7 @@ __device__ __forceinline__ void epilogue_tile_gnb(const mdm_gemm_desc& d, char* 
 // statistics over the ROUNDED values exactly as a separate GroupNorm launch would see them -- two passes (mean, then
 // centred squares: exact for constant maps like the pivot-shifted sums of norm.hip) -- and z = silu?(y_hat*gamma+beta).
 // ----------------------------------------------------------------------------
-template <int MI, int NI, int BN, bool WT = false>
+template <int MI, int NI, int BN>
 __device__ __forceinline__ void epilogue_tile_gnf(const mdm_gemm_desc& d, char* lds, int m0, int n0, int row_w, int col_w,
                                                   int lane, int t, f32x4 (&acc)[MI][NI]) {
     constexpr int PITCH = BN * 4, NCH = BN / 8, NCH_SH = NCH == 8 ? 3 : 2, ACTIVE = 64 * NCH;
@@ -1541,7 +1501,7 @@ __device__ __forceinline__ void epilogue_tile_gnf(const mdm_gemm_desc& d, char* 
             v.hi.x += b.hi.x; v.hi.y += b.hi.y; v.hi.z += b.hi.z; v.hi.w += b.hi.w;
         }
         bf16_t* yp = reinterpret_cast<bf16_t*>(d.D0) + (int64_t)m * d.ldd0 + n;
-        store8_pub<WT>(yp, v);
+        store8(yp, v);
         // the values as GroupNorm reads them back: rounded to bf16
         const float vv[8] = {v.lo.x, v.lo.y, v.lo.z, v.lo.w, v.hi.x, v.hi.y, v.hi.z, v.hi.w};
 #pragma unroll
@@ -1605,7 +1565,7 @@ __device__ __forceinline__ void epilogue_tile_gnf(const mdm_gemm_desc& d, char* 
             if (d.gnf_silu) o[e] = silu_f(o[e]);
         }
         const float8 zo = {make_float4(o[0], o[1], o[2], o[3]), make_float4(o[4], o[5], o[6], o[7])};
-        store8_pub<WT>(reinterpret_cast<bf16_t*>(d.gnf_out) + (int64_t)m * C + n, zo);
+        store8(reinterpret_cast<bf16_t*>(d.gnf_out) + (int64_t)m * C + n, zo);
     }
     const int ngt = BN >> cpg_sh;                                          // groups inside this BN-channel tile
     if (t < nimg * ngt) {
@@ -1622,7 +1582,7 @@ __device__ __forceinline__ void epilogue_tile_gnf(const mdm_gemm_desc& d, char* 
 // (x, the residual, the destination and the normalised output are each one load / store per lane), and every GroupNorm sum is a sum
 // over the lanes of an image: wave shuffles, no LDS passes, no workgroup barriers.  The LDS epilogues this replaces on these tiles
 // (epilogue_tile_gnf / _gnb: ~12 barriers, two dependent rounds of column sums with 16-way bank conflicts) took 11 000 cycles behind a
-// loop of 11 000 (in-kernel stamps, profiles/r04_small_conv_stamps.txt).  Same arithmetic: statistics in two passes over the
+// loop of 11 000 (in-kernel stamps, profiles/r04_small_conv_stamps_before_epilogue.txt).  Same arithmetic: statistics in two passes over the
 // bf16-rounded values (forward), the gn_bwd_reg_kernel formulas (backward); sums in a fixed (butterfly) order.
 // Requires C / G == 8 where a GroupNorm is fused, N0 % 8 == 0.  P16: 4x4 maps (an image = 16 lanes), else 8x8 (64 lanes).
 // (Measured and NOT kept, three ways of fetching the epilogue's vectors -- x / residual, the accumulate tensors -- early: plain loads at
@@ -1671,7 +1631,7 @@ __device__ __forceinline__ void rows_gather_small(const f32x4* red, const int g,
 }
 // `act`: this lane's pixel exists (tiles of fewer than 64 pixels leave lanes over: they load valid addresses, contribute zeros to
 // every sum and store nothing)
-template <bool WT, bool P16>
+template <bool P16>
 __device__ __forceinline__ void epilogue_rows(const mdm_gemm_desc& d, float (&v)[8], const int m0, const int n0, const int g, const int r_lane,
                                               const bool act = true) {
     constexpr int P = P16 ? 16 : 64, p_sh = P16 ? 4 : 6;
@@ -1744,7 +1704,7 @@ __device__ __forceinline__ void epilogue_rows(const mdm_gemm_desc& d, float (&v)
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] += old[e];
         }
-        if (act) store8_pub<WT>(p, pack8(o));
+        if (act) store8(p, pack8(o));
         return;
     }
     // ---- forward-type epilogue: scale, bias, time-embedding row, residual, accumulate; optionally the GroupNorm of the result
@@ -1777,7 +1737,7 @@ __device__ __forceinline__ void epilogue_rows(const mdm_gemm_desc& d, float (&v)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] += old[e];
     }
-    if (act) store8_pub<WT>(p, pack8(v));
+    if (act) store8(p, pack8(v));
     if (d.gnf_out) {
         const int G = d.gnf_G;
         float y[8], ga[8], be[8], o[8];
@@ -1796,7 +1756,7 @@ __device__ __forceinline__ void epilogue_rows(const mdm_gemm_desc& d, float (&v)
             o[e] = fmaf((y[e] - mean) * rstd, ga[e], be[e]);
             if (d.gnf_silu) o[e] = silu_f(o[e]);
         }
-        if (act) store8_pub<WT>(reinterpret_cast<bf16_t*>(d.gnf_out) + m * C + n, pack8(o));
+        if (act) store8(reinterpret_cast<bf16_t*>(d.gnf_out) + m * C + n, pack8(o));
         if (first) {
             float* sp = d.gnf_stats + ((int64_t)img * G + (n >> 3)) * 2;
             sp[0] = mean; sp[1] = rstd;
@@ -1828,7 +1788,7 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 
 // (device body: the kernel proper below, and one role of conv_pair_kernel.  bx / gx / bz stand for blockIdx.x / gridDim.x /
 // blockIdx.z of a launch of its own)
-template <int BM, int BN, int NSTAGE, int WR, int WC, int WK, bool PIPE = false, bool STAG = false, bool WT = false>
+template <int BM, int BN, int NSTAGE, int WR, int WC, int WK, bool PIPE = false, bool STAG = false>
 __device__ __forceinline__ void conv_lin2_body(const mdm_gemm_desc& d, char* ring, const int bx, const int gx, const int bz) {
     constexpr int BK = 64, NW = WR * WC * WK;
     constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE_BYTES = A_BYTES + B_BYTES;
@@ -2096,11 +2056,11 @@ __device__ __forceinline__ void conv_lin2_body(const mdm_gemm_desc& d, char* rin
             // 64-pixel halo tiles -- the same fused GroupNorm epilogues apply (lin2_gn_tile)
             // (the register form of these epilogues -- epilogue_rows with all eight waves, one GroupNorm group each -- was built for
             //  these tiles too and measured level: 3.558 vs 3.562 ms/step; not kept)
-            if (d.gnb_x) epilogue_tile_gnb<MI, NI, 64, WT>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
-            else if (d.gnf_out) epilogue_tile_gnf<MI, NI, 64, WT>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
-            else epilogue_tile<BM, BN, NW, MI, NI, bf16_t, WT>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
+            if (d.gnb_x) epilogue_tile_gnb<MI, NI, 64>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
+            else if (d.gnf_out) epilogue_tile_gnf<MI, NI, 64>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
+            else epilogue_tile<BM, BN, NW, MI, NI, bf16_t>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
         } else
-        epilogue_tile<BM, BN, NW, MI, NI, bf16_t, WT>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
+        epilogue_tile<BM, BN, NW, MI, NI, bf16_t>(d, ring, m0, n0, wr * WM, wc * WN, lane, t, acc);
     } else {
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
@@ -2797,7 +2757,7 @@ __device__ __forceinline__ void split_bf16_pair(f32x4& a, f32x4& b) {
 // channel slab is split ONCE, IN PLACE in LDS by all 512 threads during the last filter row of the slab in front of it (chunk g of a
 // 128-byte row becomes the 8 hi halves, chunk g ^ 4 the 8 lo halves of the same 8 channels: the fragment addresses do not change),
 // and the filter tiles arrive already split from the B_split shadow (mdm_split_shadow: same bytes, same arrangement).
-template <int BM, int NPW, int BN = 64, int NSB = 4, int TG = 1, typename T = bf16_t, bool SPLIT = false, bool WT = false>
+template <int BM, int NPW, int BN = 64, int NSB = 4, int TG = 1, typename T = bf16_t, bool SPLIT = false>
 __device__ __forceinline__ void conv_halo_body(const mdm_gemm_desc& d, char* lds, const int bx, const int gx, const int m_base = 0) {
     static_assert(!SPLIT || sizeof(T) == 4, "conv_halo: SPLIT is the fp32-storage variant");
     constexpr int NW = 8, WR = 4, WC = 2, WM = BM / WR, WN = BN / WC, MI = WM / 16, NI = WN / 16;
@@ -3033,11 +2993,11 @@ __device__ __forceinline__ void conv_halo_body(const mdm_gemm_desc& d, char* lds
     MDM_T(const unsigned long long t_loop_end = stamp_now();)
     __syncthreads();
     if constexpr (!F32 && BM == 64 && (BN == 64 || BN == 32)) {
-        if (d.gnb_x) epilogue_tile_gnb<MI, NI, BN, WT>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);      // uniform
-        else if (d.gnf_out) epilogue_tile_gnf<MI, NI, BN, WT>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);
-        else epilogue_tile<BM, BN, NW, MI, NI, bf16_t, WT>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);
+        if (d.gnb_x) epilogue_tile_gnb<MI, NI, BN>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);      // uniform
+        else if (d.gnf_out) epilogue_tile_gnf<MI, NI, BN>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);
+        else epilogue_tile<BM, BN, NW, MI, NI, bf16_t>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);
     } else {
-        epilogue_tile<BM, BN, NW, MI, NI, T, WT>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);
+        epilogue_tile<BM, BN, NW, MI, NI, T>(d, lds, m0, n0, wr * WM, wc * WN, lane, t, acc);
     }
 #ifdef MDM_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -3065,7 +3025,7 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(mdm_gemm_desc d) {
 // through the transposed shadow) with the REDUCTION split over the waves.  On conv_halo_body's 64 x 32 tiles of these maps every wave
 // owns ONE 16 x 16 accumulator: per filter tap it reads four fragments for two MFMAs that wait for each other, and the in-kernel
 // stamps put the loop at 430 cycles per tap (15 500 cycles for a 256 -> 256 layer: 14 B/clk of operands against the CU's ~27 B/clk
-// intake, 7 % of the matrix pipe; profiles/r04_chain_stamps.txt).  Here the tile is the same (64 pixels = whole images x 32 output
+// intake, 7 % of the matrix pipe; profiles/r04_chain_variants.txt).  Here the tile is the same (64 pixels = whole images x 32 output
 // channels, so the fused GroupNorm epilogues apply unchanged) but a channel "superslab" is 128 channels = four 32-deep k-steps:
 //   wave = (ks, ph): k-step ks of the superslab, pixel half ph -> 2 x 2 accumulator tiles per wave, four INDEPENDENT MFMAs per tap
 //   from four fragments, 12 MFMAs per barrier (3 taps); the 8 waves' partial sums meet in LDS once, behind the loop, in a fixed order.
@@ -3075,12 +3035,9 @@ __global__ __launch_bounds__(512) void conv_halo_kernel(mdm_gemm_desc d) {
 //   group (missing pieces go to a dummy page), so the waits are compile-time vmcnt counts.
 // Requires what halo_tile() == 64 requires, and C0 % 128 == C1 % 128 == 0, N % 32 == 0.
 // ----------------------------------------------------------------------------
-#ifndef MDM_SMALL_EPI
-#define MDM_SMALL_EPI 1             // 0: conv_small keeps the LDS epilogues of the halo tiles (A/B builds)
-#endif
 // BM x BN: 64 x 32, or 32 x 16 on the 4x4 maps (two whole images x two GroupNorm groups: 256 workgroups instead of 64, each streaming a
 // quarter of the bytes -- the loop is bound by what ONE CU takes in)
-template <int NPW, bool WT = false, int BM = 64, int BN = 32>
+template <int NPW, int BM = 64, int BN = 32>
 __device__ __forceinline__ void conv_small_body(const mdm_gemm_desc& d, char* lds, const int bx, const int gx) {
     constexpr int CS = 128, NSB = 3, MI = BM / 32, NI = BN / 16, BPT = BN / 4;     // BPT: 1-KiB pieces of one tap's filter tile
     static_assert((BM == 64 && BN == 32) || (BM == 32 && BN == 16), "conv_small: 64 x 32 or 32 x 16 tiles");
@@ -3220,14 +3177,14 @@ __device__ __forceinline__ void conv_small_body(const mdm_gemm_desc& d, char* ld
         MDM_T(t_e1 = stamp_now();)
         // C / G == 8 (or no fused GroupNorm): the register epilogue, four waves; anything else: the LDS epilogues of the halo tiles
         const int cpg = d.gnb_x ? d.N / d.gnb_G : (d.gnf_out ? d.N / d.gnf_G : 8);
-        if ((BM != 64 || MDM_SMALL_EPI) && cpg == 8 && (d.N0 & 7) == 0) {                                           // uniform
+        if (cpg == 8 && (d.N0 & 7) == 0) {                                                                          // uniform
             if (wave < BN / 8) {                                   // one wave per group of eight channels; lane = pixel of the tile
                 float v8[8];
                 const bool act = lane < BM;
                 rows_gather_small<MI, NI>(red, wave, act ? lane : 0, v8);
                 MDM_T(asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); t_e2 = stamp_now();)
-                if (p_sh == 4) epilogue_rows<WT, true>(d, v8, m0, n0, wave, lane, act);
-                else epilogue_rows<WT, false>(d, v8, m0, n0, wave, lane, act);
+                if (p_sh == 4) epilogue_rows<true>(d, v8, m0, n0, wave, lane, act);
+                else epilogue_rows<false>(d, v8, m0, n0, wave, lane, act);
                 MDM_T(t_e3 = stamp_now();)
             }
         } else if constexpr (BM == 64 && BN == 32) {
@@ -3241,9 +3198,9 @@ __device__ __forceinline__ void conv_small_body(const mdm_gemm_desc& d, char* ld
         }
         f32x4 one[1][1];
         one[0][0] = v;
-        if (d.gnb_x) epilogue_tile_gnb<1, 1, BN, WT>(d, lds, m0, n0, wr * 16, wc * 16, lane, t, one);          // uniform
-        else if (d.gnf_out) epilogue_tile_gnf<1, 1, BN, WT>(d, lds, m0, n0, wr * 16, wc * 16, lane, t, one);
-        else epilogue_tile<64, BN, 8, 1, 1, bf16_t, WT>(d, lds, m0, n0, wr * 16, wc * 16, lane, t, one);
+        if (d.gnb_x) epilogue_tile_gnb<1, 1, BN>(d, lds, m0, n0, wr * 16, wc * 16, lane, t, one);          // uniform
+        else if (d.gnf_out) epilogue_tile_gnf<1, 1, BN>(d, lds, m0, n0, wr * 16, wc * 16, lane, t, one);
+        else epilogue_tile<64, BN, 8, 1, 1, bf16_t>(d, lds, m0, n0, wr * 16, wc * 16, lane, t, one);
         }
     }
 #ifdef MDM_STAMP
@@ -3263,13 +3220,13 @@ __device__ __forceinline__ void conv_small_body(const mdm_gemm_desc& d, char* ld
 template <int NPW, int BM = 64, int BN = 32>
 __global__ __launch_bounds__(512) void conv_small_kernel(mdm_gemm_desc d) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
-    conv_small_body<NPW, false, BM, BN>(d, lds, (int)blockIdx.x, (int)gridDim.x);
+    conv_small_body<NPW, BM, BN>(d, lds, (int)blockIdx.x, (int)gridDim.x);
 }
 // conv_small + a 1x1 projection in one launch (the pairs of mdm_gemm_pair on the 4x4 / 8x8 maps)
 template <int NPW, int BM = 64, int BN = 32>
 __global__ __launch_bounds__(512) void conv_pair_small_kernel(mdm_gemm_desc a, mdm_gemm_desc b, int na) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
-    if ((int)blockIdx.x < na) conv_small_body<NPW, false, BM, BN>(a, lds, (int)blockIdx.x, na);
+    if ((int)blockIdx.x < na) conv_small_body<NPW, BM, BN>(a, lds, (int)blockIdx.x, na);
     else conv_lin2_body<64, 64, 4, 4, 2, 1, true, false>(b, lds, (int)blockIdx.x - na, (int)gridDim.x - na, 0);
 }
 
@@ -3487,122 +3444,6 @@ __global__ __launch_bounds__(512) void conv_pair_kernel(mdm_gemm_desc a, mdm_gem
     else conv_lin2_body<LBM, LBN, LNS, LWR, LWC, 1, true, false>(b, lds, (int)blockIdx.x - na, (int)gridDim.x - na, 0);
 }
 
-
-// ----------------------------------------------------------------------------
-// CHAIN: consecutive convolutions of the U-Net's small-map trunk (4x4 / 8x8: unet6.py:336-362, 296-333, 478-506) as ONE persistent
-// launch (mdm_chain_*).  At 32 images per GPU each of those layers is a 9-16 us launch for 1-4 us of loop (DESIGN findings 23, 26): the
-// fixed parts of a launch -- boundary, prologue, drain -- are what the trunk's time is made of.  Here a grid of resident workgroups (one
-// per CU) walks the layers ("phases") in order; a phase is one mdm_gemm or one mdm_gemm_pair, its virtual blocks are dealt out with
-// stride gridDim.x and run the SAME device bodies (conv_halo_body / conv_lin2_body) as the per-layer launches -- the results are
-// bit-identical to them.
-//   Dependencies.  Every tile of these phases is 64 output pixels = whole images (one 8x8 image or four 4x4 images) and a
-//   convolution reads only the pixels of its own images, so a block of phase p needs exactly the blocks of phase p-1 that cover ITS
-//   images -- not a grid-wide barrier.  cnt[p][image] counts the finished blocks of phase p that cover that image; a block of phase p
-//   waits until cnt[p-1][img] == target[p-1] for each of its images.  Because the wait is on ALL blocks of p-1 for those images and
-//   each of them had waited for all of p-2's, everything any earlier phase wrote for these images is complete too (residuals, skip
-//   tensors, GroupNorm statistics), and a later phase cannot overwrite what an earlier one still reads.
-//   Visibility (cdna_hip_programming.md Guideline 16): producer = every wave drains its stores (vmcnt(0)), workgroup barrier, one
-//   lane releases at agent scope, then the counter adds; consumer = one wave polls (relaxed, agent scope), ONE agent-scope acquire,
-//   vmcnt(0), workgroup barrier, then plain / LDS-DMA loads.  Nothing depends on which XCD a workgroup lands on.
-//   Progress.  Every workgroup walks (phase, block) in the same global order and waits only on earlier phases; with all gridDim.x
-//   workgroups resident (grid <= CUs: one workgroup per CU by its LDS request) the earliest unfinished block is never blocked.  The
-//   spin is bounded all the same: on a timeout the error word is set and the launch ends (with wrong results) instead of hanging.
-// ----------------------------------------------------------------------------
-#ifndef MDM_CHAIN_RELEASE_FENCE
-#define MDM_CHAIN_RELEASE_FENCE 1           // 1: an agent-scope release (L2 write-back) per block before its arrivals
-#endif
-#ifndef MDM_CHAIN_WT
-#define MDM_CHAIN_WT 0                      // 1: the tile stores of a chain's phases write through (sc1); without the release an
-                                            //    intermittent mismatch was observed (profiles/r04_chain_findings.md): not the default
-#endif
-struct ChainPhase {
-    int kind[2];            // role 0 / role 1 (mdm_gemm_pair): 0 / 1 = halo 64x32 (2 / 3 pieces per wave), 2 = lin2 64x64, 3 / 4 = conv_small 64x32,
-                            // 5 = conv_small 32x16, -1 = none
-    int desc[2];
-    int nblk[2];
-    int tiles_n[2];         // channel tiles per 64-pixel row tile
-    int img_sh_role[2];     // log2(images per row tile) of each role: 0 on 8x8 maps, 2 (64-pixel tiles) or 1 (32-pixel tiles) on 4x4
-    unsigned target;        // finished blocks per image that complete this phase
-    unsigned prev_target;   // ... the phase in front of it (0: nothing to wait for)
-};
-#ifdef MDM_STAMP
-#define MDM_CHAIN_STAMP_BASE 16384          // records [16384, 32768) of g_stamp_buf: one per (phase, virtual block)
-#endif
-
-__global__ __launch_bounds__(512) void chain_zero_kernel(unsigned* cnt, int n) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) cnt[i] = 0u;
-}
-
-__global__ __launch_bounds__(512) void chain_kernel(const mdm_gemm_desc* __restrict__ descs, const ChainPhase* __restrict__ phases,
-                                                    const int n_ph, unsigned* cnt, const int n_img, unsigned* err) {
-    extern __shared__ __attribute__((aligned(1024))) char lds[];
-    const int t = threadIdx.x;
-    for (int p = 0; p < n_ph; ++p) {
-        const ChainPhase P = phases[p];
-        const int total = P.nblk[0] + P.nblk[1];
-        unsigned* const mine = cnt + (int64_t)p * n_img;
-        const unsigned* const prev = cnt + (int64_t)(p - 1) * n_img;
-        for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
-            const int role = vb >= P.nblk[0] ? 1 : 0;
-            const int bx = role ? vb - P.nblk[0] : vb, gx = P.nblk[role];
-            const int rt = udiv_small(xcd_remap(bx, gx), P.tiles_n[role]);     // the row tile the body will compute (same arithmetic)
-            const int nimg = 1 << P.img_sh_role[role], img0 = rt << P.img_sh_role[role];
-            MDM_T(const unsigned long long t_w0 = stamp_now();)
-            if (P.prev_target != 0u) {
-                if (t < 64) {                                   // wave 0: lane i polls the counter of image img0 + i
-                    bool ok = true;
-                    if (t < nimg) {
-                        const unsigned* c = prev + img0 + t;
-                        unsigned spins = 0;
-                        while (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < P.prev_target) {
-                            __builtin_amdgcn_s_sleep(1);
-                            if (++spins > (1u << 20)) { ok = false; break; }
-                        }
-                    }
-                    if (!ok) __hip_atomic_fetch_or(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-                __syncthreads();
-            }
-            MDM_T(const unsigned long long t_w1 = stamp_now();)
-            {
-                const mdm_gemm_desc d = descs[P.desc[role]];
-                const int kind = P.kind[role];
-                constexpr bool WT = MDM_CHAIN_WT != 0;      // tile stores write through (store8_pub)
-                if (kind == 0) conv_halo_body<64, 2, 32, 3, 3, bf16_t, false, WT>(d, lds, bx, gx);
-                else if (kind == 1) conv_halo_body<64, 3, 32, 3, 3, bf16_t, false, WT>(d, lds, bx, gx);
-                else if (kind == 3) conv_small_body<4, WT>(d, lds, bx, gx);
-                else if (kind == 4) conv_small_body<5, WT>(d, lds, bx, gx);
-                else if (kind == 5) conv_small_body<3, WT, 32, 16>(d, lds, bx, gx);
-                else conv_lin2_body<64, 64, 4, 4, 2, 1, true, false, WT>(d, lds, bx, gx, 0);
-            }
-            MDM_T(const unsigned long long t_b1 = stamp_now();)
-            // publish: every wave's stores have been acknowledged, then one release for the workgroup, then the arrivals
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();                                    // (also: the next block may refill the LDS)
-            if (t < 64) {
-#if MDM_CHAIN_RELEASE_FENCE
-                if (t == 0) {                                   // (plain tile stores + L2 write-back: measured +9 us per hand-off)
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                }
-#endif
-                if (t < nimg) __hip_atomic_fetch_add(mine + img0 + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-#ifdef MDM_STAMP
-            if (t == 0) {
-                const unsigned rec = MDM_CHAIN_STAMP_BASE + (unsigned)p * 512u + (unsigned)vb;
-                if (vb < 512 && rec < MDM_STAMP_RECS) {
-                    unsigned long long* r = g_stamp_buf + (size_t)rec * 32;
-                    r[0] = t_w0; r[1] = t_w1; r[2] = t_b1; r[3] = stamp_now(); r[4] = stamp_hw_id(); r[5] = (unsigned long long)blockIdx.x; r[6] = 1;
-                }
-            }
-#endif
-        }
-    }
-}
-
 // ----------------------------------------------------------------------------
 // host launch
 // ----------------------------------------------------------------------------
@@ -3674,10 +3515,16 @@ static int launch_ring(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
     }
 }
 
-template <int BM, int BN, int NSTAGE, int WR, int WC>
-static int launch_lin2(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {         // the software-pipelined variant
+// dynamic LDS of a conv_lin2_body tile (launch_lin2, and the 1x1 role of launch_pair / launch_pair_small)
+template <int BM, int BN, int NSTAGE>
+static int lin2_lds_bytes(const mdm_gemm_desc& d) {
     int bytes = NSTAGE * (BM + BN) * 64 * 2;
     if (d.gnb_x && bytes < 16384 + 65536 + 4096 + 512) bytes = 16384 + 65536 + 4096 + 512;      // fused GroupNorm backward (64 x 64 tiles)
+    return bytes;
+}
+template <int BM, int BN, int NSTAGE, int WR, int WC>
+static int launch_lin2(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {         // the software-pipelined variant
+    const int bytes = lin2_lds_bytes<BM, BN, NSTAGE>(d);
     static int configured = 0;
     if (configured < bytes) {
         MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>),
@@ -3724,12 +3571,17 @@ static int halo_pieces(int bm, int OH, int OW) {           // 1-KiB pieces of on
     const int imgs = bm > OH * OW ? bm / (OH * OW) : 1, R = imgs > 1 ? OH : bm / OW;
     return (imgs * (R + 2) * (OW + 2) + 7) / 8;
 }
-template <int BM, int NPW, int NSB, int BN = 64, typename T = bf16_t, bool SPLIT = false, int TG = 3>
-static int launch_halo(const mdm_gemm_desc& d, hipStream_t s) {      // TG = 3: one filter row (3 taps) per barrier
-    const int NPA = halo_pieces(BM, d.OH, d.OW);
-    int bytes = 2 * NPA * 1024 + NSB * TG * BN * 128 + 1024;
+// dynamic LDS of a conv_halo_body tile (launch_halo, and the 3x3 role of launch_pair)
+template <int BM, int NSB, int BN, int TG>
+static int halo_lds_bytes(const mdm_gemm_desc& d) {
+    int bytes = 2 * halo_pieces(BM, d.OH, d.OW) * 1024 + NSB * TG * BN * 128 + 1024;
     if (bytes < BM * BN * 4) bytes = BM * BN * 4;                 // the tile epilogue parks the fp32 tile there
     if (BM == 64 && d.gnb_x && bytes < 16384 + 65536 + 4096 + 512) bytes = 16384 + 65536 + 4096 + 512;   // fused GroupNorm backward
+    return bytes;
+}
+template <int BM, int NPW, int NSB, int BN = 64, typename T = bf16_t, bool SPLIT = false, int TG = 3>
+static int launch_halo(const mdm_gemm_desc& d, hipStream_t s) {      // TG = 3: one filter row (3 taps) per barrier
+    const int NPA = halo_pieces(BM, d.OH, d.OW), bytes = halo_lds_bytes<BM, NSB, BN, TG>(d);
     MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_halo: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
     static int configured = 0;
     if (configured < bytes) {
@@ -3749,11 +3601,15 @@ static int small_lds_bytes(const mdm_gemm_desc& d, int bm = 64, int bn = 32) {
     const int bytes = 2 * small_pieces(d, bm) * 1024 + 3 * 3 * bn * 256 + 1024;
     return bytes < 16384 + 8 * 1024 ? 16384 + 8 * 1024 : bytes;          // (the parked partials: 8 waves x <= 1 KiB behind the first 16 KiB)
 }
+// C / G of the GroupNorm fused into a convolution's epilogue (8 without one): conv_small's 32 x 16 tiles have the register epilogue
+// only, which needs C / G == 8 and N0 % 8 == 0 (the 64 x 32 tiles fall back to the LDS epilogues)
+static int fused_gn_cpg(const mdm_gemm_desc& d) { return d.gnb_x ? d.N / d.gnb_G : (d.gnf_out ? d.N / d.gnf_G : 8); }
 template <int NPW, int BM = 64, int BN = 32>
 static int launch_small(const mdm_gemm_desc& d, hipStream_t s) {
     const int bytes = small_lds_bytes(d, BM, BN);
     MDM_REQUIRE(small_pieces(d, BM) <= 8 * NPW && bytes <= 160 * 1024 && (BM != 64 || bytes >= 16384 + 65536 + 4096 + 512),
                 "conv_small: tile does not fit (%d bytes)", bytes);
+    MDM_REQUIRE(BM == 64 || (fused_gn_cpg(d) == 8 && d.N0 % 8 == 0), "conv_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
     static int configured = 0;
     if (configured < bytes) {
         MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_kernel<NPW, BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
@@ -3814,19 +3670,14 @@ static int halo_tile_f32(const mdm_gemm_desc& d) {
 
 // conv_halo_mixed_kernel: whole rounds of 256-pixel tiles, the remainder as 128-pixel tiles -- taken when the remainder is at most one
 // round of small tiles (otherwise two short rounds cost more than the one long round they replace).  kNotTaken = plain launch.
-#ifndef MDM_SPLIT_BN128
-#define MDM_SPLIT_BN128 160         // 128-channel split tiles when the layer has at least this many of them (0: never)
-#endif
-#ifndef MDM_SPLIT_MIXED
-#define MDM_SPLIT_MIXED 1
-#endif
+constexpr int MDM_SPLIT_BN128 = 160;   // 128-channel split tiles when the layer has at least this many of them
 constexpr int kNotTaken = 1;       // "this launcher does not apply" (positive: every error code, hip_fail's -2 included, is negative)
 static int launch_halo_mixed(const mdm_gemm_desc& d, hipStream_t s) {
     const int tn = d.N / 64;
     const int64_t tiles = (int64_t)(d.M / 256) * tn;
     const int64_t big_m = (tiles / 256) * 256 / tn;                // M tiles of 256 pixels in whole rounds (all their channel tiles)
     const int64_t rest = (d.M / 256 - big_m) * 2 * tn;             // 128-pixel tiles behind them
-    if (!MDM_SPLIT_MIXED || d.OW != 32 || d.OH % 8 || big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return kNotTaken;
+    if (d.OW != 32 || d.OH % 8 || big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return kNotTaken;
     const int npa = halo_pieces(256, d.OH, d.OW), npb = halo_pieces(128, d.OH, d.OW);
     if (npa > 48 || npb > 32) return kNotTaken;
     int bytes = std::max(2 * npa * 1024 + 2 * 3 * 64 * 128 + 1024, 2 * npb * 1024 + 3 * 3 * 64 * 128 + 1024);
@@ -3854,9 +3705,7 @@ static int halo_small_n_split(const mdm_gemm_desc& d) {
         return 0;
     return 256;
 }
-#ifndef MDM_LIN_SPLIT_NS64
-#define MDM_LIN_SPLIT_NS64 4        // ring stages of lin_split_kernel's 64-channel tile (six, 144 KB, measured 22.5 against 21.7 us per launch)
-#endif
+constexpr int MDM_LIN_SPLIT_NS64 = 4;  // ring stages of lin_split_kernel's 64-channel tile (six, 144 KB, measured 22.5 against 21.7 us per launch)
 // lin_split_kernel: 0 = not eligible, else the channel tile (128, or 64 when 128 would leave the chip short of workgroups)
 static int lin_split_tile(const mdm_gemm_desc& d) {
     const bool k1 = d.KH == 1 && d.KW == 1 && d.stride == 1 && d.pad_t == 0 && d.pad_l == 0 && d.IH == d.OH && d.IW == d.OW;
@@ -3882,15 +3731,9 @@ static int launch_lin_split(const mdm_gemm_desc& d, hipStream_t s) {
     hipLaunchKernelGGL((lin_split_kernel<BN, NS>), dim3((unsigned)((int64_t)cdiv(d.M, 128) * (d.N / BN))), dim3(512), bytes, s, d);
     return 0;
 }
-#ifndef MDM_NSB256
-#define MDM_NSB256 2                // filter stages of the 256-pixel bf16 halo tiles
-#endif
-#ifndef MDM_SPLIT_MIN128
-#define MDM_SPLIT_MIN128 160
-#endif
-#ifndef MDM_SPLIT_NSB256
-#define MDM_SPLIT_NSB256 2          // filter stages of the 256-pixel split tiles
-#endif
+constexpr int MDM_NSB256 = 2;          // filter stages of the 256-pixel bf16 halo tiles
+constexpr int MDM_SPLIT_MIN128 = 160;
+constexpr int MDM_SPLIT_NSB256 = 2;    // filter stages of the 256-pixel split tiles
 // The split-products variant is not MFMA-bound: per flop a 256-pixel tile reads 2/3 of the LDS fragment bytes and streams half the
 // filter bytes of a 128-pixel one (stamps: 893 cycles per tap on 128 pixels; the 16x16 layers on 256-pixel tiles run the same flops in
 // 2/3 of the time of the 32x32 layers on 128-pixel tiles).  Estimated time = rounds of workgroups x tile cost (256: 1.46 x 128).
@@ -4044,12 +3887,6 @@ static bool lin2_gn_tile(const mdm_gemm_desc& d) {
 }
 enum ConvVar { CV_NONE = 0, CV_H256_4, CV_H256_6, CV_H128_3, CV_H128_4, CV_H128_6, CV_H64_2_32, CV_H64_3_32, CV_H64_2_64, CV_H64_3_64,
                CV_L128, CV_L64x128, CV_L64, CV_S64_4, CV_S64_5, CV_S32_3 };
-#ifndef MDM_SMALL_32X16
-#define MDM_SMALL_32X16 1           // 0: the 4x4 maps stay on conv_small's 64 x 32 tiles (A/B builds)
-#endif
-#ifndef MDM_SMALL_CONV
-#define MDM_SMALL_CONV 1            // 0: the 4x4 / 8x8 maps stay on conv_halo_body's 64 x 32 tiles (A/B builds)
-#endif
 
 static ConvVar conv_variant(const mdm_gemm_desc& d, const Resolved& r, unsigned grid_z) {
     if (!(d.dtype == MDM_BF16 && ring_eligible(d) && d.layout == 0 && d.conv &&
@@ -4065,11 +3902,10 @@ static ConvVar conv_variant(const mdm_gemm_desc& d, const Resolved& r, unsigned 
         if (d.N % 32 == 0 && (!(d.gnb_x || d.gnf_out) || d.N / (d.gnb_x ? d.gnb_G : d.gnf_G) <= 32)) {
             // 128-channel superslabs with the reduction split over the waves (conv_small_body) where the channel counts allow
             const int spw = (small_pieces(d) + 7) / 8;
-            if (MDM_SMALL_CONV && d.Ck % 128 == 0 && d.C0 % 128 == 0 && d.C1 % 128 == 0 && spw <= 5) {
+            if (d.Ck % 128 == 0 && d.C0 % 128 == 0 && d.C1 % 128 == 0 && spw <= 5) {
                 // 4x4 maps: 32 pixels (two whole images) x 16 channels (two GroupNorm groups of eight) -- four times the workgroups, each
                 // streaming a quarter of the filter bytes; its epilogue is the register one only (C / G == 8 where a GroupNorm is fused)
-                const int cpg = d.gnb_x ? d.N / d.gnb_G : (d.gnf_out ? d.N / d.gnf_G : 8);
-                if (MDM_SMALL_32X16 && d.OH * d.OW == 16 && d.M % 32 == 0 && d.N % 16 == 0 && cpg == 8 && (d.N0 & 7) == 0 &&
+                if (d.OH * d.OW == 16 && d.M % 32 == 0 && d.N % 16 == 0 && fused_gn_cpg(d) == 8 && (d.N0 & 7) == 0 &&
                     (int64_t)(d.M / 64) * (d.N / 32) < kBigMinTiles && (small_pieces(d, 32) + 7) / 8 <= 3)
                     return CV_S32_3;
                 return spw <= 4 ? CV_S64_4 : CV_S64_5;
@@ -4207,7 +4043,7 @@ static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
             // 256 pixels x 128 channels (one tap per barrier, four filter stages): the halo is staged and split once for twice the
             // channels and a wave multiplies 4 x 4 fragments per tap -- 16 fragment reads for 48 MFMAs where the 64-channel tile reads
             // 12 for 24; half as many tiles, so a 16x16 layer at sample_num = 100 is ONE round of workgroups instead of 1.56 in two
-            if (hb32 == 256 && MDM_SPLIT_BN128 && d.N % 128 == 0 && (d.OW == 16 || d.OW == 32) &&
+            if (hb32 == 256 && d.N % 128 == 0 && (d.OW == 16 || d.OW == 32) &&
                 (int64_t)(d.M / 256) * (d.N / 128) >= MDM_SPLIT_BN128) {
                 rc = npw <= 4 ? route(R_HS_256_4_128) + launch_halo<256, 4, 4, 128, float, true, 1>(d, s)
                                : route(R_HS_256_6_128) + launch_halo<256, 6, 4, 128, float, true, 1>(d, s);
@@ -4308,51 +4144,6 @@ struct WgradGroup {
 struct GroupItem { int desc, item, tiles_x, big, cost; };
 struct TapsTile { int desc, tile, slabs; };
 
-
-// ---- chains of small-map convolutions in one persistent launch (chain_kernel) ------------------------------------
-struct Chain {
-    const mdm_gemm_desc* descs_dev = nullptr;
-    const ChainPhase* phases_dev = nullptr;
-    unsigned* cnt_dev = nullptr;            // [n_ph][n_img] arrival counters + 4 words (error, spare)
-    int n_ph = 0, n_img = 0, grid = 0, lds_bytes = 0;
-};
-// 0 = halo 64x32 with 2 pieces per wave, 1 = with 3, 2 = lin2 64x64, 3 / 4 = conv_small with 4 / 5 pieces, -1 = not a chain link
-static int chain_kind(const mdm_gemm_desc* dh, Resolved& r, int* lds_bytes) {
-    if (resolve(dh, false, r)) return -1;
-    const mdm_gemm_desc& d = r.d;
-    if (check_fused_gn(d)) return -1;
-    const unsigned z = (unsigned)(r.zouter * d.splitk);
-    if (z != 1 || r.tap_split || d.splitk > 1 || !d.conv || d.layout != 0 || d.dtype != MDM_BF16) return -1;
-    const int P = d.OH * d.OW;
-    if (!(P == 16 || P == 64) || d.M % 64 != 0 || d.M % P != 0) return -1;
-    const ConvVar cv = conv_variant(d, r, z);
-    if (cv == CV_H64_2_32 || cv == CV_H64_3_32) {
-        const int NPA = halo_pieces(64, d.OH, d.OW);
-        int bytes = 2 * NPA * 1024 + 3 * 3 * 32 * 128 + 1024;                       // as launch_halo<64, NPW, 3, 32>
-        if (bytes < 64 * 32 * 4) bytes = 64 * 32 * 4;
-        if (d.gnb_x && bytes < 16384 + 65536 + 4096 + 512) bytes = 16384 + 65536 + 4096 + 512;
-        if (d.gnf_out && bytes < 16384 + 16384 + 4096) bytes = 16384 + 16384 + 4096;
-        if (NPA > 8 * (cv == CV_H64_2_32 ? 2 : 3)) return -1;
-        *lds_bytes = bytes;
-        return cv == CV_H64_2_32 ? 0 : 1;
-    }
-    if (cv == CV_S64_4 || cv == CV_S64_5) {
-        *lds_bytes = small_lds_bytes(d);
-        return cv == CV_S64_4 ? 3 : 4;
-    }
-    if (cv == CV_S32_3) {
-        *lds_bytes = small_lds_bytes(d, 32, 16);
-        return 5;
-    }
-    if (cv == CV_L64 && r.tiles < (1ll << 20)) {
-        int bytes = 4 * (64 + 64) * 64 * 2;                                        // as launch_lin2<64, 64, 4, 4, 2>
-        if (d.gnb_x && bytes < 16384 + 65536 + 4096 + 512) bytes = 16384 + 65536 + 4096 + 512;
-        *lds_bytes = bytes;
-        return 2;
-    }
-    return -1;
-}
-
 }  // namespace mdm
 using namespace mdm;
 
@@ -4376,11 +4167,7 @@ extern "C" int mdm_gemm_route_names(const char** out, int cap) {
 template <int BM, int NPW, int BN, int NSB, int LBM, int LBN, int LNS, int LWR, int LWC>
 static int launch_pair(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int nb, hipStream_t s) {
     const int NPA = halo_pieces(BM, a.OH, a.OW);
-    int bytes = 2 * NPA * 1024 + NSB * 3 * BN * 128 + 1024;                    // as launch_halo
-    if (bytes < BM * BN * 4) bytes = BM * BN * 4;
-    if (BM == 64 && a.gnb_x && bytes < 16384 + 65536 + 4096 + 512) bytes = 16384 + 65536 + 4096 + 512;
-    constexpr int lin_bytes = LNS * (LBM + LBN) * 64 * 2;                      // as launch_lin2
-    if (bytes < lin_bytes) bytes = lin_bytes;
+    const int bytes = std::max(halo_lds_bytes<BM, NSB, BN, 3>(a), lin2_lds_bytes<LBM, LBN, LNS>(b));
     MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_pair: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
     static int configured = 0;
     if (configured < bytes) {
@@ -4395,10 +4182,9 @@ static int launch_pair(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int nb, h
 
 template <int NPW, int BM = 64, int BN = 32>
 static int launch_pair_small(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int nb, hipStream_t s) {
-    int bytes = small_lds_bytes(a, BM, BN);
-    constexpr int lin_bytes = 4 * (64 + 64) * 64 * 2;
-    if (bytes < lin_bytes) bytes = lin_bytes;
+    const int bytes = std::max(small_lds_bytes(a, BM, BN), lin2_lds_bytes<64, 64, 4>(b));
     MDM_REQUIRE(small_pieces(a, BM) <= 8 * NPW && bytes <= 160 * 1024, "conv_pair_small: tile does not fit (%d bytes)", bytes);
+    MDM_REQUIRE(BM == 64 || (fused_gn_cpg(a) == 8 && a.N0 % 8 == 0), "conv_pair_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
     static int configured = 0;
     if (configured < bytes) {
         MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pair_small_kernel<NPW, BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
@@ -4443,105 +4229,6 @@ extern "C" int mdm_gemm_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b
     }
     if (rc) return rc;
     return launch_status("gemm pair launch");
-}
-
-// ---- mdm_chain_*: see chain_kernel ----------------------------------------------------------------------------------
-extern "C" int mdm_chain_accepts(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host) {
-    if (!a_host) return 0;
-    Resolved ra, rb;
-    int la = 0, lb = 0;
-    const int ka = chain_kind(a_host, ra, &la);
-    if (ka < 0) return 0;
-    if (!b_host) return 1;
-    const int kb = chain_kind(b_host, rb, &lb);
-    // a pair = a halo convolution + a 1x1 projection without a fused GroupNorm epilogue (what mdm_gemm_pair fuses), same batch and map
-    return (ka != 2 && kb == 2 && !rb.d.gnb_x && !rb.d.gnf_out && ra.d.M == rb.d.M && ra.d.OH == rb.d.OH && ra.d.OW == rb.d.OW) ? 1 : 0;
-}
-extern "C" int mdm_chain_create(const mdm_gemm_desc* descs_host, const int* roles, int n_phases, void* dev_buf, int64_t dev_bytes,
-                                int64_t* need_bytes_out, void** handle_out) {
-    MDM_REQUIRE(descs_host && roles && n_phases > 0 && need_bytes_out && handle_out, "chain_create: bad arguments");
-    *handle_out = nullptr;
-    static const int n_cu = [] {
-        int dev = 0; hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess || pr.multiProcessorCount <= 0) return 256;
-        return pr.multiProcessorCount;
-    }();
-    std::vector<mdm_gemm_desc> ds;
-    std::vector<ChainPhase> ph((size_t)n_phases);
-    int n_img = 0, lds_max = 0, max_blocks = 0, di = 0;
-    unsigned prev_target = 0;
-    for (int p = 0; p < n_phases; ++p) {
-        MDM_REQUIRE(roles[p] == 1 || roles[p] == 2, "chain_create: phase %d has %d descriptors (1 or 2)", p, roles[p]);
-        ChainPhase& P = ph[(size_t)p];
-        P.kind[1] = -1; P.desc[1] = 0; P.nblk[1] = 0; P.tiles_n[1] = 1; P.img_sh_role[0] = P.img_sh_role[1] = 0;
-        MDM_REQUIRE(mdm_chain_accepts(descs_host + di, roles[p] == 2 ? descs_host + di + 1 : nullptr) == 1,
-                    "chain_create: phase %d is not a chain link (mdm_chain_accepts)", p);
-        unsigned target = 0;
-        for (int q = 0; q < roles[p]; ++q) {
-            Resolved r;
-            int lb = 0;
-            const int k = chain_kind(descs_host + di + q, r, &lb);
-            const mdm_gemm_desc& d = r.d;
-            const int Pix = d.OH * d.OW, imgs = d.M / Pix, bn = k == 2 ? 64 : (k == 5 ? 16 : 32), bm = k == 5 ? 32 : 64;
-            MDM_REQUIRE(n_img == 0 || n_img == imgs, "chain_create: phase %d works on %d images, the chain on %d", p, imgs, n_img);
-            n_img = imgs;
-            P.kind[q] = k; P.desc[q] = (int)ds.size(); P.tiles_n[q] = cdiv(d.N, bn); P.nblk[q] = (d.M / bm) * P.tiles_n[q];
-            P.img_sh_role[q] = Pix == 64 ? 0 : (bm == 32 ? 1 : 2);
-            target += (unsigned)P.tiles_n[q];
-            lds_max = lb > lds_max ? lb : lds_max;
-            ds.push_back(d);
-        }
-        P.target = target; P.prev_target = prev_target;
-        prev_target = target;
-        max_blocks = std::max(max_blocks, P.nblk[0] + P.nblk[1]);
-        di += roles[p];
-    }
-    MDM_REQUIRE(lds_max <= 160 * 1024, "chain_create: %d bytes of LDS", lds_max);
-    auto pad256 = [](int64_t v) { return (v + 255) / 256 * 256; };
-    const int64_t desc_bytes = pad256((int64_t)ds.size() * (int64_t)sizeof(mdm_gemm_desc)), ph_bytes = pad256((int64_t)n_phases * (int64_t)sizeof(ChainPhase));
-    const int64_t cnt_bytes = pad256(((int64_t)n_phases * n_img + 4) * 4);
-    *need_bytes_out = desc_bytes + ph_bytes + cnt_bytes;
-    if (!dev_buf || dev_bytes < *need_bytes_out) return 0;          // size query
-    char* base = reinterpret_cast<char*>(dev_buf);
-    hipError_t e = hipMemcpy(base, ds.data(), ds.size() * sizeof(mdm_gemm_desc), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(base + desc_bytes, ph.data(), ph.size() * sizeof(ChainPhase), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(base + desc_bytes + ph_bytes, 0, (size_t)cnt_bytes);
-    if (e != hipSuccess) return hip_fail(e, "chain_create: hipMemcpy");
-    Chain* c = new Chain();
-    c->descs_dev = reinterpret_cast<const mdm_gemm_desc*>(base);
-    c->phases_dev = reinterpret_cast<const ChainPhase*>(base + desc_bytes);
-    c->cnt_dev = reinterpret_cast<unsigned*>(base + desc_bytes + ph_bytes);
-    c->n_ph = n_phases; c->n_img = n_img;
-    c->grid = std::min(n_cu, max_blocks);              // every workgroup resident: one per CU (a workgroup asks for > 80 KiB of LDS or the grid is <= CUs anyway)
-    c->lds_bytes = std::max(lds_max, 81 * 1024);       // > half of a CU's LDS: never two of these workgroups on one CU
-    *handle_out = c;
-    return 0;
-}
-extern "C" int mdm_chain_launch(void* handle, void* stream) {
-    MDM_REQUIRE(handle, "chain_launch: null handle");
-    const Chain* c = reinterpret_cast<const Chain*>(handle);
-    hipStream_t s = pick_stream(stream);
-    static int configured = 0;
-    if (configured < c->lds_bytes) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, c->lds_bytes));
-        configured = c->lds_bytes;
-    }
-    const int n_cnt = c->n_ph * c->n_img;
-    hipLaunchKernelGGL(chain_zero_kernel, dim3((unsigned)cdiv(n_cnt, 512)), dim3(512), 0, s, c->cnt_dev, n_cnt);
-    hipLaunchKernelGGL(chain_kernel, dim3((unsigned)c->grid), dim3(512), (size_t)c->lds_bytes, s, c->descs_dev, c->phases_dev, c->n_ph, c->cnt_dev,
-                       c->n_img, c->cnt_dev + n_cnt);
-    return launch_status("chain");
-}
-// the error word of the chain's last launches (0 = every wait was satisfied); synchronises with the device
-extern "C" int mdm_chain_status(void* handle, unsigned* err_out) {
-    MDM_REQUIRE(handle && err_out, "chain_status: bad arguments");
-    const Chain* c = reinterpret_cast<const Chain*>(handle);
-    MDM_CHECK_HIP(hipMemcpy(err_out, c->cnt_dev + c->n_ph * c->n_img, 4, hipMemcpyDeviceToHost));
-    return 0;
-}
-extern "C" int mdm_chain_destroy(void* handle) {
-    delete reinterpret_cast<Chain*>(handle);
-    return 0;
 }
 
 extern "C" int mdm_gemm_can_fuse_gn_bwd(const mdm_gemm_desc* desc_host, int G) {

@@ -38,9 +38,6 @@ __device__ __forceinline__ float gn_pivot(const T* s0, const T* s1, int C0, int 
 // v = t % VB (its 8-channel vector) and the sums run over the 256/VB pixel lanes of each column.
 // (The first version reduced with __shfl_xor: 4 ds_bpermute round trips per value, 128 per thread in the
 // backward -- 20k cycles of a 36k-cycle kernel.)  scratch: K * CS_PITCH floats; out[k * VB + v].
-#ifndef MDM_GN_COLSUM_SHFL
-#define MDM_GN_COLSUM_SHFL 1        // 0: every column sum through LDS (A/B builds)
-#endif
 // Column sums inside the wave by RECURSIVE HALVING (VB a power of two: the lanes of a column are those with equal low log2(VB) bits):
 // at the step over lane bit b a lane keeps one half of the quantities it still holds (the upper half where its bit is set), sends the
 // other half to its partner and adds what the partner sends -- K/2 + K/4 + ... <= K - 1 ds_bpermute per lane for ALL K quantities
@@ -98,7 +95,7 @@ __device__ __forceinline__ void block_colsum_shfl(const float (&val)[K], float* 
 // lanes hold 8 NP fp32 registers of the slice: with the halving's K more the sampler read 5.36 - 5.47 against 5.33 ms per reverse step)
 template <int K, int NT = 256, bool SHFL = true>
 __device__ __forceinline__ void block_colsum(const float (&val)[K], float* scratch, float* out, int t, int VB, int PL) {
-    if (MDM_GN_COLSUM_SHFL && SHFL && (VB & (VB - 1)) == 0 && VB <= 8) {     // uniform
+    if (SHFL && (VB & (VB - 1)) == 0 && VB <= 8) {     // uniform
         block_colsum_shfl<K, NT>(val, scratch, out, t, VB);
         return;
     }
@@ -931,9 +928,6 @@ static int gn_check(int C0, int C1, int G, int N, int P) {
 }
 
 // channels per workgroup: whole groups, whole 16-byte vectors, at least 32 channels
-#ifndef MDM_GN_F32_CBLK32
-#define MDM_GN_F32_CBLK32 1
-#endif
 static int gn_cblk(int C, int G, int N, int P) {
     int cpg = C / G, l = cpg;
     while (l % 8) l += cpg;            // lcm(cpg, 8)
@@ -955,7 +949,7 @@ extern "C" int mdm_groupnorm_fwd(int dtype, const void* src0, int C0, const void
     int cblk = gn_cblk(C, G, N, P);
     // fp32 forward on large maps: 32 channels per workgroup = whole 128-byte lines per pixel (16 fp32 channels are 64-byte pieces:
     // 3.0 TB/s on the sampler's 32x32x128 maps), as long as the slice still fits the register-cached kernels
-    if (dtype == MDM_F32 && P > 256 && MDM_GN_F32_CBLK32) {
+    if (dtype == MDM_F32 && P > 256) {
         const int wide = gn_cblk(C, G, N, 256);
         if (cdiv(P, 256 / (wide / 8)) <= 16) cblk = wide;
     }
