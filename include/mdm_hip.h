@@ -141,6 +141,11 @@ int mdm_gemm_can_fuse_gn_fwd(const mdm_gemm_desc* desc_host, int G);
  * ("pair:two launches" when it ran two mdm_gemm) or mdm_wgrad_group_launch call on THIS host thread launched, e.g.
  * "halo<256,6,NSB,64,f32,split>", "lin2<64,64>+tapsplit"; "none" before the first call or when validation failed.  Host-side only. */
 const char* mdm_gemm_last_route(void);
+/* The name mdm_gemm_last_route would give after mdm_gemm(desc) / mdm_gemm_pair(a, b) -- the descriptor's own ws / ws_bytes decide
+ * the split, as in a launch -- without launching: host arithmetic only, the pointers are never dereferenced, no device is
+ * touched and the record of the last launch stays as it is.  "none" (and mdm_last_error) when the descriptor is refused. */
+const char* mdm_gemm_route_of(const mdm_gemm_desc* desc_host);
+const char* mdm_gemm_pair_route_of(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host);
 /* every route name mdm_gemm_last_route can return: fills up to `cap` of them into out (may be NULL), returns how many there are */
 int mdm_gemm_route_names(const char** out, int cap);
 

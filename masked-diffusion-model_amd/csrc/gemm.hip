@@ -3493,15 +3493,82 @@ constexpr int kBigMinTiles = 200;      // a tile shape is used when it still yie
 constexpr int kWgradBlocks = 256;      // per-layer weight-gradient launch (mdm_gemm): aim at this many workgroups
 constexpr int kWgradMinSlabs = 4;      // ... of at least this many 64-deep k-slabs each
 
+// ---- route record (mdm_gemm_last_route): which kernel and which second stage the last call on this host thread launched.
+// One table: X(enum, kernel name, second stages it can take: T = tap-split epilogue, K = split-K reduce).  A route is
+// kernel * 3 + stage; the names of all three stages exist, mdm_gemm_route_names lists the ones the mask allows.
+enum RouteStage { S_NONE = 0, S_TAPSPLIT = 1, S_SPLITK = 2 };
+constexpr int TSPLIT = 1 << S_TAPSPLIT, KSPLIT = 1 << S_SPLITK;
+#define MDM_GEMM_ROUTES(X)                                                                                                      \
+    X(R_SKINNY_F32, "linear_skinny_f32", 0) X(R_TN_SKINNY_F32, "tn_skinny_f32", 0)                                              \
+    X(R_LIN_SPLIT_128, "lin_split<128>", 0) X(R_LIN_SPLIT_64, "lin_split<64>", 0)                                               \
+    X(R_HS_256_6_32, "halo<256,6,2,32,f32,split>", 0) X(R_HS_256_6_128, "halo<256,6,4,128,f32,split>", 0)                       \
+    X(R_HS_MIXED, "halo_mixed<256|128,f32,split>", 0) X(R_HS_256_6, "halo<256,6,NSB,64,f32,split>", 0)                          \
+    X(R_HS_128_3, "halo<128,3,3,64,f32,split>", 0) X(R_HS_128_4, "halo<128,4,3,64,f32,split>", 0)                               \
+    X(R_HS_128_6, "halo<128,6,3,64,f32,split>", 0)                                                                              \
+    X(R_HS_64_2_32, "halo<64,2,3,32,f32,split>", 0) X(R_HS_64_3_32, "halo<64,3,3,32,f32,split>", 0)                             \
+    X(R_HS_64_2_64, "halo<64,2,3,64,f32,split>", 0) X(R_HS_64_3_64, "halo<64,3,3,64,f32,split>", 0)                             \
+    X(R_HF_256_6, "halo<256,6,2,64,f32>", 0) X(R_HF_128_3, "halo<128,3,3,64,f32>", 0)                                           \
+    X(R_HF_128_4, "halo<128,4,3,64,f32>", 0) X(R_HF_128_6, "halo<128,6,3,64,f32>", 0)                                           \
+    X(R_HF_64_2_32, "halo<64,2,3,32,f32>", 0) X(R_HF_64_3_32, "halo<64,3,3,32,f32>", 0)                                         \
+    X(R_HF_64_2_64, "halo<64,2,3,64,f32>", 0) X(R_HF_64_3_64, "halo<64,3,3,64,f32>", 0)                                         \
+    X(R_F32_128, "f32_mfma<128>", KSPLIT) X(R_F32_128_SPLIT, "f32_mfma<128,split>", KSPLIT) X(R_F32_64, "f32_mfma<64>", KSPLIT) \
+    X(R_THIN_1, "conv_thin_k<1>", 0) X(R_THIN_2, "conv_thin_k<2>", 0) X(R_THIN_4, "conv_thin_k<4>", 0)                          \
+    X(R_THIN_8, "conv_thin_k<8>", 0)                                                                                            \
+    X(R_H256_6, "halo<256,6,NSB,64>", 0)                                                                                        \
+    X(R_H128_3, "halo<128,3,3,64>", 0) X(R_H128_4, "halo<128,4,3,64>", 0) X(R_H128_6, "halo<128,6,3,64>", 0)                    \
+    X(R_H64_2_32, "halo<64,2,3,32>", 0) X(R_H64_3_32, "halo<64,3,3,32>", 0)                                                     \
+    X(R_H64_2_64, "halo<64,2,3,64>", 0) X(R_H64_3_64, "halo<64,3,3,64>", 0)                                                     \
+    X(R_SMALL_4, "conv_small<4,64,32>", 0) X(R_SMALL_5, "conv_small<5,64,32>", 0)                                               \
+    X(R_SMALL_3, "conv_small<3,32,16>", 0)                                                                                      \
+    X(R_LIN2_128, "lin2<128,128>", 0) X(R_LIN2_64x128, "lin2<64,128>", TSPLIT) X(R_LIN2_64, "lin2<64,64>", TSPLIT)              \
+    X(R_WGRAD_LIN_128, "wgrad_lin<128>", KSPLIT) X(R_WGRAD_LIN_64, "wgrad_lin<64>", KSPLIT)                                     \
+    X(R_RING_128, "ring<128>", KSPLIT) X(R_RING_64, "ring<64>", TSPLIT | KSPLIT)                                                \
+    X(R_BF16_128, "bf16<128>", KSPLIT) X(R_BF16_64, "bf16<64>", KSPLIT)                                                         \
+    X(R_PAIR_SMALL_4, "pair_small<4>", 0) X(R_PAIR_SMALL_5, "pair_small<5>", 0)                                                 \
+    X(R_PAIR_SMALL_3, "pair_small<3,32,16>", 0)                                                                                 \
+    X(R_PAIR_64_2, "pair<halo<64,2,3,32>,lin2<64,64>>", 0) X(R_PAIR_64_3, "pair<halo<64,3,3,32>,lin2<64,64>>", 0)               \
+    X(R_PAIR_128_L64x128, "pair<halo<128,3,3,64>,lin2<64,128>>", 0)                                                             \
+    X(R_PAIR_128_L64, "pair<halo<128,3,3,64>,lin2<64,64>>", 0)                                                                  \
+    X(R_PAIR_256_L128, "pair<halo<256,6,NSB,64>,lin2<128,128>>", 0)                                                             \
+    X(R_PAIR_TWO, "pair:two launches", 0)                                                                                       \
+    X(R_WGROUP, "wgrad_group", KSPLIT) X(R_WGROUP_TAPS, "wgrad_taps_group", KSPLIT)
+enum GemmRoute {
+#define MDM_ROUTE_ENUM(e, n, m) e,
+    MDM_GEMM_ROUTES(MDM_ROUTE_ENUM)
+#undef MDM_ROUTE_ENUM
+    R_COUNT
+};
+static const char* const kRouteName[R_COUNT * 3] = {
+#define MDM_ROUTE_NAME(e, n, m) n, n "+tapsplit", n "+splitk",
+    MDM_GEMM_ROUTES(MDM_ROUTE_NAME)
+#undef MDM_ROUTE_NAME
+};
+static const int kRouteStages[R_COUNT] = {
+#define MDM_ROUTE_MASK(e, n, m) 1 | (m),
+    MDM_GEMM_ROUTES(MDM_ROUTE_MASK)
+#undef MDM_ROUTE_MASK
+};
+static thread_local int g_route = -1;
+static inline void route(GemmRoute r) { g_route = 3 * r; }
+static inline void route_stage(RouteStage st) { if (g_route >= 0) g_route = g_route / 3 * 3 + st; }
+
+// Opt KERNEL in to `bytes` of dynamic LDS.  One high-water mark per kernel instantiation, process-wide (one process drives one
+// device): hipFuncSetAttribute runs on the first launch and when a later launch asks for more, never once per launch -- so it
+// falls into the eager warm-up call of an instantiation, not into a graph capture.
+template <auto KERNEL>
+static int lds_opt_in(int bytes) {
+    static int configured = 0;
+    if (configured < bytes) {
+        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        configured = bytes;
+    }
+    return 0;
+}
+
 template <int BM, int BN, int LAYOUT, int NSTAGE, bool CONV>
 static int launch_ring_one(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
     constexpr int bytes = NSTAGE * (BM + BN) * 64 * 2;
-    static bool configured = false;
-    if (!configured) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_ring_kernel<BM, BN, LAYOUT, NSTAGE, CONV, 8>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = true;
-    }
+    if (int rc = lds_opt_in<&gemm_ring_kernel<BM, BN, LAYOUT, NSTAGE, CONV, 8>>(bytes)) return rc;
     hipLaunchKernelGGL((gemm_ring_kernel<BM, BN, LAYOUT, NSTAGE, CONV, 8>), grid, dim3(512), bytes, s, d);
     return 0;
 }
@@ -3525,12 +3592,7 @@ static int lin2_lds_bytes(const mdm_gemm_desc& d) {
 template <int BM, int BN, int NSTAGE, int WR, int WC>
 static int launch_lin2(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {         // the software-pipelined variant
     const int bytes = lin2_lds_bytes<BM, BN, NSTAGE>(d);
-    static int configured = 0;
-    if (configured < bytes) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = bytes;
-    }
+    if (int rc = lds_opt_in<&conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>>(bytes)) return rc;
     hipLaunchKernelGGL((conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>), grid, dim3(64 * WR * WC), bytes, s, d);
     return 0;
 }
@@ -3538,12 +3600,7 @@ static int launch_lin2(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {      
 template <int BM, int BN, int NSTAGE, int NW>
 static int launch_wgrad_lin(const mdm_gemm_desc& d, int tiles_x, int items, hipStream_t s) {
     constexpr int bytes = NSTAGE * (BM + BN) * 64 * 2;
-    static bool configured = false;
-    if (!configured) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_lin_kernel<BM, BN, NSTAGE, NW>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = true;
-    }
+    if (int rc = lds_opt_in<&wgrad_lin_kernel<BM, BN, NSTAGE, NW>>(bytes)) return rc;
     hipLaunchKernelGGL((wgrad_lin_kernel<BM, BN, NSTAGE, NW>), dim3((unsigned)items), dim3(64 * NW), bytes, s, d, tiles_x);
     return 0;
 }
@@ -3571,6 +3628,10 @@ static int halo_pieces(int bm, int OH, int OW) {           // 1-KiB pieces of on
     const int imgs = bm > OH * OW ? bm / (OH * OW) : 1, R = imgs > 1 ? OH : bm / OW;
     return (imgs * (R + 2) * (OW + 2) + 7) / 8;
 }
+// Halo pieces per wave.  A 256-pixel tile always needs the 6-piece kernels: it has at least 41 pieces (16x16 maps: 18 * 18 / 8 -> 41;
+// 32x32: 10 * 34 / 8 -> 43; 64-wide maps give 50 > 48 and are not eligible; 8- and 4-row maps with several images per tile give 45
+// and more), so there is no "<= 4 pieces per wave" 256-pixel route; launch_halo's NPA <= 8 * NPW check is the guard.
+static int halo_npw(int bm, const mdm_gemm_desc& d) { return (halo_pieces(bm, d.OH, d.OW) + 7) / 8; }
 // dynamic LDS of a conv_halo_body tile (launch_halo, and the 3x3 role of launch_pair)
 template <int BM, int NSB, int BN, int TG>
 static int halo_lds_bytes(const mdm_gemm_desc& d) {
@@ -3583,12 +3644,7 @@ template <int BM, int NPW, int NSB, int BN = 64, typename T = bf16_t, bool SPLIT
 static int launch_halo(const mdm_gemm_desc& d, hipStream_t s) {      // TG = 3: one filter row (3 taps) per barrier
     const int NPA = halo_pieces(BM, d.OH, d.OW), bytes = halo_lds_bytes<BM, NSB, BN, TG>(d);
     MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_halo: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
-    static int configured = 0;
-    if (configured < bytes) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_kernel<BM, NPW, BN, NSB, TG, T, SPLIT>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = bytes;
-    }
+    if (int rc = lds_opt_in<&conv_halo_kernel<BM, NPW, BN, NSB, TG, T, SPLIT>>(bytes)) return rc;
     dim3 grid((unsigned)((int64_t)(d.M / BM) * cdiv(d.N, BN)));
     hipLaunchKernelGGL((conv_halo_kernel<BM, NPW, BN, NSB, TG, T, SPLIT>), grid, dim3(512), bytes, s, d);
     return 0;
@@ -3610,11 +3666,7 @@ static int launch_small(const mdm_gemm_desc& d, hipStream_t s) {
     MDM_REQUIRE(small_pieces(d, BM) <= 8 * NPW && bytes <= 160 * 1024 && (BM != 64 || bytes >= 16384 + 65536 + 4096 + 512),
                 "conv_small: tile does not fit (%d bytes)", bytes);
     MDM_REQUIRE(BM == 64 || (fused_gn_cpg(d) == 8 && d.N0 % 8 == 0), "conv_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
-    static int configured = 0;
-    if (configured < bytes) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_kernel<NPW, BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = bytes;
-    }
+    if (int rc = lds_opt_in<&conv_small_kernel<NPW, BM, BN>>(bytes)) return rc;
     hipLaunchKernelGGL((conv_small_kernel<NPW, BM, BN>), dim3((unsigned)((int64_t)(d.M / BM) * cdiv(d.N, BN))), dim3(512), bytes, s, d);
     return 0;
 }
@@ -3669,28 +3721,28 @@ static int halo_tile_f32(const mdm_gemm_desc& d) {
 }
 
 // conv_halo_mixed_kernel: whole rounds of 256-pixel tiles, the remainder as 128-pixel tiles -- taken when the remainder is at most one
-// round of small tiles (otherwise two short rounds cost more than the one long round they replace).  kNotTaken = plain launch.
+// round of small tiles (otherwise two short rounds cost more than the one long round they replace).
 constexpr int MDM_SPLIT_BN128 = 160;   // 128-channel split tiles when the layer has at least this many of them
-constexpr int kNotTaken = 1;       // "this launcher does not apply" (positive: every error code, hip_fail's -2 included, is negative)
-static int launch_halo_mixed(const mdm_gemm_desc& d, hipStream_t s) {
+struct HaloMixed { int n_big, m_split, n_rest; };      // 256-pixel tiles, the pixels they cover, 128-pixel tiles behind them
+static bool halo_mixed_tiling(const mdm_gemm_desc& d, HaloMixed& t) {      // does the mixed tiling apply, and how is the layer cut
     const int tn = d.N / 64;
     const int64_t tiles = (int64_t)(d.M / 256) * tn;
     const int64_t big_m = (tiles / 256) * 256 / tn;                // M tiles of 256 pixels in whole rounds (all their channel tiles)
     const int64_t rest = (d.M / 256 - big_m) * 2 * tn;             // 128-pixel tiles behind them
-    if (d.OW != 32 || d.OH % 8 || big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return kNotTaken;
+    if (d.OW != 32 || d.OH % 8 || big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return false;
+    if (halo_pieces(256, d.OH, d.OW) > 48 || halo_pieces(128, d.OH, d.OW) > 32) return false;
+    t = {(int)(big_m * tn), (int)(big_m * 256), (int)rest};
+    return true;
+}
+static int launch_halo_mixed(const mdm_gemm_desc& d, hipStream_t s) {
+    HaloMixed t;
+    MDM_REQUIRE(halo_mixed_tiling(d, t), "conv_halo_mixed: the mixed tiling does not apply");
     const int npa = halo_pieces(256, d.OH, d.OW), npb = halo_pieces(128, d.OH, d.OW);
-    if (npa > 48 || npb > 32) return kNotTaken;
     int bytes = std::max(2 * npa * 1024 + 2 * 3 * 64 * 128 + 1024, 2 * npb * 1024 + 3 * 3 * 64 * 128 + 1024);
     bytes = std::max(bytes, 256 * 64 * 4);
     MDM_REQUIRE(bytes <= 160 * 1024, "conv_halo_mixed: tile does not fit (%d bytes)", bytes);
-    static int configured = 0;
-    if (configured < bytes) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_halo_mixed_kernel<6, 2, 4, 3>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = bytes;
-    }
-    hipLaunchKernelGGL((conv_halo_mixed_kernel<6, 2, 4, 3>), dim3((unsigned)(big_m * tn + rest)), dim3(512), bytes, s, d, (int)(big_m * tn),
-                       (int)(big_m * 256));
+    if (int rc = lds_opt_in<&conv_halo_mixed_kernel<6, 2, 4, 3>>(bytes)) return rc;
+    hipLaunchKernelGGL((conv_halo_mixed_kernel<6, 2, 4, 3>), dim3((unsigned)(t.n_big + t.n_rest)), dim3(512), bytes, s, d, t.n_big, t.m_split);
     return 0;
 }
 
@@ -3723,11 +3775,7 @@ static int launch_lin_split(const mdm_gemm_desc& d, hipStream_t s) {
     constexpr int NS = BN == 64 ? MDM_LIN_SPLIT_NS64 : 4;
     constexpr int bytes = NS * (128 * 128 + BN * 128);
     static_assert(bytes <= 160 * 1024 && bytes >= 128 * BN * 4, "lin_split: ring / epilogue tile do not fit");
-    static bool configured = false;
-    if (!configured) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lin_split_kernel<BN, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = true;
-    }
+    if (int rc = lds_opt_in<&lin_split_kernel<BN, NS>>(bytes)) return rc;
     hipLaunchKernelGGL((lin_split_kernel<BN, NS>), dim3((unsigned)((int64_t)cdiv(d.M, 128) * (d.N / BN))), dim3(512), bytes, s, d);
     return 0;
 }
@@ -3775,39 +3823,28 @@ static bool ring_eligible(const mdm_gemm_desc& d) {
 template <int BM, int BN, int LAYOUT, bool SPLIT = false>
 static int launch_f32_mfma_one(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
     constexpr int bytes = 2 * (BM + BN) * 36 * 4;
-    static bool configured = false;
-    if (!configured) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_mfma_kernel<BM, BN, LAYOUT, SPLIT>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = true;
-    }
+    if (int rc = lds_opt_in<&gemm_f32_mfma_kernel<BM, BN, LAYOUT, SPLIT>>(bytes)) return rc;
     hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, LAYOUT, SPLIT>), grid, dim3(256), bytes, s, d);
     return 0;
 }
 template <int BM, int BN>
-static int launch_f32_mfma(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
+static int launch_f32_mfma(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {      // exact products (split ones: choose_route)
     switch (d.layout) {
-        // (split products pay on the 128 x 128 tiles only: 77.6 -> 72.5 us per launch; on the 64 x 64 tiles the converting stores lengthen
-        //  a loop that is a load -> store -> barrier chain, 33 -> 51 us: measured, not taken)
-        case 0: return (d.f32_split && BM == 128) ? launch_f32_mfma_one<BM, BN, 0, BM == 128>(d, grid, s) : launch_f32_mfma_one<BM, BN, 0>(d, grid, s);
+        case 0: return launch_f32_mfma_one<BM, BN, 0>(d, grid, s);
         case 1: return launch_f32_mfma_one<BM, BN, 1>(d, grid, s);
         default: return launch_f32_mfma_one<BM, BN, 2>(d, grid, s);
     }
 }
 
 template <int BM, int BN>
-static void launch_bf16(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
+static int launch_bf16(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
     switch (d.layout) {
         case 0: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0>), grid, dim3(256), 0, s, d); break;
         case 1: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1>), grid, dim3(256), 0, s, d); break;
         default: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 2>), grid, dim3(256), 0, s, d); break;
     }
+    return 0;
 }
-
-}  // namespace mdm
-extern "C" int mdm_gemm_can_fuse_gn_bwd(const mdm_gemm_desc* desc_host, int G);
-extern "C" int mdm_gemm_can_fuse_gn_fwd(const mdm_gemm_desc* desc_host, int G);
-namespace mdm {
 
 // What mdm_gemm decides before it launches: the tile family, the reduction split, where split-K partials go.
 struct Resolved {
@@ -3871,7 +3908,7 @@ static int resolve(const mdm_gemm_desc* dh, bool planning, Resolved& r) {
     return 0;
 }
 
-// Which kernel of the conv_halo / conv_lin2 family a bf16 forward / data-gradient convolution takes (0: none of them).
+// Which kernel of the conv_halo / conv_lin2 family a bf16 forward / data-gradient convolution takes (conv_family + conv_variant).
 // Tile choice (measured per shape): the largest tile that still gives the chip ~one workgroup per CU -- whole-row halo tiles
 // of 256 / 128 pixels on the 32x32 / 16x16 maps; 64-pixel whole-image tiles on 4x4 / 8x8 (the loop there is the filter stream
 // of ONE workgroup and these maps give only 32-128 of them, so 32 output channels per workgroup: half the stream, twice the
@@ -3885,20 +3922,19 @@ static bool lin2_gn_tile(const mdm_gemm_desc& d) {
            d.IH == d.OH && d.IW == d.OW && d.OH == d.OW && (d.OW == 4 || d.OW == 8) && d.M % 64 == 0 && d.N % 64 == 0 &&
            d.C0 % 64 == 0 && d.C1 % 64 == 0 && d.Ck == d.C0 + d.C1 && d.N0 % 8 == 0 && !d.out_f32 && d.splitk <= 1;
 }
-enum ConvVar { CV_NONE = 0, CV_H256_4, CV_H256_6, CV_H128_3, CV_H128_4, CV_H128_6, CV_H64_2_32, CV_H64_3_32, CV_H64_2_64, CV_H64_3_64,
-               CV_L128, CV_L64x128, CV_L64, CV_S64_4, CV_S64_5, CV_S32_3 };
-
-static ConvVar conv_variant(const mdm_gemm_desc& d, const Resolved& r, unsigned grid_z) {
-    if (!(d.dtype == MDM_BF16 && ring_eligible(d) && d.layout == 0 && d.conv &&
-          (d.stride == 1 || (d.stride == 2 && !d.transposed && d.ups == 0)) && d.C0 <= 4096 && d.C1 <= 4096 &&
-          (d.ups == 0 || (d.splitk <= 1 && halo_tile(d) != 0)) && d.KH * d.KW <= 9 && (d.KH * d.KW) % d.splitk == 0))
-        return CV_NONE;
-    const int64_t t_mid = (int64_t)cdiv(d.M, 64) * cdiv(d.N, 128) * grid_z;
+static bool conv_family(const mdm_gemm_desc& d) {           // does the convolution take one of them at all
+    return d.dtype == MDM_BF16 && ring_eligible(d) && d.layout == 0 && d.conv &&
+           (d.stride == 1 || (d.stride == 2 && !d.transposed && d.ups == 0)) && d.C0 <= 4096 && d.C1 <= 4096 &&
+           (d.ups == 0 || (d.splitk <= 1 && halo_tile(d) != 0)) && d.KH * d.KW <= 9 && (d.KH * d.KW) % d.splitk == 0;
+}
+static GemmRoute conv_variant(const Resolved& r) {          // ... and which one (conv_family holds)
+    const mdm_gemm_desc& d = r.d;
+    const int64_t t_mid = (int64_t)cdiv(d.M, 64) * cdiv(d.N, 128) * (r.zouter * d.splitk);
     const int hb = d.splitk <= 1 ? halo_tile(d) : 0;
     if (hb) {
-        const int npw = (halo_pieces(hb, d.OH, d.OW) + 7) / 8;      // halo pieces per wave
-        if (hb == 256) return npw <= 4 ? CV_H256_4 : CV_H256_6;
-        if (hb == 128) return npw <= 3 ? CV_H128_3 : npw <= 4 ? CV_H128_4 : CV_H128_6;
+        const int npw = halo_npw(hb, d);
+        if (hb == 256) return R_H256_6;
+        if (hb == 128) return npw <= 3 ? R_H128_3 : npw <= 4 ? R_H128_4 : R_H128_6;
         if (d.N % 32 == 0 && (!(d.gnb_x || d.gnf_out) || d.N / (d.gnb_x ? d.gnb_G : d.gnf_G) <= 32)) {
             // 128-channel superslabs with the reduction split over the waves (conv_small_body) where the channel counts allow
             const int spw = (small_pieces(d) + 7) / 8;
@@ -3907,19 +3943,19 @@ static ConvVar conv_variant(const mdm_gemm_desc& d, const Resolved& r, unsigned 
                 // streaming a quarter of the filter bytes; its epilogue is the register one only (C / G == 8 where a GroupNorm is fused)
                 if (d.OH * d.OW == 16 && d.M % 32 == 0 && d.N % 16 == 0 && fused_gn_cpg(d) == 8 && (d.N0 & 7) == 0 &&
                     (int64_t)(d.M / 64) * (d.N / 32) < kBigMinTiles && (small_pieces(d, 32) + 7) / 8 <= 3)
-                    return CV_S32_3;
-                return spw <= 4 ? CV_S64_4 : CV_S64_5;
+                    return R_SMALL_3;
+                return spw <= 4 ? R_SMALL_4 : R_SMALL_5;
             }
-            return npw <= 2 ? CV_H64_2_32 : CV_H64_3_32;
+            return npw <= 2 ? R_H64_2_32 : R_H64_3_32;
         }
-        return npw <= 2 ? CV_H64_2_64 : CV_H64_3_64;
+        return npw <= 2 ? R_H64_2_64 : R_H64_3_64;
     }
-    if ((d.gnb_x || d.gnf_out) && lin2_gn_tile(d)) return CV_L64;      // the fused epilogues live on the 64 x 64 tile
-    if (r.big) return CV_L128;
+    if ((d.gnb_x || d.gnf_out) && lin2_gn_tile(d)) return R_LIN2_64;      // the fused epilogues live on the 64 x 64 tile
+    if (r.big) return R_LIN2_128;
     // (the qkv projection of the 8x8 maps is 192 such tiles -- 384 tiles of 64 x 64 = 1.5 rounds today; taking them from 180 on was level:
     //  3.582 vs 3.586 ms/step)
-    if (d.N >= 128 && t_mid >= kBigMinTiles) return CV_L64x128;
-    return CV_L64;
+    if (d.N >= 128 && t_mid >= kBigMinTiles) return R_LIN2_64x128;
+    return R_LIN2_64;
 }
 
 static int check_fused_gn(const mdm_gemm_desc& d) {
@@ -3932,194 +3968,163 @@ static int check_fused_gn(const mdm_gemm_desc& d) {
     return 0;
 }
 
-// ---- route record (mdm_gemm_last_route): which kernel and which second stage the last call on this host thread launched.
-// One table: X(enum, kernel name, second stages it can take: T = tap-split epilogue, K = split-K reduce).  A route is
-// kernel * 3 + stage; the names of all three stages exist, mdm_gemm_route_names lists the ones the mask allows.
-enum RouteStage { S_NONE = 0, S_TAPSPLIT = 1, S_SPLITK = 2 };
-constexpr int TSPLIT = 1 << S_TAPSPLIT, KSPLIT = 1 << S_SPLITK;
-#define MDM_GEMM_ROUTES(X)                                                                                                      \
-    X(R_SKINNY_F32, "linear_skinny_f32", 0) X(R_TN_SKINNY_F32, "tn_skinny_f32", 0)                                              \
-    X(R_LIN_SPLIT_128, "lin_split<128>", 0) X(R_LIN_SPLIT_64, "lin_split<64>", 0)                                               \
-    X(R_HS_256_4_32, "halo<256,4,2,32,f32,split>", 0) X(R_HS_256_6_32, "halo<256,6,2,32,f32,split>", 0)                         \
-    X(R_HS_256_4_128, "halo<256,4,4,128,f32,split>", 0) X(R_HS_256_6_128, "halo<256,6,4,128,f32,split>", 0)                     \
-    X(R_HS_MIXED, "halo_mixed<256|128,f32,split>", 0)                                                                           \
-    X(R_HS_256_4, "halo<256,4,NSB,64,f32,split>", 0) X(R_HS_256_6, "halo<256,6,NSB,64,f32,split>", 0)                           \
-    X(R_HS_128_3, "halo<128,3,3,64,f32,split>", 0) X(R_HS_128_4, "halo<128,4,3,64,f32,split>", 0)                               \
-    X(R_HS_128_6, "halo<128,6,3,64,f32,split>", 0)                                                                              \
-    X(R_HS_64_2_32, "halo<64,2,3,32,f32,split>", 0) X(R_HS_64_3_32, "halo<64,3,3,32,f32,split>", 0)                             \
-    X(R_HS_64_2_64, "halo<64,2,3,64,f32,split>", 0) X(R_HS_64_3_64, "halo<64,3,3,64,f32,split>", 0)                             \
-    X(R_HF_256_4, "halo<256,4,2,64,f32>", 0) X(R_HF_256_6, "halo<256,6,2,64,f32>", 0)                                           \
-    X(R_HF_128_3, "halo<128,3,3,64,f32>", 0) X(R_HF_128_4, "halo<128,4,3,64,f32>", 0)                                           \
-    X(R_HF_128_6, "halo<128,6,3,64,f32>", 0)                                                                                    \
-    X(R_HF_64_2_32, "halo<64,2,3,32,f32>", 0) X(R_HF_64_3_32, "halo<64,3,3,32,f32>", 0)                                         \
-    X(R_HF_64_2_64, "halo<64,2,3,64,f32>", 0) X(R_HF_64_3_64, "halo<64,3,3,64,f32>", 0)                                         \
-    X(R_F32_128, "f32_mfma<128>", KSPLIT) X(R_F32_128_SPLIT, "f32_mfma<128,split>", KSPLIT) X(R_F32_64, "f32_mfma<64>", KSPLIT) \
-    X(R_THIN_1, "conv_thin_k<1>", 0) X(R_THIN_2, "conv_thin_k<2>", 0) X(R_THIN_4, "conv_thin_k<4>", 0)                          \
-    X(R_THIN_8, "conv_thin_k<8>", 0)                                                                                            \
-    X(R_H256_4, "halo<256,4,NSB,64>", 0) X(R_H256_6, "halo<256,6,NSB,64>", 0)                                                   \
-    X(R_H128_3, "halo<128,3,3,64>", 0) X(R_H128_4, "halo<128,4,3,64>", 0) X(R_H128_6, "halo<128,6,3,64>", 0)                    \
-    X(R_H64_2_32, "halo<64,2,3,32>", 0) X(R_H64_3_32, "halo<64,3,3,32>", 0)                                                     \
-    X(R_H64_2_64, "halo<64,2,3,64>", 0) X(R_H64_3_64, "halo<64,3,3,64>", 0)                                                     \
-    X(R_SMALL_4, "conv_small<4,64,32>", 0) X(R_SMALL_5, "conv_small<5,64,32>", 0)                                               \
-    X(R_SMALL_3, "conv_small<3,32,16>", 0)                                                                                      \
-    X(R_LIN2_128, "lin2<128,128>", 0) X(R_LIN2_64x128, "lin2<64,128>", TSPLIT) X(R_LIN2_64, "lin2<64,64>", TSPLIT)              \
-    X(R_WGRAD_LIN_128, "wgrad_lin<128>", KSPLIT) X(R_WGRAD_LIN_64, "wgrad_lin<64>", KSPLIT)                                     \
-    X(R_RING_128, "ring<128>", KSPLIT) X(R_RING_64, "ring<64>", TSPLIT | KSPLIT)                                                \
-    X(R_BF16_128, "bf16<128>", KSPLIT) X(R_BF16_64, "bf16<64>", KSPLIT)                                                         \
-    X(R_PAIR_SMALL_4, "pair_small<4>", 0) X(R_PAIR_SMALL_5, "pair_small<5>", 0)                                                 \
-    X(R_PAIR_SMALL_3, "pair_small<3,32,16>", 0)                                                                                 \
-    X(R_PAIR_64_2, "pair<halo<64,2,3,32>,lin2<64,64>>", 0) X(R_PAIR_64_3, "pair<halo<64,3,3,32>,lin2<64,64>>", 0)               \
-    X(R_PAIR_128_L64x128, "pair<halo<128,3,3,64>,lin2<64,128>>", 0)                                                             \
-    X(R_PAIR_128_L64, "pair<halo<128,3,3,64>,lin2<64,64>>", 0)                                                                  \
-    X(R_PAIR_256_L128, "pair<halo<256,6,NSB,64>,lin2<128,128>>", 0)                                                             \
-    X(R_PAIR_TWO, "pair:two launches", 0)                                                                                       \
-    X(R_WGROUP, "wgrad_group", KSPLIT) X(R_WGROUP_TAPS, "wgrad_taps_group", KSPLIT)
-enum GemmRoute {
-#define MDM_ROUTE_ENUM(e, n, m) e,
-    MDM_GEMM_ROUTES(MDM_ROUTE_ENUM)
-#undef MDM_ROUTE_ENUM
-    R_COUNT
-};
-static const char* const kRouteName[R_COUNT * 3] = {
-#define MDM_ROUTE_NAME(e, n, m) n, n "+tapsplit", n "+splitk",
-    MDM_GEMM_ROUTES(MDM_ROUTE_NAME)
-#undef MDM_ROUTE_NAME
-};
-static const int kRouteStages[R_COUNT] = {
-#define MDM_ROUTE_MASK(e, n, m) 1 | (m),
-    MDM_GEMM_ROUTES(MDM_ROUTE_MASK)
-#undef MDM_ROUTE_MASK
-};
-static thread_local int g_route = -1;
-static inline int route(GemmRoute r) { g_route = 3 * r; return 0; }
-static inline void route_stage(RouteStage st) { if (g_route >= 0) g_route = g_route / 3 * 3 + st; }
+// ---- the dispatch rule, in two halves: choose_route decides (host arithmetic on the resolved descriptor only: no HIP call, no
+// state), launch_route launches what was chosen.  mdm_gemm_route_of asks the first half alone.
+static GemmRoute choose_route(const Resolved& r) {
+    const mdm_gemm_desc& d = r.d;
+    if (d.dtype == MDM_F32 && d.layout == 0 && !d.conv && d.M <= 32 && d.K % 64 == 0 && d.K <= 512 && d.splitk <= 1 &&
+        d.batch == 1 && !d.rowvec && !d.resid && !d.acc0 && d.N0 == d.N && d.lda % 4 == 0 && d.ldb % 4 == 0)
+        return R_SKINNY_F32;
+    // weight gradient of a linear layer over a batch-sized reduction (the time-embedding path)
+    if (d.dtype == MDM_F32 && d.layout == 2 && !d.conv && d.batch == 1 && d.K <= 128 && d.splitk <= 1 && d.N0 == d.N && !d.D1 &&
+        d.M % 4 == 0 && d.N % 4 == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 && d.ldd0 % 4 == 0 && !d.bias && !d.rowvec && !d.resid)
+        return R_TN_SKINNY_F32;
+    if (const int lsb = lin_split_tile(d)) return lsb == 128 ? R_LIN_SPLIT_128 : R_LIN_SPLIT_64;
+    if (halo_small_n_split(d)) return R_HS_256_6_32;
+    if (const int hb_exact = halo_tile_f32(d)) {
+        // exact-fp32 3x3 convolutions on the halo kernel (forward, folded upsample, transposed shadow): MFMA-bound
+        const bool half_n = (int64_t)(d.M / 64) * (d.N / 64) < kBigMinTiles && d.N % 32 == 0;   // 4x4 maps: 32-channel tiles, twice the workgroups
+        if (d.B_split != nullptr && !d.transposed) {
+            // fp32 storage, products as bf16 hi / lo pairs on the bf16 matrix pipe (conv_halo_body<..., SPLIT>); this arm decides
+            // with the split-products tile, the exact arm below with the exact one
+            const int hb = halo_tile_f32_split(d, hb_exact), npw = halo_npw(hb, d);
+            if (hb == 256) {
+                // 256 pixels x 128 channels (one tap per barrier, four filter stages): the halo is staged and split once for twice the
+                // channels and a wave multiplies 4 x 4 fragments per tap -- 16 fragment reads for 48 MFMAs where the 64-channel tile reads
+                // 12 for 24; half as many tiles, so a 16x16 layer at sample_num = 100 is ONE round of workgroups instead of 1.56 in two
+                if (d.N % 128 == 0 && (d.OW == 16 || d.OW == 32) && (int64_t)(d.M / 256) * (d.N / 128) >= MDM_SPLIT_BN128) return R_HS_256_6_128;
+                HaloMixed t;
+                if (halo_mixed_tiling(d, t)) return R_HS_MIXED;      // whole rounds of 256-pixel tiles + a short round of 128-pixel ones
+                return R_HS_256_6;
+            }
+            if (hb == 128) return npw <= 3 ? R_HS_128_3 : npw <= 4 ? R_HS_128_4 : R_HS_128_6;
+            if (half_n) return npw <= 2 ? R_HS_64_2_32 : R_HS_64_3_32;
+            return npw <= 2 ? R_HS_64_2_64 : R_HS_64_3_64;
+        }
+        const int npw = halo_npw(hb_exact, d);
+        if (hb_exact == 256) return R_HF_256_6;
+        if (hb_exact == 128) return npw <= 3 ? R_HF_128_3 : npw <= 4 ? R_HF_128_4 : R_HF_128_6;
+        if (half_n) return npw <= 2 ? R_HF_64_2_32 : R_HF_64_3_32;
+        return npw <= 2 ? R_HF_64_2_64 : R_HF_64_3_64;
+    }
+    if (d.dtype == MDM_F32) {
+        // exact-fp32 MFMA kernel; 128 x 128 tiles when that still gives about one workgroup per CU
+        if (!(d.M >= 128 && d.N >= 128 && (int64_t)cdiv(d.M, 128) * cdiv(d.N, 128) * (r.zouter * d.splitk) >= kBigMinTiles)) return R_F32_64;
+        // (split products pay on the 128 x 128 tiles only: 77.6 -> 72.5 us per launch; on the 64 x 64 tiles the converting stores lengthen
+        //  a loop that is a load -> store -> barrier chain, 33 -> 51 us: measured, not taken)
+        return d.layout == 0 && d.f32_split ? R_F32_128_SPLIT : R_F32_128;
+    }
+    if (thin_conv(d)) {
+        // the 8-channel ends of the U-Net: the first convolution and the data gradient of the last
+        const int nj = cdiv(d.N, 16);
+        return nj == 1 ? R_THIN_1 : nj == 2 ? R_THIN_2 : nj <= 4 ? R_THIN_4 : R_THIN_8;
+    }
+    if (conv_family(d)) return conv_variant(r);
+    if (wgrad_lin_eligible(d)) return r.big ? R_WGRAD_LIN_128 : R_WGRAD_LIN_64;
+    if (ring_eligible(d)) return r.big ? R_RING_128 : R_RING_64;
+    return r.big ? R_BF16_128 : R_BF16_64;
+}
+// the second launch of a split reduction, if any
+static RouteStage second_stage(const Resolved& r) { return r.tap_split ? S_TAPSPLIT : (r.d.splitk > 1 && r.d.ws) ? S_SPLITK : S_NONE; }
+
+// What mdm_gemm settles before it launches: the resolved descriptor and its route, or an error.
+static int plan_route(const mdm_gemm_desc* dh, Resolved& r, GemmRoute& rt) {
+    if (int rc = resolve(dh, false, r)) return rc;
+    if (int rc = check_fused_gn(r.d)) return rc;
+    const int64_t grid_z = (int64_t)r.zouter * r.d.splitk;
+    MDM_REQUIRE(r.tiles < (1ll << 31), "gemm: grid too large");
+    MDM_REQUIRE(grid_z <= 65535, "gemm: grid.z=%u too large", (unsigned)grid_z);
+    rt = choose_route(r);
+    if (rt == R_WGRAD_LIN_128 || rt == R_WGRAD_LIN_64) MDM_REQUIRE(r.tiles * grid_z < (1ll << 30), "gemm: grid too large");
+    return 0;
+}
+
+template <int NJ>
+static int launch_thin(const mdm_gemm_desc& d, hipStream_t s) {
+    const unsigned nb = (unsigned)std::min(cdiv(cdiv(d.M, 16), 4), 1024);
+    hipLaunchKernelGGL((conv_thin_k_kernel<NJ>), dim3(nb), dim3(256), 0, s, d);
+    return 0;
+}
+static int launch_route(GemmRoute rt, const Resolved& r, hipStream_t s) {
+    const mdm_gemm_desc& d = r.d;
+    const dim3 grid((unsigned)r.tiles, 1, (unsigned)(r.zouter * d.splitk));      // tiles of the shape resolve chose
+    switch (rt) {
+        case R_SKINNY_F32:      // opts in to its largest tile (K = 512) on first use, whatever K is
+            if (int rc = lds_opt_in<&linear_skinny_f32_kernel>(32 * 512 * 4)) return rc;
+            hipLaunchKernelGGL(linear_skinny_f32_kernel, dim3((unsigned)cdiv(d.N, 16)), dim3(256), 32 * (d.K > 16 * 17 ? d.K : 16 * 17) * 4, s, d);
+            return 0;
+        case R_TN_SKINNY_F32:
+            if (int rc = lds_opt_in<&tn_skinny_f32_kernel>(d.K * 128 * 4)) return rc;
+            hipLaunchKernelGGL(tn_skinny_f32_kernel, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 64))), dim3(256), d.K * 128 * 4, s, d);
+            return 0;
+        case R_LIN_SPLIT_128: return launch_lin_split<128>(d, s);
+        case R_LIN_SPLIT_64: return launch_lin_split<64>(d, s);
+        case R_HS_256_6_32: return launch_halo<256, 6, 2, 32, float, true>(d, s);
+        case R_HS_256_6_128: return launch_halo<256, 6, 4, 128, float, true, 1>(d, s);
+        case R_HS_MIXED: return launch_halo_mixed(d, s);
+        case R_HS_256_6: return launch_halo<256, 6, MDM_SPLIT_NSB256, 64, float, true>(d, s);
+        case R_HS_128_3: return launch_halo<128, 3, 3, 64, float, true>(d, s);
+        case R_HS_128_4: return launch_halo<128, 4, 3, 64, float, true>(d, s);
+        case R_HS_128_6: return launch_halo<128, 6, 3, 64, float, true>(d, s);
+        case R_HS_64_2_32: return launch_halo<64, 2, 3, 32, float, true>(d, s);
+        case R_HS_64_3_32: return launch_halo<64, 3, 3, 32, float, true>(d, s);
+        case R_HS_64_2_64: return launch_halo<64, 2, 3, 64, float, true>(d, s);
+        case R_HS_64_3_64: return launch_halo<64, 3, 3, 64, float, true>(d, s);
+        case R_HF_256_6: return launch_halo<256, 6, 2, 64, float>(d, s);
+        case R_HF_128_3: return launch_halo<128, 3, 3, 64, float>(d, s);
+        case R_HF_128_4: return launch_halo<128, 4, 3, 64, float>(d, s);
+        case R_HF_128_6: return launch_halo<128, 6, 3, 64, float>(d, s);
+        case R_HF_64_2_32: return launch_halo<64, 2, 3, 32, float>(d, s);
+        case R_HF_64_3_32: return launch_halo<64, 3, 3, 32, float>(d, s);
+        case R_HF_64_2_64: return launch_halo<64, 2, 3, 64, float>(d, s);
+        case R_HF_64_3_64: return launch_halo<64, 3, 3, 64, float>(d, s);
+        case R_F32_128: return launch_f32_mfma<128, 128>(d, dim3((unsigned)((int64_t)cdiv(d.M, 128) * cdiv(d.N, 128)), 1, grid.z), s);
+        case R_F32_128_SPLIT:
+            return launch_f32_mfma_one<128, 128, 0, true>(d, dim3((unsigned)((int64_t)cdiv(d.M, 128) * cdiv(d.N, 128)), 1, grid.z), s);
+        case R_F32_64: return launch_f32_mfma<64, 64>(d, grid, s);
+        case R_THIN_1: return launch_thin<1>(d, s);
+        case R_THIN_2: return launch_thin<2>(d, s);
+        case R_THIN_4: return launch_thin<4>(d, s);
+        case R_THIN_8: return launch_thin<8>(d, s);
+        case R_H256_6: return launch_halo<256, 6, MDM_NSB256>(d, s);
+        case R_H128_3: return launch_halo<128, 3, 3>(d, s);
+        case R_H128_4: return launch_halo<128, 4, 3>(d, s);
+        case R_H128_6: return launch_halo<128, 6, 3>(d, s);
+        case R_H64_2_32: return launch_halo<64, 2, 3, 32>(d, s);
+        case R_H64_3_32: return launch_halo<64, 3, 3, 32>(d, s);
+        case R_H64_2_64: return launch_halo<64, 2, 3>(d, s);
+        case R_H64_3_64: return launch_halo<64, 3, 3>(d, s);
+        case R_SMALL_4: return launch_small<4>(d, s);
+        case R_SMALL_5: return launch_small<5>(d, s);
+        case R_SMALL_3: return launch_small<3, 32, 16>(d, s);
+        case R_LIN2_128: return launch_lin2<128, 128, 3, 4, 2>(d, grid, s);
+        case R_LIN2_64x128: return launch_lin2<64, 128, 3, 2, 4>(d, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 128)), 1, grid.z), s);
+        case R_LIN2_64: return launch_lin2<64, 64, 4, 4, 2>(d, grid, s);
+        case R_WGRAD_LIN_128: return launch_wgrad_lin<128, 128, 3, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s);
+        case R_WGRAD_LIN_64: return launch_wgrad_lin<64, 64, 4, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s);
+        case R_RING_128: return launch_ring<128, 128, 3>(d, grid, s);
+        case R_RING_64: return launch_ring<64, 64, 4>(d, grid, s);
+        case R_BF16_128: return launch_bf16<128, 128>(d, grid, s);
+        case R_BF16_64: return launch_bf16<64, 64>(d, grid, s);
+        default: set_error("gemm: route %d is not an mdm_gemm route", (int)rt); return -1;   // (pairs and groups: entry points of their own)
+    }
+}
 
 static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
     Resolved r;
+    GemmRoute rt;
     g_route = -1;
-    if (int rc = resolve(dh, false, r)) return rc;
+    if (int rc = plan_route(dh, r, rt)) return rc;
     const mdm_gemm_desc& d = r.d;
-    const bool big = r.big;
-    if (int rc0 = check_fused_gn(d)) return rc0;
-    MDM_REQUIRE(r.tiles < (1ll << 31), "gemm: grid too large");
-    dim3 grid((unsigned)r.tiles, 1, (unsigned)(r.zouter * d.splitk));
-    MDM_REQUIRE(grid.z <= 65535, "gemm: grid.z=%u too large", grid.z);
-    int rc = 0;
-    if (d.dtype == MDM_F32 && d.layout == 0 && !d.conv && d.M <= 32 && d.K % 64 == 0 && d.K <= 512 && d.splitk <= 1 &&
-        d.batch == 1 && !d.rowvec && !d.resid && !d.acc0 && d.N0 == d.N && d.lda % 4 == 0 && d.ldb % 4 == 0) {
-        route(R_SKINNY_F32);
-        static bool configured = false;
-        const int bytes = 32 * (d.K > 16 * 17 ? d.K : 16 * 17) * 4;
-        if (!configured) {
-            MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&linear_skinny_f32_kernel),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 512 * 4));
-            configured = true;
-        }
-        hipLaunchKernelGGL(linear_skinny_f32_kernel, dim3((unsigned)cdiv(d.N, 16)), dim3(256), bytes, s, d);
-    } else if (d.dtype == MDM_F32 && d.layout == 2 && !d.conv && d.batch == 1 && d.K <= 128 && d.splitk <= 1 && d.N0 == d.N && !d.D1 &&
-               d.M % 4 == 0 && d.N % 4 == 0 && d.lda % 4 == 0 && d.ldb % 4 == 0 && d.ldd0 % 4 == 0 && !d.bias && !d.rowvec && !d.resid) {
-        // weight gradient of a linear layer over a batch-sized reduction (the time-embedding path)
-        route(R_TN_SKINNY_F32);
-        const int bytes = d.K * 128 * 4;
-        static int configured = 0;
-        if (configured < bytes) {
-            MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&tn_skinny_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-            configured = bytes;
-        }
-        hipLaunchKernelGGL(tn_skinny_f32_kernel, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 64))), dim3(256), bytes, s, d);
-    } else if (const int lsb = lin_split_tile(d)) {
-        rc = lsb == 128 ? route(R_LIN_SPLIT_128) + launch_lin_split<128>(d, s) : route(R_LIN_SPLIT_64) + launch_lin_split<64>(d, s);
-    } else if (halo_small_n_split(d)) {
-        rc = (halo_pieces(256, d.OH, d.OW) + 7) / 8 <= 4 ? route(R_HS_256_4_32) + launch_halo<256, 4, 2, 32, float, true>(d, s)
-                                                          : route(R_HS_256_6_32) + launch_halo<256, 6, 2, 32, float, true>(d, s);
-    } else if (const int hb32_exact = halo_tile_f32(d)) {
-        // exact-fp32 3x3 convolutions on the halo kernel (forward, folded upsample, transposed shadow): MFMA-bound
-        const int hb32 = hb32_exact;
-        const int npw = (halo_pieces(hb32, d.OH, d.OW) + 7) / 8;
-        if (d.B_split != nullptr && !d.transposed) {
-            // fp32 storage, products as bf16 hi / lo pairs on the bf16 matrix pipe (conv_halo_body<..., SPLIT>)
-            const int hb32 = halo_tile_f32_split(d, hb32_exact);
-            const int npw = (halo_pieces(hb32, d.OH, d.OW) + 7) / 8;
-            // 256 pixels x 128 channels (one tap per barrier, four filter stages): the halo is staged and split once for twice the
-            // channels and a wave multiplies 4 x 4 fragments per tap -- 16 fragment reads for 48 MFMAs where the 64-channel tile reads
-            // 12 for 24; half as many tiles, so a 16x16 layer at sample_num = 100 is ONE round of workgroups instead of 1.56 in two
-            if (hb32 == 256 && d.N % 128 == 0 && (d.OW == 16 || d.OW == 32) &&
-                (int64_t)(d.M / 256) * (d.N / 128) >= MDM_SPLIT_BN128) {
-                rc = npw <= 4 ? route(R_HS_256_4_128) + launch_halo<256, 4, 4, 128, float, true, 1>(d, s)
-                               : route(R_HS_256_6_128) + launch_halo<256, 6, 4, 128, float, true, 1>(d, s);
-            } else
-            if (hb32 == 256 && (rc = launch_halo_mixed(d, s)) != kNotTaken) { route(R_HS_MIXED); /* whole rounds of 256-pixel tiles + a short round of 128-pixel ones */ }
-            else if (hb32 == 256) rc = npw <= 4 ? route(R_HS_256_4) + launch_halo<256, 4, MDM_SPLIT_NSB256, 64, float, true>(d, s)
-                                                 : route(R_HS_256_6) + launch_halo<256, 6, MDM_SPLIT_NSB256, 64, float, true>(d, s);
-            else if (hb32 == 128) rc = npw <= 3 ? route(R_HS_128_3) + launch_halo<128, 3, 3, 64, float, true>(d, s)
-                                     : npw <= 4 ? route(R_HS_128_4) + launch_halo<128, 4, 3, 64, float, true>(d, s)
-                                                : route(R_HS_128_6) + launch_halo<128, 6, 3, 64, float, true>(d, s);
-            else if ((int64_t)(d.M / 64) * (d.N / 64) < kBigMinTiles && d.N % 32 == 0)
-                rc = npw <= 2 ? route(R_HS_64_2_32) + launch_halo<64, 2, 3, 32, float, true>(d, s) : route(R_HS_64_3_32) + launch_halo<64, 3, 3, 32, float, true>(d, s);
-            else rc = npw <= 2 ? route(R_HS_64_2_64) + launch_halo<64, 2, 3, 64, float, true>(d, s) : route(R_HS_64_3_64) + launch_halo<64, 3, 3, 64, float, true>(d, s);
-        } else
-        if (hb32 == 256) rc = npw <= 4 ? route(R_HF_256_4) + launch_halo<256, 4, 2, 64, float>(d, s) : route(R_HF_256_6) + launch_halo<256, 6, 2, 64, float>(d, s);
-        else if (hb32 == 128) rc = npw <= 3 ? route(R_HF_128_3) + launch_halo<128, 3, 3, 64, float>(d, s)
-                                 : npw <= 4 ? route(R_HF_128_4) + launch_halo<128, 4, 3, 64, float>(d, s)
-                                            : route(R_HF_128_6) + launch_halo<128, 6, 3, 64, float>(d, s);
-        else if ((int64_t)(d.M / 64) * (d.N / 64) < kBigMinTiles && d.N % 32 == 0)       // 4x4 maps: 32-channel tiles, twice the workgroups
-            rc = npw <= 2 ? route(R_HF_64_2_32) + launch_halo<64, 2, 3, 32, float>(d, s) : route(R_HF_64_3_32) + launch_halo<64, 3, 3, 32, float>(d, s);
-        else rc = npw <= 2 ? route(R_HF_64_2_64) + launch_halo<64, 2, 3, 64, float>(d, s) : route(R_HF_64_3_64) + launch_halo<64, 3, 3, 64, float>(d, s);
-    } else if (d.dtype == MDM_F32) {
-        // exact-fp32 MFMA kernel; 128 x 128 tiles when that still gives about one workgroup per CU
-        const bool big32 = d.M >= 128 && d.N >= 128 && (int64_t)cdiv(d.M, 128) * cdiv(d.N, 128) * grid.z >= kBigMinTiles;
-        rc = big32 ? route(d.layout == 0 && d.f32_split ? R_F32_128_SPLIT : R_F32_128) +
-                         launch_f32_mfma<128, 128>(d, dim3((unsigned)((int64_t)cdiv(d.M, 128) * cdiv(d.N, 128)), 1, grid.z), s)
-                   : route(R_F32_64) + launch_f32_mfma<64, 64>(d, grid, s);
-    } else if (thin_conv(d)) {
-        // the 8-channel ends of the U-Net: the first convolution and the data gradient of the last
-        const unsigned nb = (unsigned)std::min(cdiv(cdiv(d.M, 16), 4), 1024);
-        switch (cdiv(d.N, 16)) {
-            case 1: route(R_THIN_1); hipLaunchKernelGGL((conv_thin_k_kernel<1>), dim3(nb), dim3(256), 0, s, d); break;
-            case 2: route(R_THIN_2); hipLaunchKernelGGL((conv_thin_k_kernel<2>), dim3(nb), dim3(256), 0, s, d); break;
-            case 3: case 4: route(R_THIN_4); hipLaunchKernelGGL((conv_thin_k_kernel<4>), dim3(nb), dim3(256), 0, s, d); break;
-            default: route(R_THIN_8); hipLaunchKernelGGL((conv_thin_k_kernel<8>), dim3(nb), dim3(256), 0, s, d); break;
-        }
-    } else if (const ConvVar cv = conv_variant(d, r, grid.z)) {
-        const dim3 g2((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 128)), 1, grid.z);
-        switch (cv) {
-            case CV_H256_4: rc = route(R_H256_4) + launch_halo<256, 4, MDM_NSB256>(d, s); break;
-            case CV_H256_6: rc = route(R_H256_6) + launch_halo<256, 6, MDM_NSB256>(d, s); break;
-            case CV_H128_3: rc = route(R_H128_3) + launch_halo<128, 3, 3>(d, s); break;
-            case CV_H128_4: rc = route(R_H128_4) + launch_halo<128, 4, 3>(d, s); break;
-            case CV_H128_6: rc = route(R_H128_6) + launch_halo<128, 6, 3>(d, s); break;
-            case CV_H64_2_32: rc = route(R_H64_2_32) + launch_halo<64, 2, 3, 32>(d, s); break;
-            case CV_H64_3_32: rc = route(R_H64_3_32) + launch_halo<64, 3, 3, 32>(d, s); break;
-            case CV_H64_2_64: rc = route(R_H64_2_64) + launch_halo<64, 2, 3>(d, s); break;
-            case CV_H64_3_64: rc = route(R_H64_3_64) + launch_halo<64, 3, 3>(d, s); break;
-            case CV_S64_4: rc = route(R_SMALL_4) + launch_small<4>(d, s); break;
-            case CV_S64_5: rc = route(R_SMALL_5) + launch_small<5>(d, s); break;
-            case CV_S32_3: rc = route(R_SMALL_3) + launch_small<3, 32, 16>(d, s); break;
-            case CV_L128: rc = route(R_LIN2_128) + launch_lin2<128, 128, 3, 4, 2>(d, grid, s); break;
-            case CV_L64x128: rc = route(R_LIN2_64x128) + launch_lin2<64, 128, 3, 2, 4>(d, g2, s); break;
-            default: rc = route(R_LIN2_64) + launch_lin2<64, 64, 4, 4, 2>(d, grid, s); break;
-        }
-    } else if (wgrad_lin_eligible(d)) {
-        MDM_REQUIRE((int64_t)grid.x * grid.z < (1ll << 30), "gemm: grid too large");
-        rc = big ? route(R_WGRAD_LIN_128) + launch_wgrad_lin<128, 128, 3, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s)
-                 : route(R_WGRAD_LIN_64) + launch_wgrad_lin<64, 64, 4, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s);
-    } else if (ring_eligible(d)) {
-        rc = big ? route(R_RING_128) + launch_ring<128, 128, 3>(d, grid, s) : route(R_RING_64) + launch_ring<64, 64, 4>(d, grid, s);
-    } else if (big) {
-        route(R_BF16_128);
-        launch_bf16<128, 128>(d, grid, s);
-    } else {
-        route(R_BF16_64);
-        launch_bf16<64, 64>(d, grid, s);
-    }
-    if (rc) return rc;
-    if (r.tap_split) {
-        route_stage(S_TAPSPLIT);
+    route(rt);                  // before the launch: a failing launch still reports the route it took
+    if (int rc = launch_route(rt, r, s)) return rc;
+    const RouteStage st = second_stage(r);
+    route_stage(st);
+    if (st == S_TAPSPLIT) {
         const int64_t total4 = (int64_t)d.M * d.N / 4;
         int64_t nb = (total4 + 255) / 256;
         hipLaunchKernelGGL((splitk_epilogue_kernel<bf16_t>), dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, s, d);
-    } else if (d.splitk > 1 && d.ws) {
-        route_stage(S_SPLITK);
+    } else if (st == S_SPLITK) {
         const int64_t total4 = (int64_t)r.zouter * d.M * d.N / 4;
         int64_t nb = (total4 + 255) / 256;
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(256), 0, s,
@@ -4147,11 +4152,16 @@ struct TapsTile { int desc, tile, slabs; };
 }  // namespace mdm
 using namespace mdm;
 
-extern "C" int mdm_gemm(const mdm_gemm_desc* desc_host, void* stream) {
-    return gemm_launch(desc_host, pick_stream(stream));
-}
+extern "C" int mdm_gemm(const mdm_gemm_desc* desc_host, void* stream) { return gemm_launch(desc_host, pick_stream(stream)); }
 
 extern "C" const char* mdm_gemm_last_route(void) { return g_route >= 0 ? kRouteName[g_route] : "none"; }
+
+extern "C" const char* mdm_gemm_route_of(const mdm_gemm_desc* desc_host) {
+    Resolved r;
+    GemmRoute rt;
+    if (plan_route(desc_host, r, rt)) return "none";
+    return kRouteName[3 * rt + second_stage(r)];
+}
 
 extern "C" int mdm_gemm_route_names(const char** out, int cap) {
     int n = 0;
@@ -4169,12 +4179,7 @@ static int launch_pair(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int nb, h
     const int NPA = halo_pieces(BM, a.OH, a.OW);
     const int bytes = std::max(halo_lds_bytes<BM, NSB, BN, 3>(a), lin2_lds_bytes<LBM, LBN, LNS>(b));
     MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_pair: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
-    static int configured = 0;
-    if (configured < bytes) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = bytes;
-    }
+    if (int rc = lds_opt_in<&conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>>(bytes)) return rc;
     const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
     hipLaunchKernelGGL((conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
     return 0;
@@ -4185,50 +4190,74 @@ static int launch_pair_small(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int
     const int bytes = std::max(small_lds_bytes(a, BM, BN), lin2_lds_bytes<64, 64, 4>(b));
     MDM_REQUIRE(small_pieces(a, BM) <= 8 * NPW && bytes <= 160 * 1024, "conv_pair_small: tile does not fit (%d bytes)", bytes);
     MDM_REQUIRE(BM == 64 || (fused_gn_cpg(a) == 8 && a.N0 % 8 == 0), "conv_pair_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
-    static int configured = 0;
-    if (configured < bytes) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pair_small_kernel<NPW, BM, BN>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = bytes;
-    }
+    if (int rc = lds_opt_in<&conv_pair_small_kernel<NPW, BM, BN>>(bytes)) return rc;
     const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
     hipLaunchKernelGGL((conv_pair_small_kernel<NPW, BM, BN>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
     return 0;
 }
 
+static int plan_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, Resolved& ra, Resolved& rb) {
+    if (int rc = resolve(a_host, false, ra)) return rc;
+    if (int rc = resolve(b_host, false, rb)) return rc;
+    if (int rc = check_fused_gn(ra.d)) return rc;
+    return check_fused_gn(rb.d);
+}
+// One of the fused routes, or R_PAIR_TWO: `b` must be a conv_lin2 launch of its own with no second stage (no split reduction),
+// `a` a halo launch; the pairs below are the ones a unet6 step produces (4x4, 8x8, 16x16, 32x32 maps).  Anything else: two
+// launches, same results.  (No HIP call, no state: mdm_gemm_pair_route_of asks this alone.)
+static GemmRoute choose_pair_route(const Resolved& ra, const Resolved& rb) {
+    const mdm_gemm_desc &a = ra.d, &b = rb.d;
+    const int za = ra.zouter * a.splitk, zb = rb.zouter * b.splitk;
+    const bool b_plain = zb == 1 && !rb.tap_split && !(b.splitk > 1) && rb.tiles < (1ll << 20) && !b.gnb_x && !b.gnf_out;
+    if (!(b_plain && za == 1 && conv_family(a) && conv_family(b))) return R_PAIR_TWO;
+    const GemmRoute va = conv_variant(ra), vb = conv_variant(rb);
+    if (va == R_SMALL_4 && vb == R_LIN2_64) return R_PAIR_SMALL_4;
+    if (va == R_SMALL_5 && vb == R_LIN2_64) return R_PAIR_SMALL_5;
+    if (va == R_SMALL_3 && vb == R_LIN2_64) return R_PAIR_SMALL_3;
+    if (va == R_H64_2_32 && vb == R_LIN2_64) return R_PAIR_64_2;
+    if (va == R_H64_3_32 && vb == R_LIN2_64) return R_PAIR_64_3;
+    if (va == R_H128_3 && vb == R_LIN2_64x128) return R_PAIR_128_L64x128;
+    if (va == R_H128_3 && vb == R_LIN2_64) return R_PAIR_128_L64;
+    if (va == R_H256_6 && vb == R_LIN2_128) return R_PAIR_256_L128;
+    return R_PAIR_TWO;
+}
+static int launch_pair_route(GemmRoute rt, const Resolved& ra, const Resolved& rb, hipStream_t s) {
+    const mdm_gemm_desc &a = ra.d, &b = rb.d;
+    const int nb = (int)rb.tiles;            // workgroups of `b` on the tile shape resolve chose
+    switch (rt) {
+        case R_PAIR_SMALL_4: return launch_pair_small<4>(a, b, nb, s);
+        case R_PAIR_SMALL_5: return launch_pair_small<5>(a, b, nb, s);
+        case R_PAIR_SMALL_3: return launch_pair_small<3, 32, 16>(a, b, nb, s);
+        case R_PAIR_64_2: return launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>(a, b, nb, s);
+        case R_PAIR_64_3: return launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>(a, b, nb, s);
+        case R_PAIR_128_L64x128: return launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>(a, b, (int)((int64_t)cdiv(b.M, 64) * cdiv(b.N, 128)), s);
+        case R_PAIR_128_L64: return launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>(a, b, nb, s);
+        case R_PAIR_256_L128: return launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>(a, b, nb, s);
+        default: set_error("gemm_pair: route %d is not a fused pair", (int)rt); return -1;
+    }
+}
+
 extern "C" int mdm_gemm_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, void* stream) {
     hipStream_t s = pick_stream(stream);
     Resolved ra, rb;
-    if (int rc = resolve(a_host, false, ra)) return rc;
-    if (int rc = resolve(b_host, false, rb)) return rc;
-    const mdm_gemm_desc &a = ra.d, &b = rb.d;
-    if (int rc = check_fused_gn(a)) return rc;
-    if (int rc = check_fused_gn(b)) return rc;
-    const unsigned za = (unsigned)(ra.zouter * a.splitk), zb = (unsigned)(rb.zouter * b.splitk);
-    const ConvVar va = conv_variant(a, ra, za), vb = conv_variant(b, rb, zb);
-    // `b` must be a conv_lin2 launch of its own with no second stage (no split reduction), `a` a halo launch; the four pairs
-    // below are the ones a unet6 step produces (4x4, 8x8, 16x16, 32x32 maps).  Anything else: two launches, same results.
-    const bool b_plain = zb == 1 && !rb.tap_split && !(b.splitk > 1) && rb.tiles < (1ll << 20) && !b.gnb_x && !b.gnf_out;
-    int rc = kNotTaken;
+    if (int rc = plan_pair(a_host, b_host, ra, rb)) return rc;
     g_route = -1;
-    if (b_plain && za == 1) {
-        const int nb64 = (int)rb.tiles, nb64x128 = (int)((int64_t)cdiv(b.M, 64) * cdiv(b.N, 128));
-        if (va == CV_S64_4 && vb == CV_L64) rc = route(R_PAIR_SMALL_4) + launch_pair_small<4>(a, b, nb64, s);
-        else if (va == CV_S64_5 && vb == CV_L64) rc = route(R_PAIR_SMALL_5) + launch_pair_small<5>(a, b, nb64, s);
-        else if (va == CV_S32_3 && vb == CV_L64) rc = route(R_PAIR_SMALL_3) + launch_pair_small<3, 32, 16>(a, b, nb64, s);
-        else if (va == CV_H64_2_32 && vb == CV_L64) rc = route(R_PAIR_64_2) + launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
-        else if (va == CV_H64_3_32 && vb == CV_L64) rc = route(R_PAIR_64_3) + launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
-        else if (va == CV_H128_3 && vb == CV_L64x128) rc = route(R_PAIR_128_L64x128) + launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>(a, b, nb64x128, s);
-        else if (va == CV_H128_3 && vb == CV_L64) rc = route(R_PAIR_128_L64) + launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>(a, b, nb64, s);
-        else if (va == CV_H256_6 && vb == CV_L128) rc = route(R_PAIR_256_L128) + launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>(a, b, nb64, s);
-    }
-    if (rc == kNotTaken) {
-        rc = gemm_launch(a_host, s);
+    const GemmRoute rt = choose_pair_route(ra, rb);
+    if (rt == R_PAIR_TWO) {
+        int rc = gemm_launch(a_host, s);
         if (rc == 0) rc = gemm_launch(b_host, s);
-        route(R_PAIR_TWO);
+        route(R_PAIR_TWO);       // last: each gemm_launch recorded its own route
         return rc;
     }
-    if (rc) return rc;
+    route(rt);
+    if (int rc = launch_pair_route(rt, ra, rb, s)) return rc;
     return launch_status("gemm pair launch");
+}
+
+extern "C" const char* mdm_gemm_pair_route_of(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host) {
+    Resolved ra, rb;
+    if (plan_pair(a_host, b_host, ra, rb)) return "none";
+    return kRouteName[3 * choose_pair_route(ra, rb)];
 }
 
 extern "C" int mdm_gemm_can_fuse_gn_bwd(const mdm_gemm_desc* desc_host, int G) {
@@ -4501,12 +4530,8 @@ extern "C" int mdm_wgrad_group_launch(void* handle, void* stream) {
     const WgradGroup* g = reinterpret_cast<const WgradGroup*>(handle);
     hipStream_t s = pick_stream(stream);
     constexpr int bytes = 3 * (256 + 128) * 64 * 2;        // the largest of the three rings (256x128: 3 stages of 48 KiB)
-    static bool configured = false;
-    if (!configured) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_taps_group_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    }
-    configured = true;
+    if (int rc = lds_opt_in<&wgrad_group_kernel>(bytes)) return rc;
+    if (int rc = lds_opt_in<&wgrad_taps_group_kernel>(bytes)) return rc;
     route(g->n_taps_items > 0 ? R_WGROUP_TAPS : R_WGROUP);
     if (!g->reduces.empty()) route_stage(S_SPLITK);
     if (g->n_taps_items > 0) {
@@ -4699,11 +4724,7 @@ static int wgrad_split_plan(const mdm_gemm_desc& d, WgradSplitPlan& p) {
 template <int BT>
 static int launch_wgrad_split(const mdm_gemm_desc& d, const WgradSplitPlan& p, hipStream_t s) {
     constexpr int bytes = 2 * 2 * BT * 36 * 4;
-    static bool configured = false;
-    if (!configured) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_split_kernel<BT>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured = true;
-    }
+    if (int rc = lds_opt_in<&wgrad_split_kernel<BT>>(bytes)) return rc;
     hipLaunchKernelGGL((wgrad_split_kernel<BT>), dim3((unsigned)p.tiles, (unsigned)(d.KH * d.KW), (unsigned)p.splitk), dim3(256), bytes, s, d,
                        p.chunk);
     return 0;

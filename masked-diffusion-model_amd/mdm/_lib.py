@@ -52,6 +52,8 @@ _PROTOS = {
     "mdm_gemm_can_fuse_gn_bwd": ([C.POINTER(GemmDesc), i32], i32),
     "mdm_gemm_can_fuse_gn_fwd": ([C.POINTER(GemmDesc), i32], i32),
     "mdm_gemm_last_route": ([], C.c_char_p),
+    "mdm_gemm_route_of": ([C.POINTER(GemmDesc)], C.c_char_p),
+    "mdm_gemm_pair_route_of": ([C.POINTER(GemmDesc), C.POINTER(GemmDesc)], C.c_char_p),
     "mdm_gemm_route_names": ([C.POINTER(C.c_char_p), i32], i32),
     "mdm_groupnorm_fwd": ([i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, vp, vp], i32),
     "mdm_groupnorm_bwd": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
@@ -359,6 +361,18 @@ class WgradGroup:
 def last_route():
     """Kernel (and second stage) of the last mdm_gemm / mdm_gemm_pair / wgrad group launch on this thread (mdm_gemm_last_route)."""
     return load().mdm_gemm_last_route().decode()
+
+
+def route_of(**kw):
+    """What last_route() would name after gemm(**kw), without launching (mdm_gemm_route_of); "none" for a refused descriptor."""
+    kw.pop("_flops", None)
+    return load().mdm_gemm_route_of(C.byref(_desc(kw))).decode()
+
+
+def pair_route_of(kw_a, kw_b):
+    """What last_route() would name after gemm_pair(kw_a, kw_b), without launching (mdm_gemm_pair_route_of)."""
+    da, db = (_desc({k: v for k, v in kw.items() if k != "_flops"}) for kw in (kw_a, kw_b))
+    return load().mdm_gemm_pair_route_of(C.byref(da), C.byref(db)).decode()
 
 
 def wgrad_split_last_route():

@@ -1,0 +1,51 @@
+"""The kernel choice of mdm_gemm / mdm_gemm_pair, asked for without a GPU (mdm_gemm_route_of, mdm_gemm_pair_route_of).
+
+Every row of test_gemm_routes_gpu.CASES that goes through mdm_gemm or mdm_gemm_pair is built by the row's own builder on the CPU
+and the route the library would take is compared with the one the row names -- the names were recorded from launches on an
+MI355X.  The choice is host arithmetic on the descriptor: pointers only have to be non-null and are never dereferenced."""
+import pytest
+import torch
+
+import test_gemm_routes_gpu as R
+
+# Rows whose kernel is not chosen by mdm_gemm's dispatch, by id.
+OUTSIDE = {cid: "grouped weight gradient: mdm_wgrad_group_create schedules it, mdm_gemm's dispatch is not asked"
+           for cid in ("group_per_tap", "group_splitk", "group_taps", "group_taps_splitk")}
+
+
+@pytest.fixture
+def cpu_shadow(monkeypatch):
+    """mdm_split_shadow is a kernel; the choice only needs a second filter tensor of the same shape."""
+    monkeypatch.setattr(R, "_split_shadow", lambda w, dev: (torch.empty_like(w), torch.tensor([0, w.numel()], dtype=torch.int64)))
+
+
+def route_of(case):
+    from mdm import _lib
+    dev, g = torch.device("cpu"), torch.Generator().manual_seed(0)
+    if case.kind == "pair":
+        return _lib.pair_route_of(R.BUILD["fwd"](R.Prob(dev), case.p["a"], g), R.BUILD["fwd"](R.Prob(dev), case.p["b"], g))
+    return _lib.route_of(**R.BUILD[case.kind](R.Prob(dev), case.p, g))
+
+
+@pytest.mark.parametrize("case", [c for c in R.CASES if c.values[0].id not in OUTSIDE])
+def test_route_choice(case, cpu_shadow):
+    from mdm import _lib
+    before = _lib.last_route()
+    assert route_of(case) == case.route, case.id
+    assert _lib.last_route() == before, "asking for a route changed the record of the last launch"
+
+
+def test_only_the_grouped_rows_are_left_out():
+    kinds = {c.id: c.kind for c in R._case_list()}
+    assert set(OUTSIDE) == {cid for cid, k in kinds.items() if k != "pair" and k not in R.BUILD}
+    assert all(kinds[cid] == "group" for cid in OUTSIDE)
+
+
+def test_refused_descriptor_has_no_route():
+    from mdm import _lib
+    f = dict(dtype=R.BF, layout=0, M=64, N=64, K=64, A=16, lda=64, B=16, ldb=64, D0=16, ldd0=64, N0=64)
+    assert _lib.route_of(**f) == "ring<64>"
+    assert _lib.route_of(**dict(f, N=60)) == "none"          # N must be a multiple of 8
+    assert "N=60" in _lib.load().mdm_last_error().decode()
+    assert _lib.pair_route_of(dict(f, N=60), f) == "none"
+    assert _lib.pair_route_of(f, f) == "pair:two launches"

@@ -24,13 +24,6 @@ REL_BAR = {"bf16": 6.5e-3, "f32_bf16": 1e-6, "f32": 2e-6, "f32_split": 1.8e-5}
 
 # Routes no row reaches, with the reason.
 EXCLUDED = {
-    # a 256-pixel halo tile needs at least 41 one-KiB halo pieces (16x16 maps; 43 on 32x32, 50 on 64x64 = not eligible), so the
-    # "<= 4 pieces per wave" arm of these launches never runs
-    "halo<256,4,2,32,f32,split>": "no geometry gives a 256-pixel tile <= 32 halo pieces",
-    "halo<256,4,4,128,f32,split>": "no geometry gives a 256-pixel tile <= 32 halo pieces",
-    "halo<256,4,NSB,64,f32,split>": "no geometry gives a 256-pixel tile <= 32 halo pieces",
-    "halo<256,4,2,64,f32>": "no geometry gives a 256-pixel tile <= 32 halo pieces",
-    "halo<256,4,NSB,64>": "no geometry gives a 256-pixel tile <= 32 halo pieces",
     # conv_variant takes the 64-channel small-map tile only for a fused GroupNorm epilogue of 64 channels per group (gnb_/gnf_)
     "halo<64,2,3,64>": "only with a fused GroupNorm epilogue of 64-channel groups (values: the GroupNorm tests)",
     "halo<64,3,3,64>": "only with a fused GroupNorm epilogue of 64-channel groups (values: the GroupNorm tests)",
