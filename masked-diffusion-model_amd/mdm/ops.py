@@ -65,7 +65,7 @@ def conv_fwd(dt, g: ConvGeom, src0, src1, w, bias, out, rowvec=None, rv_ld=0, re
              f32_split=0):
     """out[N,OH,OW,Cout] = conv(concat(src0,src1), w[tap][Cout][Cin]) + bias + rowvec[n] + resid.
     Returns the descriptor.  `gnf` = dict(out, gamma, beta, stats, G, silu, eps): also the GroupNorm of the result in the
-    same launch (only where conv_fwd_can_fuse_gn says so); `fuse_gn_fwd(desc, ...)` sets it on a RECORDED call afterwards."""
+    same launch (only where conv_fwd_can_fuse_gn says so)."""
     return _lib.gemm(**conv_fwd_fields(dt, g, src0, src1, w, bias, out, rowvec, rv_ld, resid, out_f32, ws, gnf, w_split, f32_split))
 
 
@@ -98,15 +98,12 @@ def _gnf_fields(gnf):
                 gnf_silu=int(bool(gnf["silu"])), gnf_eps=float(gnf.get("eps", 1e-6)))
 
 
-def conv_fwd_can_fuse_gn(desc, G=32):
-    """True if the forward conv described by `desc` (as returned by conv_fwd) may carry the gnf_* epilogue."""
-    return bool(_lib.load().mdm_gemm_can_fuse_gn_fwd(_lib.C.byref(desc), int(G)))
-
-
-def fuse_gn_fwd(desc, gnf):
-    """Attach the GroupNorm-forward epilogue to an already RECORDED conv_fwd call (its descriptor is replayed by reference)."""
-    for k, v in _gnf_fields(gnf).items():
-        setattr(desc, k, v.data_ptr() if hasattr(v, "data_ptr") else v)
+def conv_fwd_can_fuse_gn(dt, g: ConvGeom, G=32):
+    """True if the forward conv of this geometry runs on whole-image tiles, so that `gnf` may be used (host arithmetic on the
+    descriptor's scalar fields: dummy non-null pointers, no launch)."""
+    f = conv_fwd_fields(dt, g, 16, 16 if g.C1 else None, 16, 16, 16)
+    f.pop("_flops")
+    return bool(_lib.load().mdm_gemm_can_fuse_gn_fwd(_lib.C.byref(_lib._desc(f)), int(G)))
 
 
 def conv_dgrad(dt, g: ConvGeom, dy, w, dst0, acc0, dst1=None, acc1=0):

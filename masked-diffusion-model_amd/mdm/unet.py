@@ -46,6 +46,7 @@ class Act:
         self.grad_written = False
         self.pending_add = None       # a gradient contribution (another activation's grad tensor) not yet folded into `grad`
         self.needs_grad = needs_grad
+        self.norm_spec = None         # the _Norm that produced this activation (UNet._norm), if one did
 
     @property
     def P(self):
@@ -65,6 +66,9 @@ class ParamStore:
         self.entries = OrderedDict()     # name -> SimpleNamespace(off, ishape, rshape, kind)
         self.size = 0
         self.P = self.G = self.Pb = None
+        self.PbT = self.tiles = None                     # bf16 stores: per-tap transposed shadow (allocate)
+        self.Ps = self.split_segs = None                 # fp32 stores: enable_split
+        self.PsT = self.split_t_segs = None              # fp32 stores: enable_split_t
 
     def declare(self, name, kind, rshape, ishape):
         assert name not in self.entries, name
@@ -80,7 +84,6 @@ class ParamStore:
         self.G = torch.zeros(self.size, device=device, dtype=torch.float32)
         self.Pb = torch.zeros(self.size, device=device, dtype=torch.bfloat16) if dtype == BF16 else None
         # second bf16 shadow with every conv filter transposed per tap ([tap][Cin][Cout]) for the data gradient
-        self.PbT = None
         if dtype == BF16:
             self.PbT = torch.zeros(self.size, device=device, dtype=torch.bfloat16)
             rows = []
@@ -117,7 +120,7 @@ class ParamStore:
     # -- fp32 stores: the filters once more as bf16 hi / lo pairs (mdm_gemm_desc.B_split, conv_halo_body<..., SPLIT>)
     def enable_split(self):
         """Allocate the split shadow `Ps` (same offsets as P) for every conv filter whose rows are whole 32-channel blocks."""
-        if getattr(self, "Ps", None) is not None:
+        if self.Ps is not None:
             return
         assert self.dtype == F32, "the split shadow belongs to an fp32 store"
         segs = [(e.off, e.n) for e in self.entries.values() if e.kind in ("conv", "convlin") and e.ishape[2] % 32 == 0]
@@ -126,13 +129,13 @@ class ParamStore:
         self.emit_split_shadow()
 
     def emit_split_shadow(self):
-        if getattr(self, "Ps", None) is not None:
+        if self.Ps is not None:
             _lib.call("mdm_split_shadow", _lib.ptr(self.P), _lib.ptr(self.Ps), _lib.ptr(self.split_segs),
                       int(self.split_segs.shape[0]), _lib.stream())
 
     def w_split(self, name):
         e = self.entries[name]
-        if getattr(self, "Ps", None) is None or e.kind not in ("conv", "convlin") or e.ishape[2] % 32:
+        if self.Ps is None or e.kind not in ("conv", "convlin") or e.ishape[2] % 32:
             return None
         return self.Ps[e.off:e.off + e.n].view(e.ishape)
 
@@ -140,7 +143,7 @@ class ParamStore:
     def enable_split_t(self):
         """Allocate `PsT` (same offsets as P) for every conv filter whose Cout and Cin are whole 32-channel blocks: the data
         gradient of such a layer is a forward convolution of dY through it (ops.conv_dgrad_split_fields)."""
-        if getattr(self, "PsT", None) is not None:
+        if self.PsT is not None:
             return
         assert self.dtype == F32, "the split shadow belongs to an fp32 store"
         segs = [(e.off,) + tuple(e.ishape) for e in self.entries.values()
@@ -150,13 +153,13 @@ class ParamStore:
         self.emit_split_shadow_t()
 
     def emit_split_shadow_t(self):
-        if getattr(self, "PsT", None) is not None:
+        if self.PsT is not None:
             _lib.call("mdm_split_shadow_t", _lib.ptr(self.P), _lib.ptr(self.PsT), _lib.ptr(self.split_t_segs),
                       int(self.split_t_segs.shape[0]), _lib.stream())
 
     def ws_t(self, name):       # [tap][Cin][Cout] view of PsT (flipped taps), or None
         e = self.entries[name]
-        if getattr(self, "PsT", None) is None or e.kind not in ("conv", "convlin") or e.ishape[1] % 32 or e.ishape[2] % 32:
+        if self.PsT is None or e.kind not in ("conv", "convlin") or e.ishape[1] % 32 or e.ishape[2] % 32:
             return None
         taps, co, ci = e.ishape
         return self.PsT[e.off:e.off + e.n].view(taps, ci, co)
@@ -239,10 +242,33 @@ class ParamStore:
 
 
 # --------------------------------------------------------------------------- #
+class _ResBlock:
+    """The members of one residual block (`skip`: its 1x1 projection, or None), shared by them as `spec.block`: which conv pairs
+    with which, and whose sums ride on which norm, is read from this one record.  `paired`: the block may use launch pairs."""
+
+    def __init__(self, skip, conv1, norm2, conv2, paired):
+        self.skip, self.conv1, self.norm2, self.conv2, self.paired = skip, conv1, norm2, conv2, paired
+        for s in (skip, conv1, norm2, conv2):
+            if s is not None:
+                s.block = self
+
+
 class _Conv:
-    def __init__(self, net, name, geom, src0, src1, out, fc_slot=None, resid=None):
+    def __init__(self, net, name, geom, src0, src1, out, rshape, fc_slot=None, resid=None):
         self.net, self.name, self.g, self.src0, self.src1, self.out = net, name, geom, src0, src1, out
-        self.fc_slot, self.resid = fc_slot, resid
+        self.rshape, self.fc_slot, self.resid = rshape, fc_slot, resid
+        self.block = self.param_lo = None
+        # ---- decisions, fixed by UNet._plan() before anything is recorded; fwd() / bwd() only read them
+        self.fwd_in_pair = False    # a skip projection: launched inside its block's conv1 pair
+        self.fwd_mate = None        # conv1: the skip projection that shares its launch
+        self.gn_fwd = None          # the _Norm right after this conv whose forward is this launch's epilogue
+        self.sums = None            # bias / time-embedding sums: "colsum" | "wgrad" (ride on the weight gradient) | "norm" (block.norm2 emits them)
+        self.wgrad = None           # "grouped" | "split" (mdm_conv_wgrad_split) | "single"
+        self.dgrad = None           # "t" (transposed bf16 shadow) | "split" | "exact"; None: the input needs no gradient
+        self.grad_exact = {}        # grad_products="split": {"wgrad" / "dgrad": "exact:<reason>"} of what stays exact fp32
+        self.gn_bwd = None          # the _Norm that produced this conv's only input and whose backward is the data gradient's epilogue
+        self.bwd_mate = None        # conv2: the skip projection whose whole backward runs here, data gradients in one launch
+        self.bwd_in_pair = False    # that skip projection
 
     def declare(self, st):
         g = self.g
@@ -255,23 +281,23 @@ class _Conv:
         rv, ld = (None, 0)
         if self.fc_slot is not None:
             rv, ld = n.T_all[:, self.fc_slot:], (0 if n.uniform_t else n.fc_total)     # uniform_t: ONE projection row for every image
+        # 4x4 / 8x8 maps: this conv runs on whole-image tiles -> it normalises its own output (gnf_* epilogue; no GroupNorm launch)
         return ops.conv_fwd_fields(n.dt, g, self.src0.data, self.src1.data if self.src1 else None, st.w(self.name + ".weight"),
                                    st.f(self.name + ".bias"), self.out.data, rowvec=rv, rv_ld=ld,
                                    resid=self.resid.data if self.resid else None, ws=n.splitk_ws,
+                                   gnf=self.gn_fwd.fwd_epilogue() if self.gn_fwd is not None else None,
                                    w_split=st.w_split(self.name + ".weight") if n.split_products else None,
                                    f32_split=int(n.split_products))
 
     def fwd(self):
-        n = self.net
         # A ResidualBlock's skip projection (1x1) only needs the block input, like conv1 only needs norm1's output: the two
         # run as ONE launch (mdm_gemm_pair) when conv1 is reached; conv2 consumes the projection afterwards.
-        if n.pair_convs and getattr(self, "pair_host", None) is not None:
-            return                                      # a skip projection: launched together with its block's conv1
-        mate = getattr(self, "pair_skip", None) if n.pair_convs else None
-        if mate is not None:
-            self.fwd_desc, mate.fwd_desc = ops.conv_fwd_pair(self._fwd_fields(), mate._fwd_fields())
+        if self.fwd_in_pair:
+            return
+        if self.fwd_mate is not None:
+            ops.conv_fwd_pair(self._fwd_fields(), self.fwd_mate._fwd_fields())
         else:
-            self.fwd_desc = _lib.gemm(**self._fwd_fields())
+            _lib.gemm(**self._fwd_fields())
 
     def bwd(self, pair_a=None):
         """pair_a: descriptor fields of another conv's data gradient (the block's conv2) to launch TOGETHER with this one's.
@@ -283,7 +309,7 @@ class _Conv:
         convolution: not whole 32-channel blocks); layers whose Cin is not a whole 64-channel tile (data gradient only); and
         everything that is not a convolution -- attention, GroupNorm, the time-embedding path, the loss and the optimizer."""
         n, st, g = self.net, self.net.store, self.g
-        if getattr(self, "bwd_done", False):            # a skip projection whose backward ran next to conv2's
+        if self.bwd_in_pair and pair_a is None:         # a skip projection: its backward runs next to conv2's (bwd_mate)
             return
         dy = n.grad_for_read(self.out)
         r = self.resid
@@ -291,15 +317,15 @@ class _Conv:
         if self.fc_slot is not None:
             per, ld = n.dT_all[:, self.fc_slot:], n.fc_total
         s0, s1 = self.src0, self.src1
-        fuse_bias = n.dt == BF16 and self.fc_slot is None     # bias sums ride along in the weight-gradient kernel
-        if not fuse_bias and not getattr(self, "sums_by_norm", False):
+        fuse_bias = self.sums == "wgrad"            # bias sums ride along in the weight-gradient kernel
+        if self.sums == "colsum":
             ops.colsum(n.dt, dy, g.N, g.OH * g.OW, g.Cout, per_img=per, ld=ld, acc_img=0, dbias=st.g(self.name + ".bias"))
         # Weight gradient.  It only READS dy and the layer input, and both stay in memory: on the bf16 path it is not
         # launched here but collected into the current GROUP (UNet._flush_wgrads: one launch for a whole stretch of the
         # backward, overwriting G -- no read of the zero-filled gradient).  dy must then stay untouched until the flush.
         wf = ops.wgrad_fields(n.dt, g, dy, s0.data, s1.data if s1 else None, st.g(self.name + ".weight"),
                               dbias=st.g(self.name + ".bias") if fuse_bias else None)
-        grouped = n.dt == BF16 and n.group_wgrads and _lib.wgrad_group_accepts(**wf)
+        grouped = self.wgrad == "grouped"
         if grouped:
             wf["acc0"] = 0
             n.overwritten.add(self.name + ".weight")     # this slot of G is stored, not accumulated: no zeroing needed
@@ -308,14 +334,14 @@ class _Conv:
                 wf["ws"] = n.wgrad_slab(sk * g.taps * g.Cout * g.Cin)
                 wf["ws_bytes"] = wf["ws"].numel() * 4
             n.pending_wgrads.append((self, wf))
-        elif n.grad_products == "split" and ops.split_grad_reason(g, "wgrad") is None:
+        elif self.wgrad == "split":
             ops.conv_wgrad_split(g, dy, s0.data, s1.data if s1 else None, st.g(self.name + ".weight"), ws=n.splitk_ws)
             self._note_route("wgrad", _lib.wgrad_split_last_route)
         else:
             ops.conv_wgrad(n.dt, g, dy, s0.data, s1.data if s1 else None, st.g(self.name + ".weight"), ws=n.splitk_ws,
                            dbias=st.g(self.name + ".bias") if fuse_bias else None)
-            if n.grad_products == "split":
-                n.grad_routes.setdefault(self.name, {})["wgrad"] = "exact:" + ops.split_grad_reason(g, "wgrad")
+        if self.grad_exact:
+            n.grad_routes.setdefault(self.name, {}).update(self.grad_exact)
         if r is not None and r.needs_grad:       # y = conv(..) + resid  (unet6.py:333, 362): d(resid) += dy
             if r.grad_written and not (grouped and r.pending_add is None):
                 ops.add_(n.dt, r.grad, dy)
@@ -323,14 +349,14 @@ class _Conv:
                 r.pending_add = dy               # folded in by the next writer of r.grad (dst = dy + dx): dy stays intact
             else:
                 r.grad, r.grad_written = dy, True      # alias: dy is dead after this op, later ops += into it
-        if not s0.needs_grad:
+        if self.dgrad is None:
             assert pair_a is None
             return
         # bf16: the filters come from the per-tap transposed shadow so both operands are k-contiguous
-        if n.dt == BF16:
+        if self.dgrad == "t":
             wmat = st.wT(self.name + ".weight")
             dgrad = lambda *a: ops.conv_dgrad_t(*a, ws=n.splitk_ws)     # small maps split the taps over the grid
-        elif n.grad_products == "split" and ops.split_grad_reason(g, "dgrad") is None:
+        elif self.dgrad == "split":
             # a forward convolution of dY through the flipped, transposed split shadow, on the split forward routes
             wmat = st.ws_t(self.name + ".weight")
 
@@ -339,51 +365,39 @@ class _Conv:
                 self._note_route("dgrad", _lib.last_route)
         else:
             dgrad, wmat = ops.conv_dgrad, st.w(self.name + ".weight")
-            if n.grad_products == "split":
-                n.grad_routes.setdefault(self.name, {})["dgrad"] = "exact:" + ops.split_grad_reason(g, "dgrad")
         # conv2 of a ResidualBlock with a skip projection: the projection's whole backward runs HERE, its data gradient in
         # the same launch as this one's (both read this block's dY; they write different tensors)
-        mate = getattr(self, "pair_skip_bwd", None) if (n.pair_convs and n.dt == BF16 and not g.ups) else None
+        mate = self.bwd_mate
 
         def emit(fields):
             if pair_a is not None:
                 _lib.gemm_pair(pair_a, fields)
             elif mate is not None:
                 mate.bwd(pair_a=fields)
-                mate.bwd_done = True
             else:
                 _lib.gemm(**fields)
-        nm = getattr(s0, "norm_spec", None)          # the GroupNorm that produced this conv's input (if any)
-        if (n.dt == BF16 and nm is not None and nm.src1 is None and s1 is None and not g.ups
-                and ops.conv_dgrad_t_can_fuse_gn_bwd(n.dt, g)):
+        nm = self.gn_bwd
+        if nm is not None:
             # 4x4 / 8x8 maps: the data gradient runs on whole-image tiles, so the GroupNorm backward is its epilogue --
-            # d(z) never goes to memory and the GroupNorm launch disappears (_Norm.bwd sees bwd_fused)
+            # d(z) never goes to memory and the GroupNorm launch disappears (nm.bwd_fused)
             x = nm.src0
             gx, ax, addx = n.grad_for_write(x, want_add=2)
-            sums = {}
-            prod = getattr(nm, "producer", None)     # conv1 of a ResidualBlock: this dx is its complete dY
-            if prod is not None and ax == 0 and addx is None:
-                sums = dict(sum_img=n.dT_all[:, prod.fc_slot:], sum_ld=n.fc_total, sum_all=st.g(prod.name + ".bias"))
-                prod.sums_by_norm = True
             emit(ops.conv_dgrad_t_fields(n.dt, g, dy, wmat, gx, ax, ws=n.splitk_ws,
                                          gnb=dict(x=x.data, stats=nm.stats, gamma=st.f(nm.name + ".weight"), beta=st.f(nm.name + ".bias"),
                                                   dgamma=st.g(nm.name + ".weight"), dbeta=st.g(nm.name + ".bias"), G=32, silu=nm.silu,
-                                                  add=addx, **sums)))
-            nm.bwd_fused = True
+                                                  add=addx, **nm.sums_fields(ax, addx))))
         elif g.ups:
             tmp = n.scratch(g.N * g.VH * g.VW * g.Cin)
             dgrad(n.dt, g, dy, wmat, tmp, 0)
             g0, a0, _ = n.grad_for_write(s0)
             ops.sumpool2(n.dt, tmp, g0, a0, g.N, g.IH, g.IW, g.Cin)
-        elif n.dt == BF16:
-            g0, a0, _ = n.grad_for_write(s0)
-            g1, a1, _ = n.grad_for_write(s1) if s1 is not None else (None, 0, None)
-            emit(ops.conv_dgrad_t_fields(n.dt, g, dy, wmat, g0, a0, g1, a1, ws=n.splitk_ws))
         else:
             g0, a0, _ = n.grad_for_write(s0)
             g1, a1, _ = n.grad_for_write(s1) if s1 is not None else (None, 0, None)
-            dgrad(n.dt, g, dy, wmat, g0, a0, g1, a1)
-
+            if self.dgrad == "t":
+                emit(ops.conv_dgrad_t_fields(n.dt, g, dy, wmat, g0, a0, g1, a1, ws=n.splitk_ws))
+            else:
+                dgrad(n.dt, g, dy, wmat, g0, a0, g1, a1)
 
     def _note_route(self, which, route_fn):
         """Record, each time the plan runs, the route the split launch just issued took (UNet.grad_products_table).  A split data
@@ -402,25 +416,40 @@ class _Conv:
 class _Norm:
     def __init__(self, net, name, src0, src1, out, silu, eps=1e-6):
         self.net, self.name, self.src0, self.src1, self.out, self.silu, self.eps = net, name, src0, src1, out, silu, eps
+        self.block = self.param_lo = self.stats = None
+        # ---- decisions (UNet._plan)
+        self.fwd_fused = False      # the conv right before it normalises its own output (that conv's gn_fwd)
+        self.bwd_fused = False      # its backward is the epilogue of its consumers' data gradients (their gn_bwd)
+        self.sums_for = None        # norm2 of a ResidualBlock: conv1, whose bias / time-embedding sums this backward also emits
 
     def declare(self, st):
         c = self.out.C
         st.declare(self.name + ".weight", "vec", (c,), (c,))
         st.declare(self.name + ".bias", "vec", (c,), (c,))
 
+    def fwd_epilogue(self):
+        """This GroupNorm as the `gnf` epilogue of the conv before it (fwd_fused).  Called while that conv is recorded: `stats` is
+        allocated there, which is where fwd() would have allocated it (a conv's fwd allocates nothing else)."""
+        st = self.net.store
+        self.stats = self.net.alloc((self.src0.N, 32, 2), torch.float32)
+        return dict(out=self.out.data, gamma=st.f(self.name + ".weight"), beta=st.f(self.name + ".bias"), stats=self.stats, G=32,
+                    silu=self.silu, eps=self.eps)
+
+    def sums_fields(self, acc, add):
+        """sum_* arguments of this norm's backward (own launch or epilogue): its dx is conv1's complete dY -- conv1's output has no
+        other consumer and is nobody's residual (UNet._plan checks), so it is written, not accumulated, and nothing is pending."""
+        n, prod = self.net, self.sums_for
+        if prod is None:
+            return {}
+        assert acc == 0 and add is None, self.name
+        return dict(sum_img=n.dT_all[:, prod.fc_slot:], sum_ld=n.fc_total, sum_all=n.store.g(prod.name + ".bias"))
+
     def fwd(self):
         n, st = self.net, self.net.store
         s0, s1 = self.src0, self.src1
-        self.stats = n.alloc((s0.N, 32, 2), torch.float32)
-        # 4x4 / 8x8 maps: the conv that has just produced s0 ran on whole-image tiles -> it normalises its own output
-        # (its recorded descriptor gets the gnf_* epilogue; no GroupNorm launch)
-        k = n.specs.index(self)
-        prev = n.specs[k - 1] if k > 0 else None
-        if (n.dt == BF16 and _lib._recording is not None and s1 is None and isinstance(prev, _Conv)
-                and prev.out is s0 and getattr(prev, "fwd_desc", None) is not None and ops.conv_fwd_can_fuse_gn(prev.fwd_desc)):
-            ops.fuse_gn_fwd(prev.fwd_desc, dict(out=self.out.data, gamma=st.f(self.name + ".weight"), beta=st.f(self.name + ".bias"),
-                                                stats=self.stats, G=32, silu=self.silu, eps=self.eps))
+        if self.fwd_fused:
             return
+        self.stats = n.alloc((s0.N, 32, 2), torch.float32)
         ops.groupnorm_fwd(n.dt, s0.data, s0.C, s1.data if s1 else None, s1.C if s1 else 0, s0.N, s0.P,
                           st.f(self.name + ".weight"), st.f(self.name + ".bias"), self.silu, self.out.data, self.stats, n.gn_ws,
                           eps=self.eps)
@@ -428,27 +457,24 @@ class _Norm:
     def bwd(self):
         n, st = self.net, self.net.store
         s0, s1 = self.src0, self.src1
-        if getattr(self, "bwd_fused", False):       # done in the epilogue of the consuming conv's data gradient
+        if self.bwd_fused:
             return
         dyo = n.grad_for_read(self.out)
         g0, a0, add0 = n.grad_for_write(s0, want_add=2)
         g1, a1, add1 = n.grad_for_write(s1, want_add=True) if s1 is not None else (None, 0, None)
-        sums = {}
-        prod = getattr(self, "producer", None)      # conv1 of a ResidualBlock: this dx is its complete dY
-        if prod is not None and a0 == 0 and add0 is None and s1 is None:
-            sums = dict(sum_img=n.dT_all[:, prod.fc_slot:], sum_ld=n.fc_total, sum_all=st.g(prod.name + ".bias"))
-            prod.sums_by_norm = True
         ops.groupnorm_bwd(n.dt, s0.data, s0.C, s1.data if s1 else None, s1.C if s1 else 0, s0.N, s0.P,
                           st.f(self.name + ".weight"), st.f(self.name + ".bias"), self.silu, dyo, self.stats,
                           g0, a0, g1, a1, st.g(self.name + ".weight"), st.g(self.name + ".bias"), n.gn_ws,
-                          add0=add0, add1=add1, **sums)
+                          add0=add0, add1=add1, **self.sums_fields(a0, add0))
 
 
 class _AttnCore:
     """softmax(q k^T / sqrt(C)) v over L = H*W tokens, one head (unet6.py:316-324)."""
 
     def __init__(self, net, qkv, out):
-        self.net, self.qkv, self.out = net, qkv, out
+        self.net, self.qkv, self.out, self.name = net, qkv, out, None
+        self.param_lo = self.lse = self.S = self.delta = None
+        self.mode = None            # "fused" | "f32_small" (one exact-fp32 forward launch) | "unfused"   (UNet._plan)
 
     def declare(self, st):
         pass
@@ -456,15 +482,14 @@ class _AttnCore:
     def fwd(self):
         n, q, o = self.net, self.qkv, self.out
         N, L, C = q.N, q.P, o.C
-        self.fused = ops.attn_supported(n.dt, L, C)
-        if self.fused:               # one kernel, the scores never reach memory (csrc/attn.hip)
+        if self.mode == "fused":     # one kernel, the scores never reach memory (csrc/attn.hip)
             self.lse = n.alloc((N, L), torch.float32)
             ops.attn_fwd(n.dt, q.data, o.data, self.lse, N, L, C, 1.0 / math.sqrt(C))
             return
         self.S = n.alloc((N, L, L), n.tdtype)
         d = q.data.view(N, L, 3 * C)
         sc = 1.0 / math.sqrt(C)
-        if n.dt == F32 and ops.attn_f32_small_supported(L, C):     # one exact-fp32 launch; S = the probabilities, as below
+        if self.mode == "f32_small":                               # one exact-fp32 launch; S = the probabilities, as below
             ops.attn_f32_small_fwd(q.data, o.data, self.S, N, L, C, sc)
             return
         ops.matmul(n.dt, 0, L, L, C, d, 3 * C, d[:, :, C:], 3 * C, self.S, L, batch=N, sA=L * 3 * C, sB=L * 3 * C, sD=L * L, alpha=sc)
@@ -477,7 +502,7 @@ class _AttnCore:
         do = n.grad_for_read(o)
         dqkv, acc, _ = n.grad_for_write(q)
         assert acc == 0
-        if self.fused:
+        if self.mode == "fused":
             self.delta = n.alloc((N, L), torch.float32)
             ops.attn_bwd(n.dt, q.data, o.data, do, self.lse, self.delta, dqkv, N, L, C, 1.0 / math.sqrt(C))
             return
@@ -501,6 +526,9 @@ class _Temb:
         self.net, self.hid, self.temb, self.fc_total = net, hid, temb, fc_total
         self.l1, self.l2 = names
         self.variant = variant          # None: unet6.py:18-34; (flip_sin_to_cos, freq_shift): diffusers' Timesteps
+        self.name = self.param_lo = None
+        self.e = self.h1 = self.a1 = self.tm = self.st_ = None
+        self.skinny = None              # the dedicated small-batch kernels, or the general contraction   (UNet._plan: _skinny())
 
     def declare(self, st):
         st.declare(self.l1 + ".weight", "lin", (self.temb, self.hid), (self.temb, self.hid))
@@ -524,7 +552,7 @@ class _Temb:
         N, hid, te, ft = self._rows(), self.hid, self.temb, self.fc_total
         f = lambda *s: n.alloc(s, torch.float32)
         self.e, self.h1, self.a1, self.tm, self.st_ = f(N, hid), f(N, te), f(N, te), f(N, te), f(N, te)
-        if self._skinny():      # 3 launches: embedding + Linear + SiLU, Linear + SiLU, the 22 projections
+        if self.skinny:         # 3 launches: embedding + Linear + SiLU, Linear + SiLU, the 22 projections
             ops.skinny_linear_fwd(None, st.f(self.l1 + ".weight"), st.f(self.l1 + ".bias"), N, te, hid, self.h1, act_out=self.a1,
                                   t=n.t_in, variant=self.variant, emb_out=self.e)
             ops.skinny_linear_fwd(self.a1, st.f(self.l2 + ".weight"), st.f(self.l2 + ".bias"), N, te, te, self.tm, act_out=self.st_)
@@ -543,7 +571,7 @@ class _Temb:
         N, hid, te, ft = n.N, self.hid, self.temb, self.fc_total
         f = lambda *s: n.alloc(s, torch.float32)
         d_st, d_tm, d_a1, d_h1 = f(N, te), f(N, te), f(N, te), f(N, te)
-        if self._skinny():      # 6 launches: bias gradients ride on the weight gradients, silu' on the data gradients
+        if self.skinny:         # 6 launches: bias gradients ride on the weight gradients, silu' on the data gradients
             splits = max(s_ for s_ in range(1, 17) if (ft // 64) % s_ == 0)
             slabs = f(splits, N, te)
             # single writers of their weight-gradient slots: stored (acc=0), so those slots need no zeroing either
@@ -587,33 +615,15 @@ class UNet:
         # uniform_t: the whole batch shares ONE timestep (the reverse sampler: sampler.py:137-145 passes a constant vector) -- the
         # time-embedding MLP and its 22 projections then run on one row and every image reads projection row 0.  Forward-only.
         self.uniform_t = bool(uniform_t)
-        if _dry:       # shape/parameter bookkeeping only (no device, no kernels): see `param_table`
-            self.cfg, self.N, self.H, self.W, self.dt = dict(cfg), N, H, W, dtype
-            self.store = ParamStore()
-            self._build_specs()
-            self._declare_params()
-            self._set_param_marks()
-            return
-        if not torch.cuda.is_available():
-            raise RuntimeError("mdm.UNet needs a GPU and libmdm_hip.so; there is no CPU fallback")
-        _lib.load()
         self.cfg = dict(cfg)
         self.N, self.H, self.W = N, H, W
         self.dt = dtype
-        self.tdtype = _lib.torch_dtype(dtype)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.training = True
-        self._bufs = []
-        self._scratch = None
-        self._scratch_n = 0
-        self.use_graph = use_graph
         self.group_wgrads = group_wgrads            # weight gradients of the bf16 path run as grouped launches
         self.pair_convs = dtype == BF16 and pair_convs   # skip projections share a launch with conv1 / conv2's data gradient
         # fp32 storage with the FORWARD 3x3 convolutions' products on the bf16 matrix pipe as hi / lo pairs (~2^-16 per product
         # instead of 2^-24; mdm_gemm_desc.B_split).  "exact" (default) is the parity path; "split" is for the reverse sampler.
         assert f32_products in ("exact", "split") and (f32_products == "exact" or dtype == F32), f32_products
         self.split_products = f32_products == "split"
-        self.grad_routes = {}               # conv name -> {"dgrad": route, "wgrad": route} (grad_products_table)
         if wgrad_group_bytes is None:
             # A group is one launch AND one gradient bucket (mdm/dist.py).  Under data parallelism ~32 MB groups let the exchange of one
             # bucket run under the backward of the next; a single process has nothing to exchange, and there one group over the whole
@@ -621,6 +631,24 @@ class UNet:
             import torch.distributed as dist
             wgrad_group_bytes = (32 << 20) if (dist.is_available() and dist.is_initialized()) else (1 << 40)
         self.wgrad_group_bytes = wgrad_group_bytes  # a group is flushed once it covers this many bytes of fp32 gradient
+        self._uniform_twin, self._batch_plans, self._sampling_plans = None, {}, {}
+        if _dry:       # shape/parameter bookkeeping only (no device, no kernels): see `param_table`.  `_plan()` runs on request: it
+            self.store = ParamStore()       # needs the library (host predicates only), the parameter table does not
+            self._build_specs()
+            self._declare_params()
+            self._set_param_marks()
+            return
+        if not torch.cuda.is_available():
+            raise RuntimeError("mdm.UNet needs a GPU and libmdm_hip.so; there is no CPU fallback")
+        _lib.load()
+        self.tdtype = _lib.torch_dtype(dtype)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.training = True
+        self._bufs = []
+        self._scratch = None
+        self._scratch_n = 0
+        self.use_graph = use_graph
+        self.grad_routes = {}               # conv name -> {"dgrad": route, "wgrad": route} (grad_products_table)
         self.pending_wgrads = []
         self.wgrad_groups = []
         shared = store is not None
@@ -636,6 +664,7 @@ class UNet:
         if self.grad_products == "split":
             self.store.enable_split_t()
         self._set_param_marks()
+        self._plan()
         self._materialize()
         if not shared:
             if params is None:
@@ -660,16 +689,21 @@ class UNet:
         """{reference key: reference shape} in flat-buffer order, computed on the host only."""
         return UNet(cfg, 1, H, W, _dry=True).reference_shapes()
 
+    def _twin(self, N, **overrides):
+        """Another launch plan of this architecture: same weights (store), dtype, products and timestep mode unless overridden.
+        NOT inherited, here as before: group_wgrads, pair_convs and wgrad_group_bytes -- a twin always gets their defaults."""
+        kw = dict(dtype=self.dt, device=self.device, store=self.store, use_graph=self.use_graph,
+                  f32_products="split" if self.split_products else "exact", uniform_t=self.uniform_t, grad_products=self.grad_products)
+        kw.update(overrides)
+        return type(self)(self.cfg, N, self.H, self.W, **kw)
+
     def with_batch(self, N):
         """A second launch plan over the SAME weights for another batch size (e.g. sample_num)."""
         if N == self.N:
             return self
-        plans = self.__dict__.setdefault("_batch_plans", {})
-        if N not in plans:
-            plans[N] = type(self)(self.cfg, N, self.H, self.W, dtype=self.dt, device=self.device, store=self.store, use_graph=self.use_graph,
-                                  f32_products="split" if self.split_products else "exact", uniform_t=self.uniform_t,
-                                  grad_products=self.grad_products)
-        return plans[N]
+        if N not in self._batch_plans:
+            self._batch_plans[N] = self._twin(N)
+        return self._batch_plans[N]
 
     def with_uniform_t(self):
         """The forward-only twin of this plan for a timestep shared by the whole batch (same weights, batch, dtype, products): what
@@ -677,10 +711,8 @@ class UNet:
         at sample_num = 100)."""
         if self.uniform_t:
             return self
-        if getattr(self, "_uniform_twin", None) is None:
-            self._uniform_twin = type(self)(self.cfg, self.N, self.H, self.W, dtype=self.dt, device=self.device, store=self.store,
-                                            use_graph=self.use_graph, f32_products="split" if self.split_products else "exact", uniform_t=True,
-                                            grad_products=self.grad_products)
+        if self._uniform_twin is None:
+            self._uniform_twin = self._twin(self.N, uniform_t=True)
         self._uniform_twin.training = self.training
         return self._uniform_twin
 
@@ -699,16 +731,16 @@ class UNet:
                 net.store.emit_split_shadow()
             return net
         products = "split" if precision == "f32_split" else "exact"
-        plans = self.__dict__.setdefault("_sampling_plans", {})
+        plans = self._sampling_plans
         key = (N, precision)
         if key not in plans:
+            kw = dict(dtype=F32, f32_products=products, uniform_t=False, grad_products="exact")
             if self.dt == F32:
-                plans[key] = type(self)(self.cfg, N, self.H, self.W, dtype=F32, device=self.device, store=self.store, use_graph=self.use_graph,
-                                  f32_products=products)
+                plans[key] = self._twin(N, **kw)
             else:
                 twin = next((v for (n2, p2), v in plans.items() if v.store is not self.store), None)
-                plans[key] = type(self)(self.cfg, N, self.H, self.W, dtype=F32, device=self.device, use_graph=self.use_graph, f32_products=products,
-                                  store=twin.store if twin is not None else None, params=None if twin is not None else self.state_dict())
+                plans[key] = self._twin(N, store=twin.store if twin is not None else None,
+                                        params=None if twin is not None else self.state_dict(), **kw)
                 if products == "split":
                     plans[key].store.enable_split()
         net = plans[key]
@@ -730,8 +762,47 @@ class UNet:
         self.acts.append(a)
         return a
 
+    # What a subclass with another assembly (UNet2D) changes about the shared builders below:
+    down_pads = (0, 0, 1, 1)        # (top, left, bottom, right) of a stride-2 3x3 convolution: SamePad2d pads bottom / right only
+    norm_eps = 1e-6
+    res_names = ("skip", "fc")      # member names of a residual block's 1x1 projection and time-embedding projection
+    pair_blocks = True              # residual blocks may use launch pairs (_ResBlock.paired)
+
+    def _begin_specs(self, cin, cout):
+        self.cin, self.cout, self.cin_p, self.cout_p = cin, cout, _pad8(cin), _pad8(cout)
+        self.acts, self.specs, self.blocks, self.fc_slots = [], [], [], OrderedDict()
+        self.fc_total = 0
+
+    def _conv(self, name, src0, src1, Cout, k=3, stride=1, ups=0, fc=None, resid=None, rshape=None):
+        pads = (1, 1, 1, 1) if k == 3 and stride == 1 else self.down_pads if k == 3 else (0, 0, 0, 0)
+        g = ops.ConvGeom(N=self.N, IH=src0.H, IW=src0.W, C0=src0.C, C1=src1.C if src1 else 0, Cout=Cout, KH=k, KW=k, stride=stride,
+                         pad_t=pads[0], pad_l=pads[1], pad_b=pads[2], pad_r=pads[3], ups=ups)
+        out = self._act(name, g.OH, g.OW, Cout)
+        self.specs.append(_Conv(self, name, g, src0, src1, out, rshape or (Cout, g.Cin, k, k), fc_slot=fc, resid=resid))
+        return out
+
+    def _norm(self, name, src0, src1, silu):
+        out = self._act(name, src0.H, src0.W, src0.C + (src1.C if src1 else 0))
+        out.norm_spec = _Norm(self, name, src0, src1, out, silu, eps=self.norm_eps)
+        self.specs.append(out.norm_spec)
+        return out
+
+    def _resblock(self, pre, x0, x1, Cout):               # ResidualBlock (unet6.py:336-362) / diffusers' ResnetBlock2D
+        Cin = x0.C + (x1.C if x1 else 0)
+        slot = self.fc_total
+        self.fc_slots[f"{pre}.{self.res_names[1]}"] = (slot, Cout)
+        self.fc_total += Cout
+        skip = self._conv(f"{pre}.{self.res_names[0]}", x0, x1, Cout, k=1) if Cin != Cout else x0
+        skip_spec = self.specs[-1] if Cin != Cout else None
+        a = self._norm(pre + ".norm1", x0, x1, True)
+        h = self._conv(pre + ".conv1", a, None, Cout, fc=slot)
+        b = self._norm(pre + ".norm2", h, None, True)
+        out = self._conv(pre + ".conv2", b, None, Cout, resid=skip)
+        self.blocks.append(_ResBlock(skip_spec, self.specs[-3], self.specs[-2], self.specs[-1], self.pair_blocks))
+        return out
+
     def _build_specs(self):
-        cfg, N = self.cfg, self.N
+        cfg = self.cfg
         cin, hid, cout = cfg["in_channels"], cfg["hid_channels"], cfg["out_channels"]
         mult, nres, attn = cfg["ch_multipliers"], cfg["num_res_blocks"], cfg["apply_attn"]
         if isinstance(attn, bool):
@@ -740,44 +811,8 @@ class UNet:
         levels = len(mult)
         assert hid % 32 == 0, "GroupNorm(32) needs hid_channels % 32 == 0"
         assert self.H % (1 << (levels - 1)) == 0 and self.W % (1 << (levels - 1)) == 0
-        self.cin, self.cout, self.cin_p, self.cout_p = cin, cout, _pad8(cin), _pad8(cout)
-        self.acts, self.specs, self.fc_slots = [], [], OrderedDict()
-        self.ref_order = []
-        G = ops.ConvGeom
-
-        def conv(name, src0, src1, Cout, k=3, stride=1, ups=0, fc=None, resid=None, rshape=None):
-            H_, W_ = src0.H, src0.W
-            pads = (1, 1, 1, 1) if k == 3 and stride == 1 else (0, 0, 1, 1) if k == 3 else (0, 0, 0, 0)
-            g = G(N=N, IH=H_, IW=W_, C0=src0.C, C1=src1.C if src1 else 0, Cout=Cout, KH=k, KW=k, stride=stride,
-                  pad_t=pads[0], pad_l=pads[1], pad_b=pads[2], pad_r=pads[3], ups=ups)
-            out = self._act(name, g.OH, g.OW, Cout)
-            c = _Conv(self, name, g, src0, src1, out, fc_slot=fc, resid=resid)
-            c.rshape = rshape or (Cout, g.Cin, k, k)
-            self.specs.append(c)
-            return out
-
-        def norm(name, src0, src1, silu):
-            out = self._act(name, src0.H, src0.W, src0.C + (src1.C if src1 else 0))
-            self.specs.append(_Norm(self, name, src0, src1, out, silu))
-            out.norm_spec = self.specs[-1]
-            return out
-
-        def res(pre, x0, x1, Cout):                       # ResidualBlock (unet6.py:336-362)
-            Cin = x0.C + (x1.C if x1 else 0)
-            slot = self.fc_total
-            self.fc_slots[pre + ".fc"] = (slot, Cout)
-            self.fc_total += Cout
-            skip = conv(pre + ".skip", x0, x1, Cout, k=1) if Cin != Cout else x0
-            skip_spec = self.specs[-1] if Cin != Cout else None
-            a = norm(pre + ".norm1", x0, x1, True)
-            h = conv(pre + ".conv1", a, None, Cout, fc=slot)
-            conv1_spec = self.specs[-1]
-            b = norm(pre + ".norm2", h, None, True)
-            self.specs[-1].producer = conv1_spec          # norm2's backward also emits conv1's bias / time-embedding sums
-            out = conv(pre + ".conv2", b, None, Cout, resid=skip)
-            if skip_spec is not None:                     # launch pairs (see _Conv.fwd / _Conv.bwd)
-                skip_spec.pair_host, conv1_spec.pair_skip, self.specs[-1].pair_skip_bwd = conv1_spec, skip_spec, skip_spec
-            return out
+        self._begin_specs(cin, cout)
+        conv, norm, res = self._conv, self._norm, self._resblock
 
         def att(pre, x):                                  # AttentionBlock (unet6.py:296-333)
             C = x.C
@@ -792,7 +827,6 @@ class UNet:
                 return att(pre + ".1", res(pre + ".0", x0, x1, Cout))
             return res(pre, x0, x1, Cout)
 
-        self.fc_total = 0
         self.temb_dim = temb
         self.temb_spec = _Temb(self, hid, temb, 0)
         self.specs.append(self.temb_spec)
@@ -818,6 +852,56 @@ class UNet:
         self.y_out = conv("out_conv.2", h, None, self.cout_p, rshape=(cout, hid, 3, 3))
         self.temb_spec.fc_total = self.fc_total
 
+    def _plan(self):
+        """Fix every launch decision before anything is recorded: each is a function of geometry, dtype and constructor flags alone
+        (host predicates of the library on dummy non-null pointers -- no device, no allocation, so a `_dry` net can be planned too).
+        fwd() / bwd() read these fields and assign none of them; the library checks every fused descriptor again at launch."""
+        bf16, split = self.dt == BF16, self.grad_products == "split"
+        convs = [s for s in self.specs if isinstance(s, _Conv)]
+        readers = lambda act: [s for s in self.specs if isinstance(s, (_Conv, _Norm)) and
+                               (s.src0 is act or s.src1 is act or (isinstance(s, _Conv) and s.resid is act))]
+        # ---- forward
+        for s in self.specs:
+            if isinstance(s, _AttnCore):
+                L, C = s.qkv.P, s.out.C
+                s.mode = ("fused" if ops.attn_supported(self.dt, L, C) else
+                          "f32_small" if self.dt == F32 and ops.attn_f32_small_supported(L, C) else "unfused")
+            elif isinstance(s, _Temb):
+                s.skinny = s._skinny()
+        for prev, nm in zip(self.specs, self.specs[1:]):    # a norm as the epilogue of the conv right before it (4x4 / 8x8 maps)
+            if (bf16 and isinstance(nm, _Norm) and nm.src1 is None and isinstance(prev, _Conv) and prev.out is nm.src0
+                    and ops.conv_fwd_can_fuse_gn(self.dt, prev.g)):
+                prev.gn_fwd, nm.fwd_fused = nm, True
+        pairs = [b for b in self.blocks if self.pair_convs and b.paired and b.skip is not None]
+        for b in pairs:                                     # skip projection + conv1 as one launch
+            b.skip.fwd_in_pair, b.conv1.fwd_mate = True, b.skip
+        if self.uniform_t:                                  # forward-only: no backward decisions
+            return
+        # ---- backward
+        for c in convs:
+            c.sums = "wgrad" if bf16 and c.fc_slot is None else "colsum"
+            wf = ops.wgrad_fields(self.dt, c.g, 16, 16, 16 if c.src1 else None, 16, dbias=16 if c.sums == "wgrad" else None)
+            reason = {w: ops.split_grad_reason(c.g, w) for w in ("wgrad", "dgrad")} if split else {}
+            c.wgrad = ("grouped" if bf16 and self.group_wgrads and _lib.wgrad_group_accepts(**wf) else
+                       "split" if split and reason["wgrad"] is None else "single")
+            if c.src0.needs_grad:
+                c.dgrad = "t" if bf16 else "split" if split and reason["dgrad"] is None else "exact"
+                nm = c.src0.norm_spec
+                if (bf16 and nm is not None and nm.src1 is None and c.src1 is None and not c.g.ups
+                        and ops.conv_dgrad_t_can_fuse_gn_bwd(self.dt, c.g)):
+                    c.gn_bwd, nm.bwd_fused = nm, True
+            c.grad_exact = {w: "exact:" + reason[w] for w, how in (("wgrad", c.wgrad), ("dgrad", c.dgrad))
+                            if split and how in ("single", "exact")}
+        for b in self.blocks:                               # norm2's backward also emits conv1's bias / time-embedding sums
+            assert readers(b.conv1.out) == [b.norm2] and b.norm2.src1 is None and b.conv1.fc_slot is not None, b.conv1.name
+            b.conv1.sums, b.norm2.sums_for = "norm", b.conv1
+        for b in pairs:                                     # the skip projection's backward inside conv2's, data gradients paired
+            if not b.conv2.g.ups:
+                b.skip.bwd_in_pair, b.conv2.bwd_mate = True, b.skip
+        for c in convs:                                     # a norm with several consumers: fused into all of them or into none
+            nm = c.src0.norm_spec
+            assert nm is None or not nm.bwd_fused or c.gn_bwd is nm, c.name
+
     def _declare_params(self):
         st = self.store
         self.temb_spec.declare(st)
@@ -834,7 +918,7 @@ class UNet:
         spec (and of everything after it) has run; parameter-less specs inherit their successor's."""
         st, lo = self.store, self.store.size
         for s in reversed(self.specs[1:]):
-            key = getattr(s, "name", None)
+            key = s.name
             if key is not None and key + ".weight" in st.entries:
                 lo = st.entries[key + ".weight"].off
             s.param_lo = lo
@@ -948,7 +1032,6 @@ class UNet:
         # split-K partial slabs of the weight-gradient contractions: room for 16 splits of the largest filter
         wmax = max(s.g.taps * s.g.Cout * s.g.Cin for s in self.specs if isinstance(s, _Conv))
         self.splitk_ws = self.alloc((16 * wmax,), torch.float32)
-        self.splitk_ws2 = self.splitk_ws
         # grouped weight gradients: every split layer gets its own slice of one arena for its fp32 partial slabs
         self._slab_arena, self._slab_off = None, 0
         if self.dt == BF16 and self.group_wgrads:

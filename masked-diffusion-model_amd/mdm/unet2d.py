@@ -27,8 +27,7 @@ from collections import OrderedDict
 import torch
 
 from . import ops
-from ._lib import BF16
-from .unet import UNet, _Conv, _Norm, _pad8, _Temb
+from .unet import UNet, _Temb
 
 
 def my_model_config(dim_channel, dim_height, num_attention=1, block_out_channels=(128, 128, 256, 256, 512, 512),
@@ -49,7 +48,8 @@ class _AttnMH:
     """softmax(q k^T / sqrt(d)) v with C/d heads on separate q, k, v tensors (diffusers Attention inside UNet2DModel)."""
 
     def __init__(self, net, q, k, v, out, heads):
-        self.net, self.q, self.k, self.v, self.out, self.heads = net, q, k, v, out, heads
+        self.net, self.q, self.k, self.v, self.out, self.heads, self.name = net, q, k, v, out, heads, None
+        self.param_lo = self.lse = self.delta = None
 
     def declare(self, st):
         pass
@@ -78,44 +78,18 @@ class _AttnMH:
 class UNet2D(UNet):
     """`UNet2D(my_model_config(C, H, num_attention), N, H, W, dtype)`; same surface as `mdm.UNet`."""
 
+    down_pads = (1, 1, 0, 0)        # Downsample2D: padding=1
+    res_names = ("conv_shortcut", "time_emb_proj")
+    pair_blocks = False             # unpaired: pairing would change this net's launches
+
     def _build_specs(self):
-        cfg, N = self.cfg, self.N
+        cfg = self.cfg
         cin, cout, boc = cfg["in_channels"], cfg["out_channels"], list(cfg["block_out_channels"])
-        lpb, hd, eps = cfg["layers_per_block"], cfg["attention_head_dim"], cfg.get("norm_eps", 1e-5)
+        lpb, hd = cfg["layers_per_block"], cfg["attention_head_dim"]
+        self.norm_eps = cfg.get("norm_eps", 1e-5)
         temb = 4 * boc[0]
-        self.cin, self.cout, self.cin_p, self.cout_p = cin, cout, _pad8(cin), _pad8(cout)
-        self.acts, self.specs, self.fc_slots = [], [], OrderedDict()
-        self.ref_order = []
-        G = ops.ConvGeom
-
-        def conv(name, src0, src1, Cout, k=3, stride=1, ups=0, fc=None, resid=None, rshape=None):
-            pads = (1, 1, 1, 1) if k == 3 and stride == 1 else (1, 1, 0, 0) if k == 3 else (0, 0, 0, 0)   # Downsample2D: padding=1
-            g = G(N=N, IH=src0.H, IW=src0.W, C0=src0.C, C1=src1.C if src1 else 0, Cout=Cout, KH=k, KW=k, stride=stride,
-                  pad_t=pads[0], pad_l=pads[1], pad_b=pads[2], pad_r=pads[3], ups=ups)
-            out = self._act(name, g.OH, g.OW, Cout)
-            c = _Conv(self, name, g, src0, src1, out, fc_slot=fc, resid=resid)
-            c.rshape = rshape or (Cout, g.Cin, k, k)
-            self.specs.append(c)
-            return out
-
-        def norm(name, src0, src1, silu):
-            out = self._act(name, src0.H, src0.W, src0.C + (src1.C if src1 else 0))
-            self.specs.append(_Norm(self, name, src0, src1, out, silu, eps=eps))
-            out.norm_spec = self.specs[-1]
-            return out
-
-        def resnet(pre, x0, x1, Cout):                    # ResnetBlock2D
-            Cin = x0.C + (x1.C if x1 else 0)
-            slot = self.fc_total
-            self.fc_slots[pre + ".time_emb_proj"] = (slot, Cout)
-            self.fc_total += Cout
-            skip = conv(pre + ".conv_shortcut", x0, x1, Cout, k=1) if Cin != Cout else x0
-            a = norm(pre + ".norm1", x0, x1, True)
-            h = conv(pre + ".conv1", a, None, Cout, fc=slot)
-            conv1_spec = self.specs[-1]
-            b = norm(pre + ".norm2", h, None, True)
-            self.specs[-1].producer = conv1_spec
-            return conv(pre + ".conv2", b, None, Cout, resid=skip)
+        self._begin_specs(cin, cout)
+        conv, norm, resnet = self._conv, self._norm, self._resblock
 
         def attn(pre, x):                                 # Attention (deprecated-attention-block form), heads of width hd
             C = x.C
@@ -127,7 +101,6 @@ class UNet2D(UNet):
             self.specs.append(_AttnMH(self, q, k_, v, o, C // hd))
             return conv(pre + ".to_out.0", o, None, C, k=1, resid=x, rshape=(C, C))
 
-        self.fc_total = 0
         self.temb_dim = temb
         self.temb_spec = _Temb(self, boc[0], temb, 0, names=("time_embedding.linear_1", "time_embedding.linear_2"), variant=(True, 0.0))
         self.specs.append(self.temb_spec)
@@ -161,7 +134,6 @@ class UNet2D(UNet):
 
     def _default_params(self, seed):
         return default_init_params(self.reference_shapes(), seed)
-
 
     def reference_param_order(self):
         """Registration order of diffusers' UNet2DModel as published: conv_in, time_embedding, down_blocks, up_blocks,
