@@ -405,7 +405,7 @@ int mdm_unit_rows(const float* x, float* y, int R, int D, float eps, void* strea
 int mdm_col_argmax(const float* S, int M, int B, float* val, int64_t* idx, void* stream);
 
 /* ------------------------------------------------------------------------- *
- * Optimizer: global-norm clip + AdamW + EMA + bf16 weight shadow in one pass over
+ * Optimizer: global-norm clip + AdamW (or SGD / Adam, mdm_optim_update) + EMA + bf16 weight shadow in one pass over
  * flat fp32 buffers (trainer_masked_mean_shift.py:163-172, main_train_masked.py:134-141).
  *   hp (device, 8 floats): lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ema_decay
  *   mdm_sqnorm stores sum(g^2) to *out (two-stage, fixed summation order: bit-identical on every rank).
@@ -415,6 +415,21 @@ int mdm_col_argmax(const float* S, int M, int B, float* val, int64_t* idx, void*
 int mdm_sqnorm(const float* g, int64_t n, float* out, void* stream);
 int mdm_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, void* shadow_bf16,
                   int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream);
+/* The reference's other two optimizers (`--optim sgd | adam`, main_train_masked.py:134-141, 375: `optim.SGD(params, lr=lr)`,
+ * `optim.Adam(params, lr=lr)`) in the same sweep: clip coefficient from *sqnorm, gmul, update, EMA, bf16 shadow.  Replaces
+ * accelerator.clip_grad_norm_ + torch.optim.SGD.step / torch.optim.Adam.step + EMAModel.step (trainer_masked_mean_shift.py:163-172).
+ *   kind 0  SGD with momentum == 0: buf0 = buf1 = NULL, no state            d = coef g + wd p;  p -= lr d
+ *   kind 1  SGD with momentum: buf0 = momentum buffer                       buf = buf_decay buf + g_scale d;
+ *                                                                           p -= lr (nesterov ? d + momentum buf : buf)
+ *   kind 2  Adam: buf0 = exp_avg, buf1 = exp_avg_sq; the weight decay is COUPLED (d = coef g + wd p enters both moments),
+ *           then mdm_adamw_ema's moment updates, bias corrections and step
+ *   hp (device, 8 floats)  SGD:  lr, momentum, buf_decay, g_scale, weight_decay, nesterov (0 | 1), unused, ema_decay --
+ *                                (buf_decay, g_scale) = (0, 1) on the optimizer's first step (torch: buf = d), (momentum, 1 - dampening)
+ *                                afterwards: the block is device memory, so a captured graph follows the rule
+ *                          Adam: mdm_adamw_ema's block
+ *   every buffer 16-byte aligned; any n (a tail of n % 8 elements is handled); ema / shadow may be NULL. */
+int mdm_optim_update(int kind, float* p, const float* g, float* buf0, float* buf1, float* ema, void* shadow_bf16,
+                     int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream);
 int mdm_cast_bf16(const float* src, void* dst, int64_t n, void* stream);
 /* Transposed bf16 shadow of the conv filters for the data-gradient pass, from the bf16 shadow Pb the optimizer kernel writes:
  * for every 64x64 tile listed in `tiles` (device, int64 x5 per tile: element offset of one tap's [Cout][Cin] matrix, Cout,

@@ -1,8 +1,8 @@
-// Optimizer pass over flat fp32 buffers: global grad-norm, clip, AdamW, EMA and the
-// bf16 weight shadow in one read-modify-write sweep (HBM-bound: 16 B read + 12..18 B
-// written per parameter).
+// Optimizer pass over flat fp32 buffers: global grad-norm, clip, AdamW / Adam / SGD, EMA and the
+// bf16 weight shadow in one read-modify-write sweep (HBM-bound; AdamW and Adam: 16 B read + 12..18 B
+// written per parameter, SGD: 8..12 B read + 4..8 B written, + 4 B each way for the EMA, + 2 B for the shadow).
 //
-// Replaces accelerator.clip_grad_norm_ + torch.optim.AdamW.step + diffusers EMAModel.step
+// Replaces accelerator.clip_grad_norm_ + torch.optim.{AdamW, Adam, SGD}.step + diffusers EMAModel.step
 // (reference trainer_masked_mean_shift.py:163-172, main_train_masked.py:116-141).
 #include "common.h"
 
@@ -58,6 +58,101 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
         p[i] = pi; m[i] = mi; v[i] = vi;
         if (ema) { float e = ema[i]; ema[i] = e - (1.f - ed) * (e - pi); }
         if (shadow) shadow[i] = f2bf(pi);
+    }
+}
+
+// SGD and Adam (mdm_optim_update): the same sweep as adamw_kernel -- clip coefficient, gmul, update, EMA, bf16 shadow -- for the two
+// other optimizers of the reference's `--optim` switch, 8 elements per lane and iteration: two 16-byte loads per stream, two 16-byte
+// stores per fp32 stream and one 16-byte store of the shadow.  Bytes per parameter, EMA and shadow aside (+8 B and +2 B):
+//   KIND 0  SGD, momentum == 0: no state at all               8 B read +  4 B written
+//   KIND 1  SGD with a momentum buffer (s0)                   12 B read +  8 B written
+//   KIND 2  Adam, coupled (L2) weight decay (s0 = m, s1 = v)  16 B read + 12 B written
+// hp (device, 8 floats):
+//   SGD   lr, momentum, buf_decay, g_scale, weight_decay, nesterov (0 | 1), -, ema_decay
+//         buf = buf_decay buf + g_scale d: the host sends (0, 1) on the optimizer's first step (torch: buf = d) and (momentum,
+//         1 - dampening) afterwards -- the rule lives in the block, not in a kernel argument, so a captured graph replays it
+//   Adam  adamw_kernel's block: lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ema_decay
+enum { OPT_SGD = 0, OPT_SGD_MOMENTUM = 1, OPT_ADAM = 2 };
+
+struct OptimConsts {
+    float coef, lr, wd, ed, a, b, c, d, e;      // a..e: per kind, see optim_consts
+};
+template <int KIND>
+__device__ __forceinline__ OptimConsts optim_consts(const float* hp, const float* sqnorm, float max_norm, float gmul) {
+    OptimConsts k;
+    k.coef = gmul;
+    if (max_norm > 0.f) {
+        float norm = sqrtf(*sqnorm) * gmul;
+        float c = max_norm / (norm + 1e-6f);          // torch.nn.utils.clip_grad_norm_
+        if (c < 1.f) k.coef *= c;
+    }
+    k.lr = hp[0]; k.wd = hp[4]; k.ed = hp[7];
+    if (KIND == OPT_ADAM) {
+        k.a = hp[1]; k.b = hp[2]; k.c = hp[3];        // beta1, beta2, eps
+        k.d = hp[0] / hp[5]; k.e = rsqrtf(hp[6]);     // lr / bias_corr1, 1 / sqrt(bias_corr2)
+    } else {
+        k.a = hp[1]; k.b = hp[2]; k.c = hp[3]; k.d = hp[5]; k.e = 0.f;   // momentum, buf_decay, g_scale, nesterov
+    }
+    return k;
+}
+// one element: p, s0, s1 updated in place (torch's single-tensor SGD / Adam, in their order of operations)
+template <int KIND>
+__device__ __forceinline__ void optim_elem(const OptimConsts& k, float& p, float g, float& s0, float& s1) {
+    float d = g * k.coef;
+    d += k.wd * p;                                    // coupled (L2) decay: part of the gradient, unlike AdamW's
+    if (KIND == OPT_SGD_MOMENTUM) {
+        s0 = k.b * s0 + k.c * d;
+        d = k.d != 0.f ? d + k.a * s0 : s0;           // nesterov reads the NEW buffer
+    }
+    if (KIND == OPT_ADAM) {
+        s0 = k.a * s0 + (1.f - k.a) * d;
+        s1 = k.b * s1 + (1.f - k.b) * d * d;
+        float denom = sqrtf(s1) * k.e + k.c;
+        p -= k.d * s0 / denom;
+    } else {
+        p -= k.lr * d;
+    }
+}
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_update_kernel(float* p, const float* g, float* s0, float* s1, float* ema, bf16_t* shadow,
+                                                           int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul) {
+    const OptimConsts k = optim_consts<KIND>(hp, sqnorm, max_norm, gmul);
+    const float ew = 1.f - k.ed;
+    const int64_t n8 = n >> 3;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
+        const int64_t o = i * 8;
+        float8 pv = load8(p + o), a = {}, b = {}, ev = {};
+        const float8 gv = load8(g + o);
+        if (KIND >= OPT_SGD_MOMENTUM) a = load8(s0 + o);
+        if (KIND == OPT_ADAM) b = load8(s1 + o);
+        if (ema) ev = load8(ema + o);
+        float *pf = reinterpret_cast<float*>(&pv), *af = reinterpret_cast<float*>(&a), *bf = reinterpret_cast<float*>(&b);
+        float* ef = reinterpret_cast<float*>(&ev);
+        const float* gf = reinterpret_cast<const float*>(&gv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) optim_elem<KIND>(k, pf[j], gf[j], af[j], bf[j]);
+        if (ema) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ef[j] = ef[j] - ew * (ef[j] - pf[j]);
+        }
+        store8(p + o, pv);
+        if (KIND >= OPT_SGD_MOMENTUM) store8(s0 + o, a);
+        if (KIND == OPT_ADAM) store8(s1 + o, b);
+        if (ema) store8(ema + o, ev);
+        if (shadow) store8(shadow + o, pv);
+    }
+    // the n % 8 elements behind the last whole group (the parameter store's sizes are multiples of 8: plain tensors only)
+    const int64_t t = n8 * 8 + threadIdx.x;
+    if (blockIdx.x == 0 && t < n) {
+        float pi = p[t], a = 0.f, b = 0.f;
+        if (KIND >= OPT_SGD_MOMENTUM) a = s0[t];
+        if (KIND == OPT_ADAM) b = s1[t];
+        optim_elem<KIND>(k, pi, g[t], a, b);
+        p[t] = pi;
+        if (KIND >= OPT_SGD_MOMENTUM) s0[t] = a;
+        if (KIND == OPT_ADAM) s1[t] = b;
+        if (ema) { float e = ema[t]; ema[t] = e - ew * (e - pi); }
+        if (shadow) shadow[t] = f2bf(pi);
     }
 }
 
@@ -178,6 +273,26 @@ extern "C" int mdm_adamw_ema(float* p, const float* g, float* m, float* v, float
     hipLaunchKernelGGL(adamw_kernel, dim3(ogrid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, (bf16_t*)shadow_bf16, n, hp,
                        sqnorm, max_norm, gmul);
     return launch_status("adamw");
+}
+extern "C" int mdm_optim_update(int kind, float* p, const float* g, float* buf0, float* buf1, float* ema, void* shadow_bf16, int64_t n,
+                                const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream) {
+    MDM_REQUIRE(kind == OPT_SGD || kind == OPT_SGD_MOMENTUM || kind == OPT_ADAM, "optim_update: kind must be 0 (SGD), 1 (SGD + momentum) or 2 (Adam)");
+    MDM_REQUIRE(p && g && hp && n > 0, "optim_update: bad arguments");
+    MDM_REQUIRE(kind == OPT_SGD || buf0, "optim_update: this kind needs its first state buffer");
+    MDM_REQUIRE(kind != OPT_ADAM || buf1, "optim_update: Adam needs both state buffers");
+    MDM_REQUIRE(max_norm <= 0.f || sqnorm, "optim_update: clipping needs the squared norm");
+    MDM_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf0 | (uintptr_t)buf1 | (uintptr_t)ema | (uintptr_t)shadow_bf16) & 15) == 0,
+                "optim_update: buffers must be 16-byte aligned");
+    const dim3 grid(ogrid(n / 8)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    bf16_t* sh = (bf16_t*)shadow_bf16;
+    if (kind == OPT_SGD)
+        hipLaunchKernelGGL(optim_update_kernel<OPT_SGD>, grid, block, 0, st, p, g, nullptr, nullptr, ema, sh, n, hp, sqnorm, max_norm, gmul);
+    else if (kind == OPT_SGD_MOMENTUM)
+        hipLaunchKernelGGL(optim_update_kernel<OPT_SGD_MOMENTUM>, grid, block, 0, st, p, g, buf0, nullptr, ema, sh, n, hp, sqnorm, max_norm, gmul);
+    else
+        hipLaunchKernelGGL(optim_update_kernel<OPT_ADAM>, grid, block, 0, st, p, g, buf0, buf1, ema, sh, n, hp, sqnorm, max_norm, gmul);
+    return launch_status("optim_update");
 }
 extern "C" int mdm_transpose_shadow_bf16(const void* Pb, void* PT, const int64_t* tiles, int ntiles, void* stream) {
     MDM_REQUIRE(Pb && PT && tiles && ntiles > 0, "transpose_shadow_bf16: bad arguments");

@@ -9,7 +9,7 @@ from . import _lib  # noqa: F401
 from . import evaluate  # noqa: F401
 from ._lib import BF16, F32  # noqa: F401
 from .dist import GradComm  # noqa: F401
-from .optim import EMA, Accelerator, AdamW, get_lr_scheduler  # noqa: F401
+from .optim import EMA, SGD, Accelerator, Adam, AdamW, get_lr_scheduler, get_optimizer  # noqa: F401
 from .sampler import Sampler  # noqa: F401
 from .scheduler import Scheduler  # noqa: F401
 from .trainer import BaseTrainer, Trainer  # noqa: F401

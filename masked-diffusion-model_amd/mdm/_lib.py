@@ -98,6 +98,7 @@ _PROTOS = {
     "mdm_sampler_step_params": ([vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
     "mdm_sqnorm": ([vp, i64, vp, vp], i32),
     "mdm_adamw_ema": ([vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp], i32),
+    "mdm_optim_update": ([i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp], i32),
     "mdm_cast_bf16": ([vp, vp, i64, vp], i32),
     "mdm_transpose_shadow_bf16": ([vp, vp, vp, i32, vp], i32),
     "mdm_split_shadow": ([vp, vp, vp, i32, vp], i32),

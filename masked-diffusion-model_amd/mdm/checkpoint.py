@@ -10,8 +10,9 @@ hooks of main_train_masked.py:195-225, and resumes with `accelerator.load_state(
                                                      decay, min_decay, optimization_step, update_after_step,
                                                      use_ema_warmup, inv_gamma, power
     <path>/unet_ema/diffusion_pytorch_model.safetensors   the shadow parameters under the same keys
-    <path>/optimizer.bin                             torch.save(optimizer.state_dict()): torch.optim.AdamW layout,
-                                                     parameters indexed in `model.parameters()` order
+    <path>/optimizer.bin                             torch.save(optimizer.state_dict()): the layout of the matching torch.optim class
+                                                     (AdamW / Adam: step, exp_avg, exp_avg_sq; SGD: momentum_buffer, or no
+                                                     state when momentum == 0), parameters indexed in `model.parameters()` order
     <path>/scheduler.bin                             torch.save(lr_scheduler.state_dict())
     <path>/random_states_<rank>.pkl                  torch.save (despite the suffix) of {step, random_state,
                                                      numpy_random_seed, torch_manual_seed[, torch_cuda_manual_seed]}

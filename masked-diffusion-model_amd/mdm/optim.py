@@ -1,8 +1,9 @@
-"""Optimizer-side objects the reference's trainers are handed: AdamW, EMA,
+"""Optimizer-side objects the reference's trainers are handed: AdamW / Adam / SGD, EMA,
 LR schedule, and a thin accelerator -- over the flat parameter buffers of mdm.UNet.
 
-Reference call sites: optimizer `optim.AdamW(model.parameters(), lr=lr)` (main_train_masked.py:134-141,
-torch defaults betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2); EMA `EMAModel(decay=ema_max_decay,
+Reference call sites: optimizer `get_optimizer(model, args.optim, args.lr)` -> `optim.SGD | Adam | AdamW(model.parameters(), lr=lr)`
+(main_train_masked.py:134-141, 375; torch defaults: AdamW betas (0.9, 0.999), eps 1e-8, weight_decay 1e-2; Adam the same with
+weight_decay 0; SGD momentum 0, dampening 0, weight_decay 0); EMA `EMAModel(decay=ema_max_decay,
 use_ema_warmup=True, inv_gamma, power)` (:116-131) stepped at trainer_masked_mean_shift.py:170-172;
 LR schedules diffusers `get_*_schedule_with_warmup` (:144-165).  EMAModel and the LR schedules are
 third-party code that is absent from the reference tree: their semantics are implemented from the
@@ -18,13 +19,19 @@ from . import _lib, ops
 from ._lib import call, ptr, stream
 
 
-class AdamW:
-    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+class _FlatOptimizer:
+    """What AdamW, Adam and SGD share over the flat buffers of a ParamStore: the pinned ring the 8-float hyper-parameter block
+    travels through, the squared gradient norm, the launches behind the update kernel, `step` / `zero_grad` / `grad_norm`, and the
+    torch.optim `state_dict()` grammar (parameters indexed in `model.reference_param_order()`).  A subclass gives
+      _fill(h, g, ema_decay)   write the block for step `self.t` into the pinned slot `h`
+      _emit_kernel(...)        enqueue (or record) its update kernel
+      _state() / _load(st)     the per-parameter `state` entries, out and in
+      _group() / _FIELDS       the `param_groups[0]` fields torch writes besides lr / initial_lr / params."""
+
+    def __init__(self, model, group):
         st = model.store
         self.model, self.store = model, st
-        self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, initial_lr=lr)]
-        self.m = torch.zeros_like(st.P)
-        self.v = torch.zeros_like(st.P)
+        self.param_groups = [dict(group, initial_lr=group["lr"])]
         self.t = 0
         # the 8-float hyper-parameter block travels by async H2D copy from pinned memory, which is read when the copy
         # EXECUTES: a host that runs ahead of the GPU must not overwrite a block whose copy has not run yet -> a ring of
@@ -36,21 +43,27 @@ class AdamW:
         self.hp = torch.zeros(8, device=st.P.device)
         self.sqnorm = torch.zeros(1, device=st.P.device)
 
+    def _advance(self):
+        self.t += 1
+
+    def _check_flags(self, g):
+        """Adam and SGD refuse a checkpoint whose group asks for what they do not implement (AdamW reads its fields as it always did)."""
+        for k in ("amsgrad", "maximize", "capturable", "differentiable"):
+            if g.get(k):
+                raise ValueError(f"{type(self).__name__}.load_state_dict: {k}=True is not implemented")
+
     def hyper(self, ema_decay=0.0, advance=True):
-        """Refresh the 8-float device block read by mdm_adamw_ema (async H2D)."""
+        """Refresh the 8-float device block the update kernel reads (async H2D)."""
         g = self.param_groups[0]
         if advance:
-            self.t += 1
-        b1, b2 = g["betas"]
+            self._advance()
         k = self._hp_k
         self._hp_k = (k + 1) % self._hp_slots
         g16 = k // 16
         if k % 16 == 0 and self._hp_events[g16] is not None:
             self._hp_events[g16].synchronize()        # every copy that read this group of slots has executed
         h = self.hp_host[k]
-        h[0] = g["lr"]; h[1] = b1; h[2] = b2; h[3] = g["eps"]
-        h[4] = g["weight_decay"]
-        h[5] = 1 - b1 ** self.t; h[6] = 1 - b2 ** self.t; h[7] = ema_decay
+        self._fill(h, g, ema_decay)
         self.hp.copy_(h, non_blocking=True)
         if self.hp.is_cuda and k % 16 == 15:
             ev = self._hp_events[g16] or torch.cuda.Event()
@@ -58,11 +71,10 @@ class AdamW:
             self._hp_events[g16] = ev
 
     def emit_update(self, ema_buf=None, max_norm=1.0, gmul=1.0):
-        """Enqueue (or record) grad-norm + clip + AdamW + EMA + bf16 shadow over the flat buffers."""
+        """Enqueue (or record) grad-norm + clip + update + EMA + bf16 shadow over the flat buffers."""
         st = self.store
         call("mdm_sqnorm", ptr(st.G), st.size, ptr(self.sqnorm), stream())
-        call("mdm_adamw_ema", ptr(st.P), ptr(st.G), ptr(self.m), ptr(self.v), ptr(ema_buf), ptr(st.Pb), st.size,
-             ptr(self.hp), ptr(self.sqnorm), float(max_norm), float(gmul), stream())
+        self._emit_kernel(ema_buf, float(max_norm), float(gmul))
         st.emit_transposed_shadow()
         st.emit_split_shadow()          # fp32 stores with split products: the filters' hi / lo shadow follows the weights
         st.emit_split_shadow_t()        # ... and so does the flipped, transposed one of split-product gradients
@@ -77,33 +89,213 @@ class AdamW:
     def grad_norm(self):
         return float(self.sqnorm.sqrt())
 
-    def state_dict(self):
-        """`torch.optim.AdamW.state_dict()` layout: per-parameter `step` / `exp_avg` / `exp_avg_sq` in the reference's
-        shapes, indexed in `model.parameters()` order (what accelerate writes to optimizer.bin)."""
+    def _per_param(self, **bufs):
+        """{index: {name: tensor in the reference's shape}} over `model.parameters()` order, from flat buffers."""
         order = self.model.reference_param_order()
-        m = self.store.state_dict(order=order, src=self.m)
-        v = self.store.state_dict(order=order, src=self.v)
-        state = {i: dict(step=torch.tensor(float(self.t)), exp_avg=m[k], exp_avg_sq=v[k]) for i, k in enumerate(order)} if self.t else {}
+        views = {name: self.store.state_dict(order=order, src=b) for name, b in bufs.items()}
+        return {i: {name: v[k] for name, v in views.items()} for i, k in enumerate(order)}
+
+    def _flat(self, st, name, dst):
+        order = self.model.reference_param_order()
+        assert len(st) == len(order), (len(st), len(order))
+        dst.copy_(self.store.flat_from_reference({k: st[i][name] for i, k in enumerate(order)}).to(dst.device))
+
+    def state_dict(self):
         g = self.param_groups[0]
-        group = dict(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"], amsgrad=False,
-                     maximize=False, foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True,
-                     initial_lr=g["initial_lr"], params=list(range(len(order))))
-        return dict(state=state, param_groups=[group])
+        group = dict(lr=g["lr"], **self._group(g), initial_lr=g["initial_lr"], params=list(range(len(self.model.reference_param_order()))))
+        return dict(state=self._state(), param_groups=[group])
 
     def load_state_dict(self, sd):
-        order = self.model.reference_param_order()
-        st = sd["state"]
+        g = sd["param_groups"][0]
+        self._check_flags(g)
+        new = dict(lr=g["lr"], initial_lr=g.get("initial_lr", g["lr"]))
+        for k in self._FIELDS:
+            new[k] = tuple(g[k]) if k == "betas" else g[k]
+        self._check(new)
+        self._load(sd["state"])
+        self.param_groups = [new]
+
+
+def _no(what, **flags):
+    for k, v in flags.items():
+        if v:
+            raise ValueError(f"{what}: {k}=True is not implemented")
+
+
+def _check_adam(g):
+    b1, b2 = g["betas"]
+    if not 0.0 <= g["lr"]:
+        raise ValueError(f"Invalid learning rate: {g['lr']}")
+    if not 0.0 <= g["eps"]:
+        raise ValueError(f"Invalid epsilon value: {g['eps']}")
+    if not 0.0 <= b1 < 1.0:
+        raise ValueError(f"Invalid beta parameter at index 0: {b1}")
+    if not 0.0 <= b2 < 1.0:
+        raise ValueError(f"Invalid beta parameter at index 1: {b2}")
+    if not 0.0 <= g["weight_decay"]:
+        raise ValueError(f"Invalid weight_decay value: {g['weight_decay']}")
+
+
+class _AdamBase(_FlatOptimizer):
+    """Two moment buffers, a step count and AdamW's 8-float block: lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2,
+    ema_decay.  `torch.optim.Adam[W].state_dict()` layout: per-parameter `step` / `exp_avg` / `exp_avg_sq` in the reference's
+    shapes, indexed in `model.parameters()` order (what accelerate writes to optimizer.bin)."""
+    _FIELDS = ("betas", "eps", "weight_decay")
+    _DECOUPLED = None
+
+    def __init__(self, model, lr, betas, eps, weight_decay):
+        super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.m = torch.zeros_like(self.store.P)
+        self.v = torch.zeros_like(self.store.P)
+
+    def _check(self, g):
+        pass
+
+    def _fill(self, h, g, ema_decay):
+        b1, b2 = g["betas"]
+        h[0] = g["lr"]; h[1] = b1; h[2] = b2; h[3] = g["eps"]
+        h[4] = g["weight_decay"]
+        h[5] = 1 - b1 ** self.t; h[6] = 1 - b2 ** self.t; h[7] = ema_decay
+
+    def _group(self, g):
+        return dict(betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"], amsgrad=False, maximize=False, foreach=None,
+                    capturable=False, differentiable=False, fused=None, decoupled_weight_decay=self._DECOUPLED)
+
+    def _state(self):
+        if not self.t:
+            return {}
+        st = self._per_param(exp_avg=self.m, exp_avg_sq=self.v)
+        return {i: dict(step=torch.tensor(float(self.t)), **d) for i, d in st.items()}
+
+    def _load(self, st):
         if st:
-            assert len(st) == len(order), (len(st), len(order))
-            dev = self.m.device
-            self.m.copy_(self.store.flat_from_reference({k: st[i]["exp_avg"] for i, k in enumerate(order)}).to(dev))
-            self.v.copy_(self.store.flat_from_reference({k: st[i]["exp_avg_sq"] for i, k in enumerate(order)}).to(dev))
+            self._flat(st, "exp_avg", self.m)
+            self._flat(st, "exp_avg_sq", self.v)
             self.t = int(float(st[0]["step"]))
         else:
             self.m.zero_(); self.v.zero_(); self.t = 0
-        g = sd["param_groups"][0]
-        self.param_groups = [dict(lr=g["lr"], betas=tuple(g["betas"]), eps=g["eps"], weight_decay=g["weight_decay"],
-                                  initial_lr=g.get("initial_lr", g["lr"]))]
+
+
+class AdamW(_AdamBase):
+    """`torch.optim.AdamW(params, lr)`: decoupled weight decay (mdm_adamw_ema)."""
+    _DECOUPLED = True
+
+    def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        super().__init__(model, lr, betas, eps, weight_decay)
+
+    def _check_flags(self, g):
+        pass
+
+    def _emit_kernel(self, ema_buf, max_norm, gmul):
+        st = self.store
+        call("mdm_adamw_ema", ptr(st.P), ptr(st.G), ptr(self.m), ptr(self.v), ptr(ema_buf), ptr(st.Pb), st.size,
+             ptr(self.hp), ptr(self.sqnorm), max_norm, gmul, stream())
+
+
+class Adam(_AdamBase):
+    """`torch.optim.Adam(params, lr)` (main_train_masked.py:137-138): AdamW's moments, bias corrections and step, with the weight
+    decay COUPLED -- added to the gradient (L2), so it enters both moments (mdm_optim_update, kind 2)."""
+    _DECOUPLED = False
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False):
+        _no("Adam", amsgrad=amsgrad, maximize=maximize)
+        _check_adam(dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        super().__init__(model, lr, betas, eps, weight_decay)
+
+    _check = staticmethod(_check_adam)
+
+    def _emit_kernel(self, ema_buf, max_norm, gmul):
+        st = self.store
+        call("mdm_optim_update", 2, ptr(st.P), ptr(st.G), ptr(self.m), ptr(self.v), ptr(ema_buf), ptr(st.Pb), st.size,
+             ptr(self.hp), ptr(self.sqnorm), max_norm, gmul, stream())
+
+
+def _check_sgd(g):
+    if g["lr"] < 0.0:
+        raise ValueError(f"Invalid learning rate: {g['lr']}")
+    if g["momentum"] < 0.0:
+        raise ValueError(f"Invalid momentum value: {g['momentum']}")
+    if g["dampening"] < 0.0:                     # (torch lets this one through; it has no meaning)
+        raise ValueError(f"Invalid dampening value: {g['dampening']}")
+    if g["weight_decay"] < 0.0:
+        raise ValueError(f"Invalid weight_decay value: {g['weight_decay']}")
+    if g["nesterov"] and (g["momentum"] <= 0 or g["dampening"] != 0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+
+class SGD(_FlatOptimizer):
+    """`torch.optim.SGD(params, lr)` (main_train_masked.py:135-136) with torch's momentum / dampening / weight_decay / nesterov
+    (mdm_optim_update, kind 0 or 1).  With momentum == 0 there is NO state buffer: two parameter-sized buffers less than AdamW.
+    Whether there is one is fixed at construction.  The block: lr, momentum, buf_decay, g_scale, weight_decay, nesterov, 0,
+    ema_decay -- (buf_decay, g_scale) = (0, 1) on the step that creates the momentum buffer (torch: buf = d), (momentum,
+    1 - dampening) afterwards; it is device memory refreshed per step, so a captured graph follows the rule."""
+    _FIELDS = ("momentum", "dampening", "weight_decay", "nesterov")
+
+    def __init__(self, model, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, maximize=False):
+        _no("SGD", maximize=maximize)
+        g = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov)
+        _check_sgd(g)
+        super().__init__(model, g)
+        self.buf = torch.zeros_like(self.store.P) if momentum != 0 else None
+        self._has_buf = False                    # torch: `momentum_buffer` exists from the first step on
+        self._first = True                       # the block of the current step carries the first-step rule
+
+    def _check(self, g):
+        _check_sgd(g)
+        if (g["momentum"] != 0) != (self.buf is not None):
+            raise ValueError("SGD.load_state_dict: momentum == 0 and momentum != 0 are different kernels with different state; "
+                             "build the optimizer with the momentum of the checkpoint")
+
+    def _advance(self):
+        self.t += 1
+        self._first = not self._has_buf
+        self._has_buf = True
+
+    def _fill(self, h, g, ema_decay):
+        first = self._first or self.buf is None
+        h[0] = g["lr"]; h[1] = g["momentum"]
+        h[2] = 0.0 if first else g["momentum"]
+        h[3] = 1.0 if first else 1.0 - g["dampening"]
+        h[4] = g["weight_decay"]; h[5] = float(bool(g["nesterov"])); h[6] = 0.0; h[7] = ema_decay
+
+    def _emit_kernel(self, ema_buf, max_norm, gmul):
+        st = self.store
+        call("mdm_optim_update", 0 if self.buf is None else 1, ptr(st.P), ptr(st.G), ptr(self.buf), None, ptr(ema_buf), ptr(st.Pb), st.size,
+             ptr(self.hp), ptr(self.sqnorm), max_norm, gmul, stream())
+
+    def _group(self, g):
+        return dict(momentum=g["momentum"], dampening=g["dampening"], weight_decay=g["weight_decay"], nesterov=g["nesterov"],
+                    maximize=False, foreach=None, differentiable=False, fused=None)
+
+    def _state(self):
+        """`torch.optim.SGD.state_dict()`: `momentum_buffer` per parameter once a step has run; nothing when momentum == 0."""
+        if self.buf is None or not self._has_buf:
+            return {}
+        return self._per_param(momentum_buffer=self.buf)
+
+    def _load(self, st):
+        if st and self.buf is not None and st[0].get("momentum_buffer") is not None:
+            self._flat(st, "momentum_buffer", self.buf)
+            self._has_buf = True
+        else:
+            if self.buf is not None:
+                self.buf.zero_()
+            self._has_buf = False
+        self._first = not self._has_buf
+
+
+def get_optimizer(model, optim_name, lr):
+    """`get_optimizer(model, optim_name, lr)` of main_train_masked.py:134-141 (`--optim {adam, adamw, sgd}`, :375): the name is
+    case-insensitive, every other hyper-parameter is torch's default, and any other name fails as upstream's does (its
+    `optimizer` is never bound)."""
+    name = optim_name.lower()
+    if name == "sgd":
+        return SGD(model, lr=lr)
+    if name == "adam":
+        return Adam(model, lr=lr)
+    if name == "adamw":
+        return AdamW(model, lr=lr)
+    raise UnboundLocalError(f"cannot access local variable 'optimizer' where it is not associated with a value (optim_name={optim_name!r})")
 
 
 class EMA:
@@ -249,7 +441,7 @@ class Accelerator:
         for o in objs:                      # main_train_masked.py:299-307: model, optimizer, dataloader, lr_scheduler
             if isinstance(o, UNet):
                 self._ckpt["model"] = o
-            elif isinstance(o, AdamW):
+            elif isinstance(o, _FlatOptimizer):      # AdamW | Adam | SGD
                 self._ckpt["optimizer"] = o
             elif isinstance(o, LambdaLR):
                 self._ckpt["lr_scheduler"] = o

@@ -49,7 +49,7 @@ class Trainer:
         return input[0]
 
     def _step(self, input):
-        """ms:139-172.  `accelerator.accumulate` decides whether this micro-step syncs; clip + AdamW + EMA are one fused
+        """ms:139-172.  `accelerator.accumulate` decides whether this micro-step syncs; clip + optimizer update + EMA are one fused
         launch inside the step and run only then.  The LR schedule advances only on a syncing step, and -- like accelerate's
         AcceleratedScheduler, which the reference's `prepare()` at main_train_masked.py:299 wraps it in -- `num_processes`
         times per optimizer step unless `split_batches`: schedules are written in single-process steps."""
