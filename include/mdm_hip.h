@@ -240,6 +240,28 @@ int mdm_groupnorm_bwd_add(int dtype, const void* src0, int C0, const void* src1,
                           const void* dy, const float* stats, void* dst0, const void* add0, void* dst1, const void* add1,
                           float* dgamma, float* dbeta, float* sum_img, int sum_ld, float* sum_all, float* ws,
                           const void* add0b, void* stream);
+
+/* Dropout on a GroupNorm output, fused into the kernels above (nn.Dropout between silu(norm2(.)) and conv2 of a ResidualBlock,
+ * unet6.py:354, 360): y = silu?(GN(x)) * keep * scale in the forward, dz = dy * keep * scale right behind the load of dy in the
+ * backward -- no extra pass over memory, no stored mask.  Element e = (n*P + p)*C + c has the global index g = base + e (`base`: the
+ * caller's running element count of the dropout sites before this one, a multiple of 8); its random word is the 16-bit lane g & 7 of
+ * Philox4x32-10(key = rng[0], counter = {g >> 3, rng[1] * 8 + 5}) (lane j = half j & 1 of 32-bit word j >> 1, low half first).
+ * ctl = {uint32 thr, float scale} in device memory: an element is kept iff its lane >= thr, kept values are multiplied by scale
+ * (thr = clamp(round(rate * 65536), 0, 65535), scale = 65536 / (65536 - thr)), dropped ones are exact zeros; thr == 0 (eval mode:
+ * {0, 1.0f}) draws nothing and gives the bits of the plain entry points.  rng = {seed, offset} as for mdm_rng_advance: forward and
+ * backward of one step must see the same offset.  One source only (C1 == 0).  Other arguments: mdm_groupnorm_fwd / _bwd_add. */
+int mdm_groupnorm_fwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1,
+                              int N, int P, int G, float eps, const float* gamma, const float* beta,
+                              int silu, void* y, float* stats, float* ws,
+                              const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream);
+int mdm_groupnorm_bwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1,
+                              int N, int P, int G, const float* gamma, const float* beta, int silu,
+                              const void* dy, const float* stats, void* dst0, const void* add0, void* dst1, const void* add1,
+                              float* dgamma, float* dbeta, float* sum_img, int sum_ld, float* sum_all, float* ws,
+                              const void* add0b, const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream);
+/* keep[i] = 1 / 0 for the n consecutive elements from global index `base` on (any base): the mask the two entry points above
+ * apply, for tests and debugging. */
+int mdm_dropout_mask(const uint64_t* rng, uint64_t base, const uint32_t* ctl, int64_t n, uint8_t* keep, void* stream);
 /* add0b (NULL = none): a SECOND tensor laid out like dst0 that is added too -- an activation with two forward consumers and a
  * residual join receives dst0 (accumulate) + the residual branch's dY + dx in one pass. */
 

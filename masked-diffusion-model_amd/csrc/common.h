@@ -145,6 +145,12 @@ struct Philox {
         return make_uint4(c0, c1, c2, c3);
     }
 };
+// rng = {seed, offset} in device memory (mdm_rng_advance bumps the offset in stream order); the stream id keeps the draws of one
+// offset apart (the ids are listed in sched.hip)
+__device__ __forceinline__ uint4 philox_at(const uint64_t* rng, int stream_id, uint64_t idx) {
+    Philox ph(rng[0]);
+    return ph(idx, rng[1] * 8 + (uint64_t)stream_id);
+}
 // [0,1) with 24 bits, like torch's float uniform
 __device__ __forceinline__ float u01(uint32_t x) { return (x >> 8) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float2 box_muller(uint32_t a, uint32_t b) {

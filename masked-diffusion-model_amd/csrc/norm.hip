@@ -138,238 +138,28 @@ __device__ __forceinline__ void group_sums(const float* csum, int VB, int lc0, i
     for (int w = 0; w < NQ; ++w) out[w] = a[w];
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void gn_fwd_kernel(const T* s0, int C0, const T* s1, int C1, int P, int G, int CBLK,
-                                                     float eps, const float* gamma, const float* beta, int silu, T* y,
-                                                     float* stats) {
-    const int C = C0 + C1, cpg = div_small(C, rcp_small(G));
-    const float inv_cpg = rcp_small(cpg);
-    const int VB = CBLK >> 3, PL = div_small(256, rcp_small(VB));
-    const int img = blockIdx.x, cb = blockIdx.y * CBLK;     // image fastest: the channel blocks of one image (they share 128-B lines) land on one XCD
-    const int t = threadIdx.x, lane = div_small(t, rcp_small(VB)), v = t - lane * VB, c = cb + v * 8;
-    const int ng = div_small(CBLK, inv_cpg), g0 = div_small(cb, inv_cpg);
-    const bool on = t < VB * PL && c < C;
-    __shared__ float gsum[2 * 64], gmean[64], grstd[64];
-    __shared__ float scratch[16 * (256 + 4)];
-    __shared__ float csum[16 * 8];
-    const int64_t base = (int64_t)img * P;
-    float part[16];                       // [0, 8): sums of (x - K), [8, 16): sums of (x - K)^2, per channel of this lane's vector
-#pragma unroll
-    for (int k = 0; k < 16; ++k) part[k] = 0.f;
-    if (on) {
-        float K[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) K[e] = gn_pivot(s0, s1, C0, C1, base, div_small(c + e, inv_cpg), cpg);
-        auto add = [&](const float8& x) {
-            float xv[8] = F8_TO_ARR(x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { float dlt = xv[e] - K[e]; part[e] += dlt; part[8 + e] = fmaf(dlt, dlt, part[8 + e]); }
-        };
-        int p = lane;
-        for (; p + 3 * PL < P; p += 4 * PL) {          // four independent 16-byte loads in flight per lane
-            float8 x0 = load8(src_ptr(s0, s1, C0, C1, base + p, c));
-            float8 x1 = load8(src_ptr(s0, s1, C0, C1, base + p + PL, c));
-            float8 x2 = load8(src_ptr(s0, s1, C0, C1, base + p + 2 * PL, c));
-            float8 x3 = load8(src_ptr(s0, s1, C0, C1, base + p + 3 * PL, c));
-            add(x0); add(x1); add(x2); add(x3);
-        }
-        for (; p < P; p += PL) add(load8(src_ptr(s0, s1, C0, C1, base + p, c)));
-    }
-    // FIXED summation order (no float atomics: the same input gives the same bits on every box): pixel lanes per channel
-    // through block_colsum, then one thread per group walks its channels in order
-    block_colsum<16, 256>(part, scratch, csum, t, VB, PL);          // csum[(q*8+e)*VB + v]
-    if (t < ng) group_sums<2>(csum, VB, t * cpg, cpg, 8, &gsum[2 * t]);
-    __syncthreads();
-    if (t < ng && (g0 + t) < G) {
-        const float inv_cnt = 1.f / ((float)cpg * (float)P);
-        float K = gn_pivot(s0, s1, C0, C1, base, g0 + t, cpg);
-        float md = gsum[2 * t] * inv_cnt;
-        float var = fmaxf(gsum[2 * t + 1] * inv_cnt - md * md, 0.f);
-        float mean = K + md, rstd = rsqrtf(var + eps);
-        gmean[t] = mean; grstd[t] = rstd;
-        stats[((int64_t)img * G + g0 + t) * 2] = mean;
-        stats[((int64_t)img * G + g0 + t) * 2 + 1] = rstd;
-    }
-    __syncthreads();
-    if (on) {
-        float m[8], a[8], bt[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int gl = div_small(c + e, inv_cpg) - g0;
-            m[e] = gmean[gl]; a[e] = grstd[gl] * gamma[c + e]; bt[e] = beta[c + e];
-        }
-        auto put = [&](int p, const float8& x) {
-            float xv[8] = F8_TO_ARR(x);
-            float o[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                o[e] = fmaf(xv[e] - m[e], a[e], bt[e]);     // (x - mean) stays exact
-                if (silu) o[e] = silu_f(o[e]);
-            }
-            float8 r = {make_float4(o[0], o[1], o[2], o[3]), make_float4(o[4], o[5], o[6], o[7])};
-            store8(y + (base + p) * C + c, r);
-        };
-        int p = lane;
-        for (; p + 3 * PL < P; p += 4 * PL) {
-            float8 x0 = load8(src_ptr(s0, s1, C0, C1, base + p, c));
-            float8 x1 = load8(src_ptr(s0, s1, C0, C1, base + p + PL, c));
-            float8 x2 = load8(src_ptr(s0, s1, C0, C1, base + p + 2 * PL, c));
-            float8 x3 = load8(src_ptr(s0, s1, C0, C1, base + p + 3 * PL, c));
-            put(p, x0); put(p + PL, x1); put(p + 2 * PL, x2); put(p + 3 * PL, x3);
-        }
-        for (; p < P; p += PL) put(p, load8(src_ptr(s0, s1, C0, C1, base + p, c)));
-    }
+// ---- dropout on the output of a residual block's norm2 (nn.Dropout between silu(norm2(.)) and conv2, unet6.py:354, 360), fused into
+// the standalone GroupNorm kernels: no extra pass over memory and no stored mask.  Element e = (n P + p) C + c of dropout site k has
+// the global index g = base_k + e (base_k: the host's running element count of the sites before it, a multiple of 8); its random word
+// is the 16-bit lane g & 7 of philox_at(rng, 5, g >> 3) (lane j = half j & 1 of 32-bit word j >> 1, low half first): ONE Philox call
+// per 16-byte bf16 vector.  Kept iff lane >= thr; kept values are multiplied by scale = 65536 / (65536 - thr), dropped ones are exact
+// zeros.  ctl = {uint32 thr, float scale} lives in device memory (eval mode rewrites it to {0, 1.0f} under plans and graphs that are
+// already recorded); thr == 0 skips the Philox work (a uniform branch).  The forward masks y in registers before the store, the
+// backward masks dy right behind its load -- from the same (seed, offset, g), so both see the same mask and none is stored.
+__device__ __forceinline__ uint4 drop_keep_bits(const uint64_t* rng, uint64_t g, uint32_t thr) {      // 0xffff per kept lane
+    const uint4 r = philox_at(rng, 5, g >> 3);
+    auto m = [&](uint32_t w) { return ((w & 0xffffu) >= thr ? 0x0000ffffu : 0u) | ((w >> 16) >= thr ? 0xffff0000u : 0u); };
+    return make_uint4(m(r.x), m(r.y), m(r.z), m(r.w));
 }
-
-// backward: dx = rstd*gamma*g - rstd*(s1 + xhat*s2)/cnt with g = dy * act'(xhat*gamma + beta),
-// s1 = sum(g*gamma), s2 = sum(g*gamma*xhat) per (image, group); dgamma += sum g*xhat, dbeta += sum g.
-// Every reduction has a FIXED order.  Inside the workgroup: block_colsum + one thread per group.  Across the images:
-// `part` != nullptr (the fp32 path) -> this workgroup's per-channel sums go to part[img][{dgamma, dbeta}][C] (plain stores)
-// and gn_param_reduce_kernel adds them up image by image behind this launch (it also forms sum_all from sum_img);
-// part == nullptr (bf16 large maps) -> one float atomic per channel per image, as the register-cached kernels do.
-template <typename T>
-__global__ __launch_bounds__(256) void gn_bwd_kernel(const T* s0, int C0, const T* s1, int C1, int P, int G, int CBLK,
-                                                     const float* gamma, const float* beta, int silu, const T* dy,
-                                                     const float* stats, T* d0, const T* add0, T* d1, const T* add1, const T* add0b,
-                                                     float* dgamma, float* dbeta, float* sum_img, int sum_ld, float* sum_all,
-                                                     float* part) {
-    const int C = C0 + C1, cpg = div_small(C, rcp_small(G));
-    const float inv_cpg = rcp_small(cpg);
-    const int VB = CBLK >> 3, PL = div_small(256, rcp_small(VB));
-    const int img = blockIdx.x, cb = blockIdx.y * CBLK;     // image fastest: the channel blocks of one image (they share 128-B lines) land on one XCD
-    const int t = threadIdx.x, lane = div_small(t, rcp_small(VB)), v = t - lane * VB, c = cb + v * 8;
-    const int ng = div_small(CBLK, inv_cpg), g0 = div_small(cb, inv_cpg);
-    const bool on = t < VB * PL && c < C;
-    __shared__ float gsum[2 * 64];
-    __shared__ float scratch[32 * (256 + 4)];
-    __shared__ float csum[32 * 8];
-    const int64_t base = (int64_t)img * P;
-    float ga[8], be[8], mean[8], rstd[8];
-    float acc[32];                        // per channel of this lane's vector: a1, a2, dgamma, dbeta
+__device__ __forceinline__ void drop_apply(float (&v)[8], const uint4& k, float scale) {
+    const uint32_t kw[4] = {k.x, k.y, k.z, k.w};
 #pragma unroll
-    for (int k = 0; k < 32; ++k) acc[k] = 0.f;
-    if (on) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int grp = div_small(c + e, inv_cpg);
-            ga[e] = gamma[c + e]; be[e] = beta[c + e];
-            mean[e] = stats[((int64_t)img * G + grp) * 2]; rstd[e] = stats[((int64_t)img * G + grp) * 2 + 1];
-        }
-        auto add = [&](const float8& x, const float8& d) {
-            float xv[8] = F8_TO_ARR(x);
-            float dv[8] = F8_TO_ARR(d);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float xh = (xv[e] - mean[e]) * rstd[e];
-                float gz = dv[e];
-                if (silu) gz *= silu_grad_f(fmaf(xh, ga[e], be[e]));
-                acc[16 + e] = fmaf(gz, xh, acc[16 + e]); acc[24 + e] += gz;
-                float gg = gz * ga[e];
-                acc[e] += gg; acc[8 + e] = fmaf(gg, xh, acc[8 + e]);
-            }
-        };
-        int p = lane;
-        for (; p + PL < P; p += 2 * PL) {
-            float8 x0 = load8(src_ptr(s0, s1, C0, C1, base + p, c));
-            float8 e0 = load8(dy + (base + p) * C + c);
-            float8 x1 = load8(src_ptr(s0, s1, C0, C1, base + p + PL, c));
-            float8 e1 = load8(dy + (base + p + PL) * C + c);
-            add(x0, e0); add(x1, e1);
-        }
-        for (; p < P; p += PL) add(load8(src_ptr(s0, s1, C0, C1, base + p, c)), load8(dy + (base + p) * C + c));
-    }
-    block_colsum<32, 256>(acc, scratch, csum, t, VB, PL);          // csum[(q*8+e)*VB + v], q = {a1, a2, dgamma, dbeta}
-    if (t < ng) group_sums<2>(csum, VB, t * cpg, cpg, 8, &gsum[2 * t]);
-    if (t < CBLK && cb + t < C) {            // this workgroup is the only one that holds (image, channel)
-        const float dgv = csum[(16 + (t & 7)) * VB + (t >> 3)], dbv = csum[(24 + (t & 7)) * VB + (t >> 3)];
-        if (part) {
-            part[((int64_t)img * 3) * C + cb + t] = dgv;
-            part[((int64_t)img * 3 + 1) * C + cb + t] = dbv;
-        } else {
-            atomicAdd(&dgamma[cb + t], dgv);
-            atomicAdd(&dbeta[cb + t], dbv);
-        }
-    }
-    __syncthreads();
-    float k1[8], k2[8], ag[8];
-    if (on) {
-        const float inv_cnt = 1.f / ((float)cpg * (float)P);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int gl = div_small(c + e, inv_cpg) - g0;
-            k1[e] = rstd[e] * gsum[2 * gl] * inv_cnt;
-            k2[e] = rstd[e] * gsum[2 * gl + 1] * inv_cnt;
-            ag[e] = rstd[e] * ga[e];
-        }
-    }
-    float sx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // column sums of dx (bias / time-embedding gradient of the producer conv)
-    if (on) {
-        T* dst; const T* addp; int cc, CS;           // addp: a tensor laid out like dst whose values are added (dst itself = accumulate)
-        if (c < C0) { dst = d0; addp = add0; cc = c; CS = C0; } else { dst = d1; addp = add1; cc = c - C0; CS = C1; }
-        const T* addq = c < C0 ? add0b : nullptr;    // a second addend for source 0 (accumulate AND a residual-branch gradient)
-        auto put = [&](int p, const float8& x, const float8& d) {
-            float xv[8] = F8_TO_ARR(x);
-            float dv[8] = F8_TO_ARR(d);
-            float o[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float xh = (xv[e] - mean[e]) * rstd[e];
-                float gz = dv[e];
-                if (silu) gz *= silu_grad_f(fmaf(xh, ga[e], be[e]));
-                o[e] = ag[e] * gz - fmaf(xh, k2[e], k1[e]);
-                sx[e] += o[e];
-            }
-            T* q = dst + (base + p) * CS + cc;
-            if (addp) {
-                float8 old = load8(addp + (base + p) * CS + cc);
-                float ov[8] = F8_TO_ARR(old);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] += ov[e];
-            }
-            if (addq) {
-                float8 old2 = load8(addq + (base + p) * CS + cc);
-                float ov2[8] = F8_TO_ARR(old2);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[e] += ov2[e];
-            }
-            float8 r = {make_float4(o[0], o[1], o[2], o[3]), make_float4(o[4], o[5], o[6], o[7])};
-            store8(q, r);
-        };
-        int p = lane;
-        for (; p + PL < P; p += 2 * PL) {
-            float8 x0 = load8(src_ptr(s0, s1, C0, C1, base + p, c));
-            float8 e0 = load8(dy + (base + p) * C + c);
-            float8 x1 = load8(src_ptr(s0, s1, C0, C1, base + p + PL, c));
-            float8 e1 = load8(dy + (base + p + PL) * C + c);
-            put(p, x0, e0); put(p + PL, x1, e1);
-        }
-        for (; p < P; p += PL) put(p, load8(src_ptr(s0, s1, C0, C1, base + p, c)), load8(dy + (base + p) * C + c));
-    }
-    if (sum_img || sum_all) {               // uniform
-        block_colsum<8, 256>(sx, scratch, csum, t, VB, PL);
-        if (t < CBLK && cb + t < C) {
-            const float r = csum[(t & 7) * VB + (t >> 3)];
-            if (sum_img) sum_img[(int64_t)img * sum_ld + cb + t] = r;              // one workgroup owns (image, channel)
-            if (part) part[((int64_t)img * 3 + 2) * C + cb + t] = r;              // fixed-order mode: the reduce kernel adds the images up
-            else if (sum_all) atomicAdd(&sum_all[cb + t], r);
-        }
-    }
+    for (int e = 0; e < 8; ++e) v[e] = ((kw[e >> 1] >> ((e & 1) * 16)) & 1u) ? v[e] * scale : 0.f;
 }
-
-// second stage of the fixed-order GroupNorm backward over part[img][{dgamma, dbeta, colsum(dx)}][C]: dgamma[c] += sum_img
-// part[img][0][c], dbeta[c] += sum_img part[img][1][c], sum_all[c] += sum_img part[img][2][c], images in ascending order
-// (one thread per channel)
-__global__ __launch_bounds__(256) void gn_param_reduce_kernel(const float* part, int N, int C, float* dgamma, float* dbeta, float* sum_all) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= C) return;
-    float a = 0.f, b = 0.f, s = 0.f;
-    for (int n = 0; n < N; ++n) {
-        a += part[((int64_t)n * 3) * C + c];
-        b += part[((int64_t)n * 3 + 1) * C + c];
-        if (sum_all) s += part[((int64_t)n * 3 + 2) * C + c];
-    }
-    dgamma[c] += a; dbeta[c] += b;
-    if (sum_all) sum_all[c] += s;
+__device__ __forceinline__ void drop_apply(float8& d, const uint4& k, float scale) {
+    float v[8] = F8_TO_ARR(d);
+    drop_apply(v, k, scale);
+    d.lo = make_float4(v[0], v[1], v[2], v[3]); d.hi = make_float4(v[4], v[5], v[6], v[7]);
 }
 
 // ---- register-cached variants (bf16): a lane's share of the slice is at most NP 16-byte vectors per tensor,
@@ -419,316 +209,61 @@ template <> struct RegVec<float> {
     static __device__ __forceinline__ float8 ld(const float* p) { return load8(p); }
     static __device__ __forceinline__ float8 unpack(const float8& r) { return r; }
 };
-template <int NP, int MODE, int NT = 256, typename T = bf16_t>
-__global__ __launch_bounds__(NT) void gn_fwd_reg_kernel(const T* s0, int C0, const T* s1, int C1, int P, int G, int CBLK,
-                                                         float eps, const float* gamma, const float* beta, int silu, T* y,
-                                                         float* stats, float* ws) {
-    constexpr int CS_PITCH = NT + 4;
-    const int C = C0 + C1, cpg = div_small(C, rcp_small(G));
-    const float inv_cpg = rcp_small(cpg);
-    const int VB = CBLK >> 3, PL = div_small(NT, rcp_small(VB));
-    const int img = blockIdx.x, cb = blockIdx.y * CBLK;     // image fastest: the channel blocks of one image (they share 128-B lines) land on one XCD
-    const int t = threadIdx.x, lane = div_small(t, rcp_small(VB)), v = t - lane * VB, c = cb + v * 8;
-    const int ng = div_small(CBLK, inv_cpg), g0 = div_small(cb, inv_cpg);
-    const bool on = t < VB * PL && c < C;
-    const int chunks = gridDim.z, chunk = blockIdx.z;
-    const int plen = chunks == 1 ? P : (P + chunks - 1) / chunks, pbeg = chunk * plen, pend = min(P, pbeg + plen);
-    __shared__ float scratch[16 * CS_PITCH];
-    __shared__ float csum[16 * 8];
-    __shared__ float gsum[2 * 64], gmean[64], grstd[64], gpiv[64];
-    const int64_t base = (int64_t)img * P;
-    if (t < 2 * ng) {
-        float a = 0.f;
-        if (MODE == 2)
-            for (int ch = 0; ch < chunks; ++ch) a += ws[(((int64_t)img * chunks + ch) * G + g0 + (t >> 1)) * 2 + (t & 1)];
-        gsum[t] = a;
+
+// ---- the four standalone kernels (gn_fwd_kernel, gn_bwd_kernel, gn_fwd_reg_kernel, gn_bwd_reg_kernel), once as they are and
+// once with dropout (gn_*_kernel_drop): gn_kernels.inc
+#define GN_DROP 0
+#define GN_K(name) name
+#define GN_DROP_PARAMS
+#define GN_LOAD_DY(pix) load8(dy + (pix) * C + c)
+#define GN_DZ(v) v
+#include "gn_kernels.inc"
+#undef GN_DROP
+#undef GN_K
+#undef GN_DROP_PARAMS
+#undef GN_LOAD_DY
+#undef GN_DZ
+#define GN_DROP 1
+#define GN_K(name) name##_drop
+#define GN_DROP_PARAMS , const uint64_t* rng, uint64_t dbase, const uint32_t* ctl
+#define GN_LOAD_DY(pix) load_dy(pix)
+#define GN_DZ(v) ((v) * dscale)
+#include "gn_kernels.inc"
+#undef GN_DROP
+#undef GN_K
+#undef GN_DROP_PARAMS
+#undef GN_LOAD_DY
+#undef GN_DZ
+
+// second stage of the fixed-order GroupNorm backward over part[img][{dgamma, dbeta, colsum(dx)}][C]: dgamma[c] += sum_img
+// part[img][0][c], dbeta[c] += sum_img part[img][1][c], sum_all[c] += sum_img part[img][2][c], images in ascending order
+// (one thread per channel)
+__global__ __launch_bounds__(256) void gn_param_reduce_kernel(const float* part, int N, int C, float* dgamma, float* dbeta, float* sum_all) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float a = 0.f, b = 0.f, s = 0.f;
+    for (int n = 0; n < N; ++n) {
+        a += part[((int64_t)n * 3) * C + c];
+        b += part[((int64_t)n * 3 + 1) * C + c];
+        if (sum_all) s += part[((int64_t)n * 3 + 2) * C + c];
     }
-    // one pivot load per group (in flight together with the slice loads below), shared through LDS: every thread
-    // loading its 8 pivots itself and the statistics thread loading its pivot AGAIN after the reduction put a second
-    // memory round trip on the critical path of a ~3 us kernel
-    if (t < ng && g0 + t < G) gpiv[t] = gn_pivot(s0, s1, C0, C1, base, g0 + t, cpg);
-    typename RegVec<T>::type cx[NP];
-    float part[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) part[k] = 0.f;
-    if (on) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            int p = pbeg + lane + i * PL;
-            cx[i] = p < pend ? RegVec<T>::ld(src_ptr(s0, s1, C0, C1, base + p, c)) : RegVec<T>::zero();
-        }
-    }
-    __syncthreads();
-    if (MODE != 2 && on) {
-        float K[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) K[e] = gpiv[div_small(c + e, inv_cpg) - g0];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            if (pbeg + lane + i * PL < pend) {
-                float8 x = RegVec<T>::unpack(cx[i]);
-                float xv[8] = F8_TO_ARR(x);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { float dlt = xv[e] - K[e]; part[e] += dlt; part[8 + e] = fmaf(dlt, dlt, part[8 + e]); }
-            }
-        }
-    }
-    if (MODE != 2) {
-        block_colsum<16, NT, sizeof(T) == 2>(part, scratch, csum, t, VB, PL);      // csum[(q*8+e)*VB + v]
-        // one thread per group walks its channels in order (it was an LDS float atomic per channel: arrival order)
-        if (t < ng) {
-            float gv[2];
-            group_sums<2>(csum, VB, t * cpg, cpg, 8, gv);
-            gsum[2 * t] += gv[0]; gsum[2 * t + 1] += gv[1];
-        }
-    }
-    __syncthreads();
-    if (MODE == 1) {
-        if (t < 2 * ng && g0 + (t >> 1) < G) ws[(((int64_t)img * chunks + chunk) * G + g0 + (t >> 1)) * 2 + (t & 1)] = gsum[t];
-        return;
-    }
-    if (t < ng && (g0 + t) < G) {
-        const float inv_cnt = 1.f / ((float)cpg * (float)P);
-        float K = gpiv[t];
-        float md = gsum[2 * t] * inv_cnt;
-        float var = fmaxf(gsum[2 * t + 1] * inv_cnt - md * md, 0.f);
-        float mean = K + md, rstd = rsqrtf(var + eps);
-        gmean[t] = mean; grstd[t] = rstd;
-        if (chunk == 0) {
-            stats[((int64_t)img * G + g0 + t) * 2] = mean;
-            stats[((int64_t)img * G + g0 + t) * 2 + 1] = rstd;
-        }
-    }
-    __syncthreads();
-    if (on) {
-        float m[8], a[8], bt[8];
-        const float4 g_lo = *reinterpret_cast<const float4*>(gamma + c), g_hi = *reinterpret_cast<const float4*>(gamma + c + 4);
-        const float4 b_lo = *reinterpret_cast<const float4*>(beta + c), b_hi = *reinterpret_cast<const float4*>(beta + c + 4);
-        const float gv[8] = {g_lo.x, g_lo.y, g_lo.z, g_lo.w, g_hi.x, g_hi.y, g_hi.z, g_hi.w};
-        const float bv[8] = {b_lo.x, b_lo.y, b_lo.z, b_lo.w, b_hi.x, b_hi.y, b_hi.z, b_hi.w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int gl = div_small(c + e, inv_cpg) - g0;
-            m[e] = gmean[gl]; a[e] = grstd[gl] * gv[e]; bt[e] = bv[e];
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            int p = pbeg + lane + i * PL;
-            if (p < pend) {
-                float8 x = RegVec<T>::unpack(cx[i]);
-                float xv[8] = F8_TO_ARR(x);
-                float o[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    o[e] = fmaf(xv[e] - m[e], a[e], bt[e]);
-                    if (silu) o[e] = silu_f(o[e]);
-                }
-                float8 r = {make_float4(o[0], o[1], o[2], o[3]), make_float4(o[4], o[5], o[6], o[7])};
-                store8(y + (base + p) * C + c, r);
-            }
-        }
-    }
+    dgamma[c] += a; dbeta[c] += b;
+    if (sum_all) sum_all[c] += s;
 }
 
-template <int NP, int MODE, int NT = 256>
-__global__ __launch_bounds__(NT) void gn_bwd_reg_kernel(const bf16_t* s0, int C0, const bf16_t* s1, int C1, int P, int G, int CBLK,
-                                                         const float* gamma, const float* beta, int silu, const bf16_t* dy,
-                                                         const float* stats, bf16_t* d0, const bf16_t* add0, bf16_t* d1, const bf16_t* add1, const bf16_t* add0b,
-                                                         float* dgamma, float* dbeta, float* sum_img, int sum_ld, float* sum_all,
-                                                         float* ws) {
-    constexpr int CS_PITCH = NT + 4;
-    const int C = C0 + C1, cpg = div_small(C, rcp_small(G));
-    const float inv_cpg = rcp_small(cpg);
-    const int VB = CBLK >> 3, PL = div_small(NT, rcp_small(VB));
-    const int img = blockIdx.x, cb = blockIdx.y * CBLK;     // image fastest: the channel blocks of one image (they share 128-B lines) land on one XCD
-    const int t = threadIdx.x, lane = div_small(t, rcp_small(VB)), v = t - lane * VB, c = cb + v * 8;
-    const int ng = div_small(CBLK, inv_cpg), g0 = div_small(cb, inv_cpg);
-    const bool on = t < VB * PL && c < C;
-    const int chunks = gridDim.z, chunk = blockIdx.z;
-    const int plen = chunks == 1 ? P : (P + chunks - 1) / chunks, pbeg = chunk * plen, pend = min(P, pbeg + plen);
-    __shared__ float scratch[16 * CS_PITCH];
-    __shared__ float csum[32 * 8];
-    __shared__ float gsum[2 * 64], sgam[64];
-    MDM_T(const unsigned long long ts0 = nstamp_now();)
-    if (t >= 128 && t < 128 + CBLK && cb + t - 128 < C) sgam[t - 128] = gamma[cb + t - 128];     // for the group sums behind the column sums
-    if (t < 2 * ng) {
-        float a = 0.f;
-        if (MODE == 2)
-            for (int ch = 0; ch < chunks; ++ch) a += ws[(((int64_t)img * chunks + ch) * G + g0 + (t >> 1)) * 2 + (t & 1)];
-        gsum[t] = a;
+
+// keep flags of n consecutive elements from global index `base` on (tests, debugging): one thread per 8-element vector
+__global__ __launch_bounds__(256) void dropout_mask_kernel(const uint64_t* rng, uint64_t base, const uint32_t* ctl, int64_t n, uint8_t* keep) {
+    const uint32_t thr = ctl[0];
+    const uint64_t v = (base >> 3) + (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v * 8 >= base + (uint64_t)n) return;
+    const uint4 k = thr ? drop_keep_bits(rng, v * 8, thr) : make_uint4(~0u, ~0u, ~0u, ~0u);
+    const uint32_t kw[4] = {k.x, k.y, k.z, k.w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const uint64_t g = v * 8 + j;
+        if (g >= base && g < base + (uint64_t)n) keep[g - base] = (kw[j >> 1] >> ((j & 1) * 16)) & 1u;
     }
-    const int64_t base = (int64_t)img * P;
-    uint4 cx[NP], cd[NP];
-    // the tensors ADDED to dx (accumulated gradient / residual branch) are fetched with x and dy, not behind the reduction:
-    // a second exposed memory round trip on a kernel that is one round trip + a reduction long
-    constexpr bool PRE_ADD = NP <= 4;
-    uint4 cadd[PRE_ADD ? NP : 1], caddq[PRE_ADD ? NP : 1];
-    // single-launch mode with a small slice: dy * silu'(..) is kept in fp32 registers for the apply pass instead of being
-    // recomputed (exp + rcp per element: the large-map kernels are VALU-bound, 1 wave per SIMD)
-    constexpr bool CACHE = MODE == 0 && NP <= 8;
-    float gzc[CACHE ? NP : 1][8];
-    float ga[8], be[8], mean[8], rstd[8], nmr[8], za[8], zb[8];
-    float part[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) part[k] = 0.f;
-    MDM_T(unsigned long long ts1 = 0;)
-    if (on) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            int p = pbeg + lane + i * PL;
-            bool ok = p < pend;
-            cx[i] = ok ? *reinterpret_cast<const uint4*>(src_ptr(s0, s1, C0, C1, base + p, c)) : make_uint4(0, 0, 0, 0);
-            cd[i] = ok ? *reinterpret_cast<const uint4*>(dy + (base + p) * C + c) : make_uint4(0, 0, 0, 0);
-            if (PRE_ADD) {
-                const bf16_t* ap = c < C0 ? add0 : add1;
-                const int cc2 = c < C0 ? c : c - C0, CS2 = c < C0 ? C0 : C1;
-                cadd[i] = (ok && ap) ? *reinterpret_cast<const uint4*>(ap + (base + p) * CS2 + cc2) : make_uint4(0, 0, 0, 0);
-                caddq[i] = (ok && add0b && c < C0) ? *reinterpret_cast<const uint4*>(add0b + (base + p) * C0 + c) : make_uint4(0, 0, 0, 0);
-            }
-        }
-        {
-            const float4 g_lo = *reinterpret_cast<const float4*>(gamma + c), g_hi = *reinterpret_cast<const float4*>(gamma + c + 4);
-            const float4 b_lo = *reinterpret_cast<const float4*>(beta + c), b_hi = *reinterpret_cast<const float4*>(beta + c + 4);
-            ga[0] = g_lo.x; ga[1] = g_lo.y; ga[2] = g_lo.z; ga[3] = g_lo.w; ga[4] = g_hi.x; ga[5] = g_hi.y; ga[6] = g_hi.z; ga[7] = g_hi.w;
-            be[0] = b_lo.x; be[1] = b_lo.y; be[2] = b_lo.z; be[3] = b_lo.w; be[4] = b_hi.x; be[5] = b_hi.y; be[6] = b_hi.z; be[7] = b_hi.w;
-            // 8 consecutive channels touch at most 8/cpg + 1 groups; load each group's pair once
-            const int gA = div_small(c, inv_cpg);
-            float2 st_prev = *reinterpret_cast<const float2*>(stats + ((int64_t)img * G + gA) * 2);
-            int g_prev = gA;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int grp = div_small(c + e, inv_cpg);
-                if (grp != g_prev) { st_prev = *reinterpret_cast<const float2*>(stats + ((int64_t)img * G + grp) * 2); g_prev = grp; }
-                mean[e] = st_prev.x; rstd[e] = st_prev.y;
-            }
-        }
-        MDM_T(ts1 = nstamp_now();)
-        // (round 4: these kernels are VALU-bound -- ~60 vector instructions per element at two waves per SIMD, finding 48.  The
-        // normalisation and the affine map are one fma each from per-channel constants, and only TWO sums are kept per channel:
-        // sum(gz xh) = dgamma and sum(gz) = dbeta; the group sums of gz gamma and gz gamma xh are gamma-weighted sums of those
-        // two over the group's channels, taken once behind the column sums: 16 quantities through block_colsum instead of 32.)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            nmr[e] = -mean[e] * rstd[e];                     // xh = fma(x, rstd, nmr)
-            za[e] = rstd[e] * ga[e]; zb[e] = fmaf(nmr[e], ga[e], be[e]);      // gamma xh + beta = fma(x, za, zb)
-        }
-        if (MODE != 2) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            if (pbeg + lane + i * PL < pend) {
-                float8 x = unpack8(cx[i]), d = unpack8(cd[i]);
-                float xv[8] = F8_TO_ARR(x);
-                float dv[8] = F8_TO_ARR(d);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float xh = fmaf(xv[e], rstd[e], nmr[e]);
-                    float gz = dv[e];
-                    if (silu) gz *= silu_grad_f(fmaf(xv[e], za[e], zb[e]));
-                    if (CACHE) gzc[CACHE ? i : 0][e] = gz;
-                    part[e] = fmaf(gz, xh, part[e]); part[8 + e] += gz;                      // dgamma, dbeta
-                }
-            }
-        }
-        }
-    }
-    if (MODE != 2) {
-        block_colsum<16, NT>(part, scratch, csum, t, VB, PL);      // csum[(q*8+e)*VB + v], q = {dgamma, dbeta}
-        if (t < CBLK && cb + t < C) {            // across images: one float atomic per (image, channel) (bf16 path)
-            const int vv = t >> 3, e = t & 7;
-            atomicAdd(&dgamma[cb + t], csum[e * VB + vv]);
-            atomicAdd(&dbeta[cb + t], csum[(8 + e) * VB + vv]);
-        }
-        if (t >= 64 && t < 64 + ng) {            // inside the workgroup: fixed order (a second wave, next to the atomics above)
-            const int gi = t - 64;
-            float a1 = 0.f, a2 = 0.f;            // sum over the group's channels of gamma dbeta / gamma dgamma, in channel order
-            for (int lc = gi * cpg; lc < (gi + 1) * cpg; ++lc) {
-                const float gm = sgam[lc];
-                a1 = fmaf(gm, csum[(8 + (lc & 7)) * VB + (lc >> 3)], a1);
-                a2 = fmaf(gm, csum[(lc & 7) * VB + (lc >> 3)], a2);
-            }
-            gsum[2 * gi] += a1; gsum[2 * gi + 1] += a2;
-        }
-    }
-    MDM_T(const unsigned long long ts2 = nstamp_now();)
-    __syncthreads();
-    if (MODE == 1) {
-        if (t < 2 * ng && g0 + (t >> 1) < G) ws[(((int64_t)img * chunks + chunk) * G + g0 + (t >> 1)) * 2 + (t & 1)] = gsum[t];
-        if (sum_img && chunk == 0 && t < CBLK && cb + t < C) sum_img[(int64_t)img * sum_ld + cb + t] = 0.f;
-        return;
-    }
-    MDM_T(const unsigned long long ts3 = nstamp_now(); const unsigned long long ts4 = ts3;)
-    float k1[8], k2[8], ag[8];              // dx = ag gz - (k2 xh + k1) = fma(ag, gz, -fma(x, k2 rstd, k2 nmr + k1))
-    if (on) {
-        const float inv_cnt = 1.f / ((float)cpg * (float)P);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int gl = div_small(c + e, inv_cpg) - g0;
-            const float q1 = rstd[e] * gsum[2 * gl] * inv_cnt, q2 = rstd[e] * gsum[2 * gl + 1] * inv_cnt;
-            k1[e] = fmaf(q2, nmr[e], q1);
-            k2[e] = q2 * rstd[e];
-            ag[e] = za[e];
-        }
-    }
-    float sx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (on) {
-        bf16_t* dst; const bf16_t* addp; int cc, CS;
-        if (c < C0) { dst = d0; addp = add0; cc = c; CS = C0; } else { dst = d1; addp = add1; cc = c - C0; CS = C1; }
-        const bf16_t* addq = c < C0 ? add0b : nullptr;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            int p = pbeg + lane + i * PL;
-            if (p < pend) {
-                float8 x = unpack8(cx[i]), d = unpack8(cd[i]);
-                float xv[8] = F8_TO_ARR(x);
-                float dv[8] = F8_TO_ARR(d);
-                float o[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float gz;
-                    if (CACHE) gz = gzc[CACHE ? i : 0][e];
-                    else { gz = dv[e]; if (silu) gz *= silu_grad_f(fmaf(xv[e], za[e], zb[e])); }
-                    o[e] = fmaf(ag[e], gz, -fmaf(xv[e], k2[e], k1[e]));
-                    sx[e] += o[e];
-                }
-                bf16_t* q = dst + (base + p) * CS + cc;
-                if (addp) {
-                    float8 old = PRE_ADD ? unpack8(cadd[PRE_ADD ? i : 0]) : load8(addp + (base + p) * CS + cc);
-                    float ov[8] = F8_TO_ARR(old);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] += ov[e];
-                }
-                if (addq) {
-                    float8 old2 = PRE_ADD ? unpack8(caddq[PRE_ADD ? i : 0]) : load8(addq + (base + p) * CS + cc);
-                    float ov2[8] = F8_TO_ARR(old2);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] += ov2[e];
-                }
-                float8 r = {make_float4(o[0], o[1], o[2], o[3]), make_float4(o[4], o[5], o[6], o[7])};
-                store8(q, r);
-            }
-        }
-    }
-    if (sum_img || sum_all) {            // uniform
-        block_colsum<8, NT>(sx, scratch, csum, t, VB, PL);
-        if (t < CBLK && cb + t < C) {
-            const float r = csum[(t & 7) * VB + (t >> 3)];
-            if (sum_img) {
-                if (MODE == 0) sum_img[(int64_t)img * sum_ld + cb + t] = r;         // single writer
-                else atomicAdd(&sum_img[(int64_t)img * sum_ld + cb + t], r);        // zeroed by the MODE 1 launch
-            }
-            if (sum_all) atomicAdd(&sum_all[cb + t], r);
-        }
-    }
-#ifdef MDM_STAMP
-    {
-        const unsigned long long ts5 = nstamp_now();
-        const unsigned widx = (blockIdx.y * gridDim.x + blockIdx.x) * 4 + (t >> 6);
-        if ((t & 63) == 0 && widx < 4096) {
-            unsigned long long* r = g_nstamp_buf + widx * 16;
-            r[0] = 1; r[1] = ts1 - ts0; r[2] = ts2 - ts1; r[3] = ts3 - ts2; r[4] = ts4 - ts3; r[5] = ts5 - ts4; r[6] = ts0; r[7] = ts5;
-        }
-    }
-#endif
 }
 
 // ---- row softmax: one wave per row
@@ -941,9 +476,12 @@ static int gn_cblk(int C, int G, int N, int P) {
 }
 // (A pixel-chunked statistics + apply pair of launches -- MODE 1 / 2 of the register kernels -- was measured no faster
 // than the single launch at cfg2: 13.4 vs 13.7 us forward, 25.3 vs 24.1 us backward on 32x32x128; it is not dispatched.)
-extern "C" int mdm_groupnorm_fwd(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                 float eps, const float* gamma, const float* beta, int silu, void* y, float* stats,
-                                 float* ws, void* stream) {
+// DROP: the dropout variants of the same kernels (mdm_groupnorm_fwd_dropout); one route choice for both, so a dropout site runs
+// on the kernel its plain GroupNorm runs on
+template <bool DROP>
+static int gn_fwd_dispatch(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
+                           float eps, const float* gamma, const float* beta, int silu, void* y, float* stats,
+                           float* ws, const uint64_t* rng, uint64_t dbase, const uint32_t* ctl, void* stream) {
     if (int rc = gn_check(C0, C1, G, N, P)) return rc;
     const int C = C0 + C1;
     int cblk = gn_cblk(C, G, N, P);
@@ -957,24 +495,65 @@ extern "C" int mdm_groupnorm_fwd(int dtype, const void* src0, int C0, const void
     dim3 grid(N, cdiv(C, cblk));
     const int np = cdiv(P, 256 / (cblk / 8));          // 16-byte vectors per lane of a 256-thread workgroup
     if (dtype == MDM_BF16 && np <= 16) {
-#define GN_FWD_REG(NPV, NT) hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0, \
-                                               (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws)
+#define GN_FWD_REG(NPV, NT)                                                                                                                          \
+    do {                                                                                                                                             \
+        if constexpr (DROP)                                                                                                                          \
+            hipLaunchKernelGGL((gn_fwd_reg_kernel_drop<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0,                \
+                               (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws, rng, dbase, ctl);                 \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0,                     \
+                               (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws);                                  \
+    } while (0)
         if (np <= 1) GN_FWD_REG(1, 256); else if (np <= 2) GN_FWD_REG(2, 256); else if (np <= 4) GN_FWD_REG(2, 512);
         else if (np <= 8) GN_FWD_REG(4, 512); else GN_FWD_REG(8, 512);
 #undef GN_FWD_REG
         return launch_status("groupnorm_fwd");
     }
     if (dtype == MDM_F32 && np <= 16) {            // the same kernels on fp32 storage: one read of the slice instead of two
-#define GN_FWD_REG(NPV, NT) hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT, float>), grid, dim3(NT), 0, (hipStream_t)stream, (const float*)src0, C0, \
-                                               (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws)
+#define GN_FWD_REG(NPV, NT)                                                                                                                          \
+    do {                                                                                                                                             \
+        if constexpr (DROP)                                                                                                                          \
+            hipLaunchKernelGGL((gn_fwd_reg_kernel_drop<NPV, 0, NT, float>), grid, dim3(NT), 0, (hipStream_t)stream, (const float*)src0, C0,          \
+                               (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws, rng, dbase, ctl);                   \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT, float>), grid, dim3(NT), 0, (hipStream_t)stream, (const float*)src0, C0,               \
+                               (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws);                                    \
+    } while (0)
         if (np <= 1) GN_FWD_REG(1, 256); else if (np <= 2) GN_FWD_REG(2, 256); else if (np <= 4) GN_FWD_REG(2, 512);
         else if (np <= 8) GN_FWD_REG(4, 512); else GN_FWD_REG(8, 512);
 #undef GN_FWD_REG
         return launch_status("groupnorm_fwd");
     }
-    DISPATCH_T(dtype, hipLaunchKernelGGL((gn_fwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
-                                         (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats));
+    if constexpr (DROP)
+        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_fwd_kernel_drop<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
+                                             (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats, rng, dbase, ctl));
+    else
+        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_fwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
+                                             (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats));
     return launch_status("groupnorm_fwd");
+}
+extern "C" int mdm_groupnorm_fwd(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
+                                 float eps, const float* gamma, const float* beta, int silu, void* y, float* stats,
+                                 float* ws, void* stream) {
+    return gn_fwd_dispatch<false>(dtype, src0, C0, src1, C1, N, P, G, eps, gamma, beta, silu, y, stats, ws, nullptr, 0, nullptr, stream);
+}
+static int drop_check(const char* what, int C1, const uint64_t* rng, uint64_t base, const uint32_t* ctl) {
+    MDM_REQUIRE(C1 == 0, "%s: a dropout site has one source (C1=%d)", what, C1);
+    MDM_REQUIRE(rng && ctl, "%s: null rng / ctl", what);
+    MDM_REQUIRE(base % 8 == 0, "%s: base must be a multiple of 8", what);
+    return 0;
+}
+extern "C" int mdm_groupnorm_fwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
+                                         float eps, const float* gamma, const float* beta, int silu, void* y, float* stats,
+                                         float* ws, const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream) {
+    if (int rc = drop_check("groupnorm_fwd_dropout", C1, rng, base, ctl)) return rc;
+    return gn_fwd_dispatch<true>(dtype, src0, C0, src1, C1, N, P, G, eps, gamma, beta, silu, y, stats, ws, rng, base, ctl, stream);
+}
+extern "C" int mdm_dropout_mask(const uint64_t* rng, uint64_t base, const uint32_t* ctl, int64_t n, uint8_t* keep, void* stream) {
+    MDM_REQUIRE(rng && ctl && keep && n > 0 && n < (1ll << 36), "dropout_mask: bad arguments");
+    const int64_t vecs = (int64_t)(((base + (uint64_t)n + 7) >> 3) - (base >> 3));
+    hipLaunchKernelGGL(dropout_mask_kernel, dim3(cdiv(vecs, 256)), dim3(256), 0, (hipStream_t)stream, rng, base, ctl, n, keep);
+    return launch_status("dropout_mask");
 }
 
 // floats of `ws` the backward entry points write for this problem (0: none needed).  The C ABI carries no buffer sizes, so a caller
@@ -983,10 +562,12 @@ extern "C" int64_t mdm_groupnorm_bwd_ws_floats(int dtype, int N, int C) {
     return dtype == MDM_F32 ? (int64_t)3 * N * C : 0;
 }
 
-extern "C" int mdm_groupnorm_bwd_add(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                     const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
-                                     void* dst0, const void* add0, void* dst1, const void* add1, float* dgamma, float* dbeta,
-                                     float* sum_img, int sum_ld, float* sum_all, float* ws, const void* add0b, void* stream) {
+template <bool DROP>
+static int gn_bwd_dispatch(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
+                           const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
+                           void* dst0, const void* add0, void* dst1, const void* add1, float* dgamma, float* dbeta,
+                           float* sum_img, int sum_ld, float* sum_all, float* ws, const void* add0b,
+                           const uint64_t* rng, uint64_t dbase, const uint32_t* ctl, void* stream) {
     if (int rc = gn_check(C0, C1, G, N, P)) return rc;
     const int C = C0 + C1, cblk = gn_cblk(C, G, N, P);
     MDM_REQUIRE(cblk <= 64 && cblk / (C / G) <= 64, "groupnorm: unsupported channel/group combination C=%d G=%d", C, G);
@@ -994,24 +575,52 @@ extern "C" int mdm_groupnorm_bwd_add(int dtype, const void* src0, int C0, const 
     dim3 grid(N, cdiv(C, cblk));
     const int np = cdiv(P, 256 / (cblk / 8));
     if (dtype == MDM_BF16 && np <= 16) {
-#define GN_BWD_REG(NPV, NT) hipLaunchKernelGGL((gn_bwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0, \
-                                               (const bf16_t*)src1, C1, P, G, cblk, gamma, beta, silu, (const bf16_t*)dy, stats,            \
-                                               (bf16_t*)dst0, (const bf16_t*)add0, (bf16_t*)dst1, (const bf16_t*)add1, (const bf16_t*)add0b, dgamma, dbeta, \
-                                               sum_img, sum_ld, sum_all, ws)
+#define GN_BWD_ARGS (const bf16_t*)src0, C0, (const bf16_t*)src1, C1, P, G, cblk, gamma, beta, silu, (const bf16_t*)dy, stats, (bf16_t*)dst0,      \
+                    (const bf16_t*)add0, (bf16_t*)dst1, (const bf16_t*)add1, (const bf16_t*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, ws
+#define GN_BWD_REG(NPV, NT)                                                                                                                          \
+    do {                                                                                                                                             \
+        if constexpr (DROP)                                                                                                                          \
+            hipLaunchKernelGGL((gn_bwd_reg_kernel_drop<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, GN_BWD_ARGS, rng, dbase, ctl);          \
+        else                                                                                                                                         \
+            hipLaunchKernelGGL((gn_bwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, GN_BWD_ARGS);                                \
+    } while (0)
         if (np <= 1) GN_BWD_REG(1, 256); else if (np <= 2) GN_BWD_REG(2, 256); else if (np <= 4) GN_BWD_REG(2, 512);
         else if (np <= 8) GN_BWD_REG(4, 512); else GN_BWD_REG(8, 512);
 #undef GN_BWD_REG
+#undef GN_BWD_ARGS
         return launch_status("groupnorm_bwd");
     }
     // fp32 path: fixed summation order across the images too (per-image partials in ws + a second stage); bf16 large maps: atomics
     float* part = dtype == MDM_F32 ? ws : nullptr;
     MDM_REQUIRE(dtype != MDM_F32 || ws, "groupnorm_bwd: the fp32 path needs ws (>= 3 * N * C floats) for its fixed-order sums");
-    DISPATCH_T(dtype, hipLaunchKernelGGL((gn_bwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
-                                         (const T*)src1, C1, P, G, cblk, gamma, beta, silu, (const T*)dy, stats, (T*)dst0,
-                                         (const T*)add0, (T*)dst1, (const T*)add1, (const T*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, part));
+    if constexpr (DROP)
+        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_bwd_kernel_drop<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
+                                             (const T*)src1, C1, P, G, cblk, gamma, beta, silu, (const T*)dy, stats, (T*)dst0,
+                                             (const T*)add0, (T*)dst1, (const T*)add1, (const T*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, part,
+                                             rng, dbase, ctl));
+    else
+        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_bwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
+                                             (const T*)src1, C1, P, G, cblk, gamma, beta, silu, (const T*)dy, stats, (T*)dst0,
+                                             (const T*)add0, (T*)dst1, (const T*)add1, (const T*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, part));
     if (part)
         hipLaunchKernelGGL(gn_param_reduce_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, part, N, C, dgamma, dbeta, sum_all);
     return launch_status("groupnorm_bwd");
+}
+extern "C" int mdm_groupnorm_bwd_add(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
+                                     const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
+                                     void* dst0, const void* add0, void* dst1, const void* add1, float* dgamma, float* dbeta,
+                                     float* sum_img, int sum_ld, float* sum_all, float* ws, const void* add0b, void* stream) {
+    return gn_bwd_dispatch<false>(dtype, src0, C0, src1, C1, N, P, G, gamma, beta, silu, dy, stats, dst0, add0, dst1, add1, dgamma, dbeta,
+                                  sum_img, sum_ld, sum_all, ws, add0b, nullptr, 0, nullptr, stream);
+}
+extern "C" int mdm_groupnorm_bwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
+                                         const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
+                                         void* dst0, const void* add0, void* dst1, const void* add1, float* dgamma, float* dbeta,
+                                         float* sum_img, int sum_ld, float* sum_all, float* ws, const void* add0b,
+                                         const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream) {
+    if (int rc = drop_check("groupnorm_bwd_dropout", C1, rng, base, ctl)) return rc;
+    return gn_bwd_dispatch<true>(dtype, src0, C0, src1, C1, N, P, G, gamma, beta, silu, dy, stats, dst0, add0, dst1, add1, dgamma, dbeta,
+                                 sum_img, sum_ld, sum_all, ws, add0b, rng, base, ctl, stream);
 }
 
 extern "C" int mdm_groupnorm_bwd_sums(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,

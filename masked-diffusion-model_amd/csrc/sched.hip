@@ -8,12 +8,8 @@
 
 namespace mdm {
 
-// Philox stream ids so the draws of one step never overlap
-// (id 0: timesteps, 1: training mask, 2: shift, 3/4: sampler masks t / t-1)
-__device__ __forceinline__ uint4 philox_at(const uint64_t* rng, int stream_id, uint64_t idx) {
-    Philox ph(rng[0]);
-    return ph(idx, rng[1] * 8 + (uint64_t)stream_id);
-}
+// Philox stream ids (philox_at, common.h) so the draws of one step never overlap
+// (id 0: timesteps, 1: training mask, 2: shift, 3/4: sampler masks t / t-1; 5: the dropout masks of norm.hip, on the U-Net's own state)
 
 __global__ void draw_timesteps_kernel(const uint64_t* rng, const int32_t* used, int n_used, const double* table,
                                       const float* wtab, int N, float* t_out, double* amount_out, float* weight_out,

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (MDM_LIB_PATH: load another BUILD of the same library -- A/B timing of two builds on one box; it selects a file, not a code path)
 LIB_PATH = os.environ.get("MDM_LIB_PATH") or os.path.join(_HERE, "libmdm_hip.so")
 
-vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
 
 class GemmDesc(C.Structure):
@@ -60,6 +60,10 @@ _PROTOS = {
     "mdm_groupnorm_bwd_sums": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp], i32),
     "mdm_groupnorm_bwd_ws_floats": ([i32, i32, i32], i64),
     "mdm_groupnorm_bwd_add": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp], i32),
+    "mdm_groupnorm_fwd_dropout": ([i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, vp, vp, u64, vp, vp], i32),
+    "mdm_groupnorm_bwd_dropout": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                   vp, u64, vp, vp], i32),
+    "mdm_dropout_mask": ([vp, u64, vp, i64, vp, vp], i32),
     "mdm_attn_supported": ([i32, i32, i32], i32),
     "mdm_attn_fwd": ([i32, vp, vp, vp, i32, i32, i32, f32, vp], i32),
     "mdm_attn_f32_small_supported": ([i32, i32], i32),

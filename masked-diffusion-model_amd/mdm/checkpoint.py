@@ -16,7 +16,8 @@ hooks of main_train_masked.py:195-225, and resumes with `accelerator.load_state(
     <path>/scheduler.bin                             torch.save(lr_scheduler.state_dict())
     <path>/random_states_<rank>.pkl                  torch.save (despite the suffix) of {step, random_state,
                                                      numpy_random_seed, torch_manual_seed[, torch_cuda_manual_seed]}
-                                                     (here also the device Philox key/offset under its own key)
+                                                     (here also the device Philox key/offset under its own key, and -- for a
+                                                     model with drop_rate > 0 only -- that of its dropout masks)
 
 optimizer.bin / scheduler.bin / random_states_<rank>.pkl are PINNED: tests/golden/train_traj.npz holds the key / shape /
 dtype manifest of the directory a real `accelerate.Accelerator.save_state` wrote at the end of the reference's `train()`
@@ -98,6 +99,8 @@ def save_state(path, model, optimizer=None, ema=None, lr_scheduler=None, schedul
         states["torch_cuda_manual_seed"] = torch.cuda.get_rng_state_all()
     if scheduler is not None and getattr(scheduler, "dev_rng", None) is not None:
         states["mdm_philox"] = [int(v) for v in scheduler.dev_rng.dev.cpu().tolist()]
+    if getattr(model, "drop_rng", None) is not None:        # a model with drop_rate > 0: the Philox key/offset of its dropout masks
+        states["mdm_dropout_philox"] = [int(v) for v in model.drop_rng.dev.cpu().tolist()]
     if extra:
         states["mdm_extra"] = dict(extra)
     torch.save(states, os.path.join(path, f"random_states_{rank}.pkl"))
@@ -130,6 +133,8 @@ def load_state(path, model, optimizer=None, ema=None, lr_scheduler=None, schedul
         extra_step = st.get("step")
         if scheduler is not None and "mdm_philox" in st:
             scheduler.dev_rng.dev.copy_(torch.tensor(st["mdm_philox"], dtype=torch.int64))
+        if "mdm_dropout_philox" in st and getattr(model, "drop_rng", None) is not None:
+            model.drop_rng.dev.copy_(torch.tensor(st["mdm_dropout_philox"], dtype=torch.int64))
         extra = dict(st.get("mdm_extra", {}))
         if extra_step is not None:
             extra.setdefault("step", int(extra_step))

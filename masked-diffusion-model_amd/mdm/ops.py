@@ -285,6 +285,38 @@ def groupnorm_bwd(dt, src0, C0, src1, C1, N, P, gamma, beta, silu, dy, stats, ds
          ptr(sum_all), ptr(ws), ptr(a0b), stream())
 
 
+def dropout_ctl_words(rate):
+    """(thr, scale) of a dropout rate: thr = clamp(round(rate * 65536), 0, 65535) of the 16-bit lanes, scale = 65536 / (65536 - thr)
+    (the expectation is exact for the QUANTISED probability thr / 65536)."""
+    thr = max(0, min(65535, int(round(float(rate) * 65536))))
+    return thr, 65536.0 / (65536 - thr)
+
+
+def groupnorm_fwd_dropout(dt, src0, C0, N, P, gamma, beta, silu, y, stats, ws, rng, base, ctl, G=32, eps=1e-6):
+    """groupnorm_fwd of ONE source with y *= keep * scale (mdm_groupnorm_fwd_dropout): rng = int64[2] {seed, offset}, base = the
+    site's first global element index, ctl = int32[2] holding {thr, bits of the fp32 scale} -- all three in device memory."""
+    call("mdm_groupnorm_fwd_dropout", dt, ptr(src0), C0, None, 0, N, P, G, eps, ptr(gamma), ptr(beta), int(silu),
+         ptr(y), ptr(stats), ptr(ws), ptr(rng), int(base), ptr(ctl), stream())
+
+
+def groupnorm_bwd_dropout(dt, src0, C0, N, P, gamma, beta, silu, dy, stats, dst0, acc0, dgamma, dbeta, ws, rng, base, ctl, G=32,
+                          sum_img=None, sum_ld=0, sum_all=None, add0=None):
+    """groupnorm_bwd of ONE source on dz = dy * keep * scale (mdm_groupnorm_bwd_dropout); the mask is drawn again from (rng, base)."""
+    need = _lib.load().mdm_groupnorm_bwd_ws_floats(dt, N, C0)
+    if need and (ws is None or ws.numel() < need):
+        raise ValueError(f"groupnorm_bwd_dropout: workspace of {0 if ws is None else ws.numel()} floats, {need} needed")
+    a0 = dst0 if acc0 else add0
+    a0b = add0 if acc0 else None
+    call("mdm_groupnorm_bwd_dropout", dt, ptr(src0), C0, None, 0, N, P, G, ptr(gamma), ptr(beta), int(silu), ptr(dy),
+         ptr(stats), ptr(dst0), ptr(a0), None, None, ptr(dgamma), ptr(dbeta), ptr(sum_img), sum_ld,
+         ptr(sum_all), ptr(ws), ptr(a0b), ptr(rng), int(base), ptr(ctl), stream())
+
+
+def dropout_mask(rng, base, ctl, n, keep):
+    """keep (uint8[n]) = the keep flags of the n elements from global index `base` on (mdm_dropout_mask)."""
+    call("mdm_dropout_mask", ptr(rng), int(base), ptr(ctl), int(n), ptr(keep), stream())
+
+
 def attn_supported(dt, L, C):
     return bool(_lib.load().mdm_attn_supported(dt, L, C))
 

@@ -9,6 +9,7 @@ list of C-ABI launches over statically allocated NHWC activations.
 from __future__ import annotations
 
 import math
+import struct
 from collections import OrderedDict
 from types import SimpleNamespace
 
@@ -19,16 +20,20 @@ from . import _lib, ops
 from ._lib import BF16, F32
 
 
-def unet6_config(image_size, in_channels=3, out_channels=3):
-    """Presets of reference models_Unet.py:132-171 (`Model('unet6', C, H, W, out_C)`)."""
+def unet6_config(image_size, in_channels=3, out_channels=3, drop_rate=0.0):
+    """Presets of reference models_Unet.py:132-171 (`Model('unet6', C, H, W, out_C)`).  `drop_rate`: unet6's constructor argument of
+    that name (unet6.py:378; the factory passes 0.0) -- a key of the dict only when it is not zero, so the default dict is unchanged."""
     if image_size in (32, 64):
         mult, attn = [1, 2, 2, 2], [False, False, True, False]
     elif image_size in (128, 256):
         mult, attn = [1, 1, 2, 2, 4, 4], [False, False, False, False, True, False]
     else:
         raise NotImplementedError("model selection error")
-    return dict(in_channels=in_channels, hid_channels=128, out_channels=out_channels, ch_multipliers=mult,
-                num_res_blocks=2, apply_attn=attn)
+    cfg = dict(in_channels=in_channels, hid_channels=128, out_channels=out_channels, ch_multipliers=mult,
+               num_res_blocks=2, apply_attn=attn)
+    if drop_rate:
+        cfg["drop_rate"] = float(drop_rate)
+    return cfg
 
 
 def _pad8(c):
@@ -421,6 +426,8 @@ class _Norm:
         self.fwd_fused = False      # the conv right before it normalises its own output (that conv's gn_fwd)
         self.bwd_fused = False      # its backward is the epilogue of its consumers' data gradients (their gn_bwd)
         self.sums_for = None        # norm2 of a ResidualBlock: conv1, whose bias / time-embedding sums this backward also emits
+        # ---- set while the specs are built (UNet._resblock), not a decision of the plan
+        self.drop_base = None       # norm2 of a ResidualBlock of a net with drop_rate > 0: first global element index of this dropout site
 
     def declare(self, st):
         c = self.out.C
@@ -450,6 +457,10 @@ class _Norm:
         if self.fwd_fused:
             return
         self.stats = n.alloc((s0.N, 32, 2), torch.float32)
+        if self.drop_base is not None:      # y = silu(GN(x)) * keep * scale (unet6.py:360), the mask drawn inside the kernel
+            ops.groupnorm_fwd_dropout(n.dt, s0.data, s0.C, s0.N, s0.P, st.f(self.name + ".weight"), st.f(self.name + ".bias"), self.silu,
+                                      self.out.data, self.stats, n.gn_ws, n.drop_rng.dev, self.drop_base, n.drop_ctl, eps=self.eps)
+            return
         ops.groupnorm_fwd(n.dt, s0.data, s0.C, s1.data if s1 else None, s1.C if s1 else 0, s0.N, s0.P,
                           st.f(self.name + ".weight"), st.f(self.name + ".bias"), self.silu, self.out.data, self.stats, n.gn_ws,
                           eps=self.eps)
@@ -461,6 +472,11 @@ class _Norm:
             return
         dyo = n.grad_for_read(self.out)
         g0, a0, add0 = n.grad_for_write(s0, want_add=2)
+        if self.drop_base is not None:      # the same mask again, from the same counters, on dy as it is loaded
+            ops.groupnorm_bwd_dropout(n.dt, s0.data, s0.C, s0.N, s0.P, st.f(self.name + ".weight"), st.f(self.name + ".bias"), self.silu,
+                                      dyo, self.stats, g0, a0, st.g(self.name + ".weight"), st.g(self.name + ".bias"), n.gn_ws,
+                                      n.drop_rng.dev, self.drop_base, n.drop_ctl, add0=add0, **self.sums_fields(a0, add0))
+            return
         g1, a1, add1 = n.grad_for_write(s1, want_add=True) if s1 is not None else (None, 0, None)
         ops.groupnorm_bwd(n.dt, s0.data, s0.C, s1.data if s1 else None, s1.C if s1 else 0, s0.N, s0.P,
                           st.f(self.name + ".weight"), st.f(self.name + ".bias"), self.silu, dyo, self.stats,
@@ -604,7 +620,7 @@ class UNet:
 
     def __init__(self, cfg, N, H, W, dtype=BF16, device=None, params=None, seed=1234, store=None, use_graph=True,
                  group_wgrads=True, wgrad_group_bytes=None, pair_convs=True, f32_products="exact", uniform_t=False, grad_products="exact",
-                 _dry=False):
+                 drop_seed=0, _drop_parent=None, _dry=False):
         # grad_products="split": fp32 TRAINING with the backward's convolution products as hi / lo pairs too (data gradients through
         # the flipped, transposed split shadow PsT on the split forward routes, weight gradients on mdm_conv_wgrad_split); fp32
         # storage, accumulation and optimizer state.  Only with dtype=F32, f32_products="split"; "exact" (default) is today's path.
@@ -616,6 +632,15 @@ class UNet:
         # time-embedding MLP and its 22 projections then run on one row and every image reads projection row 0.  Forward-only.
         self.uniform_t = bool(uniform_t)
         self.cfg = dict(cfg)
+        # drop_rate (unet6.py:378): nn.Dropout between silu(norm2(.)) and conv2 of every ResidualBlock (:354, :360), here inside the
+        # standalone GroupNorm kernels of those norm2 (csrc/norm.hip).  Forward-only plans (uniform_t, the fp32 sampling twins:
+        # _drop_parent=False) are built without it and keep every fusion; a twin with dropout shares its parent's state (_drop_parent).
+        rate = float(self.cfg.get("drop_rate", 0.0))
+        if not 0.0 <= rate < 1.0:
+            raise ValueError(f"drop_rate={rate!r}: need 0 <= drop_rate < 1")
+        self.drop_rate = 0.0 if (self.uniform_t or _drop_parent is False) else rate
+        self.drop_seed = int(drop_seed)
+        self.drop_rng = self.drop_ctl = self._drop_ctl_modes = None
         self.N, self.H, self.W = N, H, W
         self.dt = dtype
         self.group_wgrads = group_wgrads            # weight gradients of the bf16 path run as grouped launches
@@ -666,6 +691,8 @@ class UNet:
         self._set_param_marks()
         self._plan()
         self._materialize()
+        if self.drop_rate > 0:
+            self._init_dropout(_drop_parent)
         if not shared:
             if params is None:
                 params = self._default_params(seed)
@@ -680,6 +707,29 @@ class UNet:
             self._build_zero_table()
         self._graph_fwd = None
 
+    def _init_dropout(self, parent):
+        """The dropout state: a DeviceRng keyed by (drop_seed, data-parallel rank) whose offset the FIRST launch of forward_plan bumps
+        (forward and backward of one step see one offset, every eager run / graph replay / micro-batch a new one), and the control
+        words ctl = {thr, scale} the kernels read -- train() / eval() rewrite them on the device, in stream order, so they act on plans
+        and graphs that are already recorded.  Plans over the same weights (with_batch, sampling_plan "model") share both."""
+        if parent is not None:
+            assert parent.drop_rate == self.drop_rate and parent.drop_rng is not None
+            self.drop_rng, self.drop_ctl, self._drop_ctl_modes = parent.drop_rng, parent.drop_ctl, parent._drop_ctl_modes
+            return
+        from .scheduler import DeviceRng
+        import torch.distributed as dist
+        rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
+        self.drop_rng = DeviceRng(self.device, self.drop_seed, rank)
+        thr, scale = ops.dropout_ctl_words(self.drop_rate)
+        bits = lambda f: struct.unpack("<i", struct.pack("<f", f))[0]
+        self._drop_ctl_modes = torch.tensor([[0, bits(1.0)], [thr, bits(scale)]], dtype=torch.int32, device=self.device)    # eval, train
+        self.drop_ctl = self._drop_ctl_modes[1].clone()
+
+    def dropout_sites(self):
+        """[(norm2 name, base, elements)] of the dropout sites in `specs` order ([] without dropout): element e of a site has the
+        global index base + e in the mask definition of csrc/norm.hip."""
+        return [(s.name, s.drop_base, s.out.N * s.out.P * s.out.C) for s in self.specs if isinstance(s, _Norm) and s.drop_base is not None]
+
     def _default_params(self, seed):
         from .init import xavier_like_params
         return xavier_like_params(self.reference_shapes(), seed)
@@ -693,7 +743,8 @@ class UNet:
         """Another launch plan of this architecture: same weights (store), dtype, products and timestep mode unless overridden.
         NOT inherited, here as before: group_wgrads, pair_convs and wgrad_group_bytes -- a twin always gets their defaults."""
         kw = dict(dtype=self.dt, device=self.device, store=self.store, use_graph=self.use_graph,
-                  f32_products="split" if self.split_products else "exact", uniform_t=self.uniform_t, grad_products=self.grad_products)
+                  f32_products="split" if self.split_products else "exact", uniform_t=self.uniform_t, grad_products=self.grad_products,
+                  drop_seed=self.drop_seed, _drop_parent=self if self.drop_rate > 0 else None)
         kw.update(overrides)
         return type(self)(self.cfg, N, self.H, self.W, **kw)
 
@@ -734,7 +785,7 @@ class UNet:
         plans = self._sampling_plans
         key = (N, precision)
         if key not in plans:
-            kw = dict(dtype=F32, f32_products=products, uniform_t=False, grad_products="exact")
+            kw = dict(dtype=F32, f32_products=products, uniform_t=False, grad_products="exact", _drop_parent=False)     # forward-only: no dropout
             if self.dt == F32:
                 plans[key] = self._twin(N, **kw)
             else:
@@ -772,6 +823,7 @@ class UNet:
         self.cin, self.cout, self.cin_p, self.cout_p = cin, cout, _pad8(cin), _pad8(cout)
         self.acts, self.specs, self.blocks, self.fc_slots = [], [], [], OrderedDict()
         self.fc_total = 0
+        self._drop_elems = 0            # running element count of the dropout sites (64-bit on the host; every site a multiple of 8)
 
     def _conv(self, name, src0, src1, Cout, k=3, stride=1, ups=0, fc=None, resid=None, rshape=None):
         pads = (1, 1, 1, 1) if k == 3 and stride == 1 else self.down_pads if k == 3 else (0, 0, 0, 0)
@@ -797,6 +849,9 @@ class UNet:
         a = self._norm(pre + ".norm1", x0, x1, True)
         h = self._conv(pre + ".conv1", a, None, Cout, fc=slot)
         b = self._norm(pre + ".norm2", h, None, True)
+        if self.drop_rate > 0:                            # a dropout site: nn.Dropout on silu(norm2(.)) (unet6.py:354, 360)
+            b.norm_spec.drop_base = self._drop_elems
+            self._drop_elems += b.N * b.P * b.C
         out = self._conv(pre + ".conv2", b, None, Cout, resid=skip)
         self.blocks.append(_ResBlock(skip_spec, self.specs[-3], self.specs[-2], self.specs[-1], self.pair_blocks))
         return out
@@ -870,6 +925,7 @@ class UNet:
                 s.skinny = s._skinny()
         for prev, nm in zip(self.specs, self.specs[1:]):    # a norm as the epilogue of the conv right before it (4x4 / 8x8 maps)
             if (bf16 and isinstance(nm, _Norm) and nm.src1 is None and isinstance(prev, _Conv) and prev.out is nm.src0
+                    and nm.drop_base is None            # a dropout site stays a launch: the conv epilogues know no dropout
                     and ops.conv_fwd_can_fuse_gn(self.dt, prev.g)):
                 prev.gn_fwd, nm.fwd_fused = nm, True
         pairs = [b for b in self.blocks if self.pair_convs and b.paired and b.skip is not None]
@@ -887,7 +943,7 @@ class UNet:
             if c.src0.needs_grad:
                 c.dgrad = "t" if bf16 else "split" if split and reason["dgrad"] is None else "exact"
                 nm = c.src0.norm_spec
-                if (bf16 and nm is not None and nm.src1 is None and c.src1 is None and not c.g.ups
+                if (bf16 and nm is not None and nm.src1 is None and c.src1 is None and not c.g.ups and nm.drop_base is None
                         and ops.conv_dgrad_t_can_fuse_gn_bwd(self.dt, c.g)):
                     c.gn_bwd, nm.bwd_fused = nm, True
             c.grad_exact = {w: "exact:" + reason[w] for w, how in (("wgrad", c.wgrad), ("dgrad", c.dgrad))
@@ -1052,6 +1108,8 @@ class UNet:
         return rec
 
     def _emit_fwd(self):
+        if self.drop_rate > 0:
+            self.drop_rng.advance()     # first launch of the plan: the masks of this run (its backward draws them again from the same offset)
         for s in self.specs:
             s.fwd()
 
@@ -1139,7 +1197,11 @@ class UNet:
         return n
 
     def train(self, mode=True):
-        self.training = mode
+        """PyTorch's semantics: a plan drops iff the model is in training mode when it RUNS -- the control words are rewritten on the
+        device, in stream order and without a host synchronisation, so recorded plans and captured graphs follow."""
+        self.training = bool(mode)
+        if self.drop_ctl is not None:
+            self.drop_ctl.copy_(self._drop_ctl_modes[1 if mode else 0])
         return self
 
     def eval(self):
