@@ -331,6 +331,16 @@ int mdm_colsum(int dtype, const void* dY, int N, int P, int C, float* per_img, i
 /* 2x2 sum-pool of g[N][2H][2W][C] into dst[N][H][W][C] (backward of nn.Upsample(2,'nearest'), unet6.py:472) */
 int mdm_sumpool2(int dtype, const void* g, void* dst, int acc, int N, int H, int W, int C, void* stream);
 
+/* resample_with_conv=False (unet6.py:441-442, 472-475): the parameter-free resampling.  NHWC, C % 8 == 0, fp32 arithmetic,
+ * one rounding to storage, no atomics.
+ *   mdm_avgpool2   H, W = OUTPUT extents, src[N][2H][2W][C]: dst[n,h,w,c] = (acc ? dst : 0) + 0.25 (((a + b) + c) + d) over the
+ *                  2x2 block, taps in mdm_sumpool2's order.  Forward of nn.AvgPool2d(2) (unet6.py:441-442).
+ *   mdm_upsample2  H, W = SOURCE extents, dst[N][2H][2W][C]: dst[n,y,x,c] = (acc ? dst : 0) + scale * src[n,y/2,x/2,c].  Forward of
+ *                  nn.Upsample(scale_factor=2, mode="nearest") (unet6.py:472-475; scale 1, acc 0) and backward of the average pool
+ *                  (scale 0.25).  The backward of the bare upsample is mdm_sumpool2. */
+int mdm_avgpool2(int dtype, const void* src, void* dst, int acc, int N, int H, int W, int C, void* stream);
+int mdm_upsample2(int dtype, const void* src, void* dst, int acc, float scale, int N, int H, int W, int C, void* stream);
+
 /* dst += src over n elements of `dtype` (n % 8 == 0): joins two gradient contributions of one activation */
 int mdm_add(int dtype, void* dst, const void* src, int64_t n, void* stream);
 /* dst = x + y (y == NULL: dst = x) */

@@ -372,6 +372,76 @@ __global__ __launch_bounds__(256) void sumpool2_kernel(const T* g, T* dst, int a
     }
 }
 
+// ---- resample_with_conv=False (unet6.py:441-442, 472-475): the 2x2 average pool and the bare nearest x2 upsample.  Pure streaming
+// kernels, one 8-channel vector of the SMALL map per lane: vector i of [N][H][W][C/8] <-> the 2x2 block of [N][2H][2W][C] it pairs with.
+struct Quad { int64_t small, big; };        // element offsets of the vector in the small map and of the block's top-left vector
+__device__ __forceinline__ Quad quad_of(int64_t i, int64_t total_vec, int H, int W, int C) {
+    const int VPP = C / 8;
+    int64_t pix, img;
+    int c, x, y;
+    if (total_vec < (1ll << 31)) {              // 32-bit quotients, as sumpool2_kernel
+        const unsigned iu = (unsigned)i, pu = iu / (unsigned)VPP, ru = pu / (unsigned)W, mu = ru / (unsigned)H;
+        pix = pu; c = (int)(iu - pu * (unsigned)VPP) * 8; x = (int)(pu - ru * (unsigned)W); y = (int)(ru - mu * (unsigned)H); img = mu;
+    } else {
+        pix = i / VPP;
+        c = (int)(i - pix * VPP) * 8;
+        x = (int)(pix % W);
+        const int64_t r = pix / W;
+        y = (int)(r % H);
+        img = r / H;
+    }
+    return {pix * C + c, (((img * 2 * H + 2 * y) * 2 * W) + 2 * x) * (int64_t)C + c};
+}
+__device__ __forceinline__ float8 scale8(float s, const float8& v) {
+    float8 r;
+    r.lo = make_float4(s * v.lo.x, s * v.lo.y, s * v.lo.z, s * v.lo.w);
+    r.hi = make_float4(s * v.hi.x, s * v.hi.y, s * v.hi.z, s * v.hi.w);
+    return r;
+}
+__device__ __forceinline__ float8 axpy8(float s, const float8& v, const float8& o) {      // o + s * v: product and sum each rounded (no fma)
+#pragma clang fp contract(off)
+    float8 r;
+    r.lo = make_float4(s * v.lo.x + o.lo.x, s * v.lo.y + o.lo.y, s * v.lo.z + o.lo.z, s * v.lo.w + o.lo.w);
+    r.hi = make_float4(s * v.hi.x + o.hi.x, s * v.hi.y + o.hi.y, s * v.hi.z + o.hi.z, s * v.hi.w + o.hi.w);
+    return r;
+}
+
+// dst[N][H][W][C] (=|+=) 0.25 * (((a + b) + c) + d) over the 2x2 block of src[N][2H][2W][C]: the taps in sumpool2_kernel's order
+template <typename T>
+__global__ __launch_bounds__(256) void avgpool2_kernel(const T* src, T* dst, int acc, int H, int W, int C, int64_t total_vec) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_vec; i += (int64_t)gridDim.x * blockDim.x) {
+        const Quad q = quad_of(i, total_vec, H, W, C);
+        const T* base = src + q.big;
+        float8 a = load8(base), b = load8(base + C), cc = load8(base + (int64_t)2 * W * C), dd = load8(base + (int64_t)2 * W * C + C);
+        float8 s;
+        s.lo = make_float4(a.lo.x + b.lo.x + cc.lo.x + dd.lo.x, a.lo.y + b.lo.y + cc.lo.y + dd.lo.y,
+                           a.lo.z + b.lo.z + cc.lo.z + dd.lo.z, a.lo.w + b.lo.w + cc.lo.w + dd.lo.w);
+        s.hi = make_float4(a.hi.x + b.hi.x + cc.hi.x + dd.hi.x, a.hi.y + b.hi.y + cc.hi.y + dd.hi.y,
+                           a.hi.z + b.hi.z + cc.hi.z + dd.hi.z, a.hi.w + b.hi.w + cc.hi.w + dd.hi.w);
+        T* o = dst + q.small;
+        store8(o, acc ? axpy8(0.25f, s, load8(o)) : scale8(0.25f, s));
+    }
+}
+
+// dst[N][2H][2W][C] (=|+=) scale * src[N][H][W][C] at the four pixels of the block: ONE load of the source vector, four stores
+template <typename T>
+__global__ __launch_bounds__(256) void upsample2_kernel(const T* src, T* dst, int acc, float scale, int H, int W, int C, int64_t total_vec) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total_vec; i += (int64_t)gridDim.x * blockDim.x) {
+        const Quad q = quad_of(i, total_vec, H, W, C);
+        const float8 v = load8(src + q.small);
+        T* o = dst + q.big;
+        const int64_t row = (int64_t)2 * W * C;
+        if (acc) {
+            const float8 a = load8(o), b = load8(o + C), cc = load8(o + row), dd = load8(o + row + C);
+            store8(o, axpy8(scale, v, a)); store8(o + C, axpy8(scale, v, b));
+            store8(o + row, axpy8(scale, v, cc)); store8(o + row + C, axpy8(scale, v, dd));
+        } else {
+            const float8 r = scale8(scale, v);
+            store8(o, r); store8(o + C, r); store8(o + row, r); store8(o + row + C, r);
+        }
+    }
+}
+
 template <typename T>
 __global__ void nchw_to_nhwc_kernel(const float* x, T* y, int C, int HW, int Cp, int64_t total) {
     int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // over N*HW*Cp
@@ -696,6 +766,21 @@ extern "C" int mdm_sumpool2(int dtype, const void* g, void* dst, int acc, int N,
     const int64_t tv = (int64_t)N * H * W * (C / 8);
     DISPATCH_T(dtype, hipLaunchKernelGGL((sumpool2_kernel<T>), dim3(stream_grid(tv)), dim3(256), 0, (hipStream_t)stream, (const T*)g, (T*)dst, acc, H, W, C, tv));
     return launch_status("sumpool2");
+}
+
+extern "C" int mdm_avgpool2(int dtype, const void* src, void* dst, int acc, int N, int H, int W, int C, void* stream) {
+    MDM_REQUIRE(C % 8 == 0, "avgpool2: C must be a multiple of 8");
+    MDM_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && src && dst, "avgpool2: bad shape");
+    const int64_t tv = (int64_t)N * H * W * (C / 8);
+    DISPATCH_T(dtype, hipLaunchKernelGGL((avgpool2_kernel<T>), dim3(stream_grid(tv)), dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)dst, acc, H, W, C, tv));
+    return launch_status("avgpool2");
+}
+extern "C" int mdm_upsample2(int dtype, const void* src, void* dst, int acc, float scale, int N, int H, int W, int C, void* stream) {
+    MDM_REQUIRE(C % 8 == 0, "upsample2: C must be a multiple of 8");
+    MDM_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && src && dst, "upsample2: bad shape");
+    const int64_t tv = (int64_t)N * H * W * (C / 8);
+    DISPATCH_T(dtype, hipLaunchKernelGGL((upsample2_kernel<T>), dim3(stream_grid(tv)), dim3(256), 0, (hipStream_t)stream, (const T*)src, (T*)dst, acc, scale, H, W, C, tv));
+    return launch_status("upsample2");
 }
 
 extern "C" int mdm_add(int dtype, void* dst, const void* src, int64_t n, void* stream) {

@@ -83,6 +83,8 @@ _PROTOS = {
     "mdm_silu_bwd_sum": ([vp, vp, i32, i64, vp, vp], i32),
     "mdm_colsum": ([i32, vp, i32, i32, i32, vp, i32, i32, vp, vp], i32),
     "mdm_sumpool2": ([i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "mdm_avgpool2": ([i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),
+    "mdm_upsample2": ([i32, vp, vp, i32, f32, i32, i32, i32, i32, vp], i32),
     "mdm_add": ([i32, vp, vp, i64, vp], i32),
     "mdm_add3": ([i32, vp, vp, vp, i64, vp], i32),
     "mdm_nchw_to_nhwc": ([i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),

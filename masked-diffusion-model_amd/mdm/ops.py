@@ -378,6 +378,17 @@ def sumpool2(dt, g, dst, acc, N, H, W, C):
     call("mdm_sumpool2", dt, ptr(g), ptr(dst), int(acc), N, H, W, C, stream())
 
 
+def avgpool2(dt, src, dst, acc, N, H, W, C):
+    """dst[N,H,W,C] (=|+=) the 2x2 average of src[N,2H,2W,C]: nn.AvgPool2d(2) (unet6.py:441-442).  H, W: OUTPUT extents."""
+    call("mdm_avgpool2", dt, ptr(src), ptr(dst), int(acc), N, H, W, C, stream())
+
+
+def upsample2(dt, src, dst, acc, scale, N, H, W, C):
+    """dst[N,2H,2W,C] (=|+=) scale * src[N,H,W,C] at the four pixels of each 2x2 block: nn.Upsample(2, "nearest") (unet6.py:472-475;
+    scale 1) and the backward of avgpool2 (scale 0.25).  H, W: SOURCE extents."""
+    call("mdm_upsample2", dt, ptr(src), ptr(dst), int(acc), float(scale), N, H, W, C, stream())
+
+
 def nchw_to_nhwc(dt, x, y, N, C, H, W, Cp):
     call("mdm_nchw_to_nhwc", dt, ptr(x), ptr(y), N, C, H, W, Cp, stream())
 

@@ -20,9 +20,10 @@ from . import _lib, ops
 from ._lib import BF16, F32
 
 
-def unet6_config(image_size, in_channels=3, out_channels=3, drop_rate=0.0):
+def unet6_config(image_size, in_channels=3, out_channels=3, drop_rate=0.0, resample_with_conv=True):
     """Presets of reference models_Unet.py:132-171 (`Model('unet6', C, H, W, out_C)`).  `drop_rate`: unet6's constructor argument of
-    that name (unet6.py:378; the factory passes 0.0) -- a key of the dict only when it is not zero, so the default dict is unchanged."""
+    that name (unet6.py:378; the factory passes 0.0) -- a key of the dict only when it is not zero, so the default dict is unchanged.
+    `resample_with_conv` (unet6.py:379; the factory passes True): likewise a key only when it is False."""
     if image_size in (32, 64):
         mult, attn = [1, 2, 2, 2], [False, False, True, False]
     elif image_size in (128, 256):
@@ -33,6 +34,8 @@ def unet6_config(image_size, in_channels=3, out_channels=3, drop_rate=0.0):
                num_res_blocks=2, apply_attn=attn)
     if drop_rate:
         cfg["drop_rate"] = float(drop_rate)
+    if resample_with_conv is not True:
+        cfg["resample_with_conv"] = resample_with_conv      # False; anything else is rejected by UNet
     return cfg
 
 
@@ -534,6 +537,38 @@ class _AttnCore:
         ops.matmul(n.dt, 2, L, C, L, dP, L, d, 3 * C, g[:, :, C:], 3 * C, batch=N, sA=sl, sB=s3, sD=s3, alpha=sc)        # dK = dS^T Q
 
 
+class _Resample:
+    """The parameter-free resampling of resample_with_conv=False: kind "avgpool2" = nn.AvgPool2d(2) in place of a level's stride-2
+    convolution (unet6.py:441-442), "nearest2" = the bare nn.Upsample(scale_factor=2, mode="nearest") (unet6.py:472-475).  One
+    streaming launch per direction; each is the other's backward (up to the pool's 0.25)."""
+
+    def __init__(self, net, kind, src, out):
+        assert kind in ("avgpool2", "nearest2"), kind
+        self.net, self.kind, self.src, self.out, self.name = net, kind, src, out, None
+        self.param_lo = None
+
+    def declare(self, st):
+        pass
+
+    def fwd(self):
+        n, s, o = self.net, self.src, self.out
+        if self.kind == "avgpool2":
+            ops.avgpool2(n.dt, s.data, o.data, 0, o.N, o.H, o.W, o.C)
+        else:
+            ops.upsample2(n.dt, s.data, o.data, 0, 1.0, s.N, s.H, s.W, s.C)
+
+    def bwd(self):
+        n, s, o = self.net, self.src, self.out
+        if not s.needs_grad:
+            return
+        dy = n.grad_for_read(o)
+        g, acc, _ = n.grad_for_write(s)
+        if self.kind == "avgpool2":         # every pixel of the 2x2 block receives a quarter of the pooled pixel's gradient
+            ops.upsample2(n.dt, dy, g, acc, 0.25, o.N, o.H, o.W, o.C)
+        else:                               # the backward of nn.Upsample, as behind the folded x2 convolutions (_Conv.bwd)
+            ops.sumpool2(n.dt, dy, g, acc, s.N, s.H, s.W, s.C)
+
+
 class _Temb:
     """Sinusoidal embedding -> 2-layer MLP -> SiLU -> all 22 per-block projections in one
     contraction (unet6.py:18-34, 395-399, 350, 359).  fp32 throughout (rows = batch only)."""
@@ -640,6 +675,10 @@ class UNet:
             raise ValueError(f"drop_rate={rate!r}: need 0 <= drop_rate < 1")
         self.drop_rate = 0.0 if (self.uniform_t or _drop_parent is False) else rate
         self.drop_seed = int(drop_seed)
+        # resample_with_conv (unet6.py:379, 393): False = the parameter-free resampling of the original DDPM U-Net (_Resample)
+        self.resample_with_conv = self.cfg.get("resample_with_conv", True)
+        if not isinstance(self.resample_with_conv, bool):
+            raise ValueError(f"resample_with_conv={self.resample_with_conv!r}: need True or False")
         self.drop_rng = self.drop_ctl = self._drop_ctl_modes = None
         self.N, self.H, self.W = N, H, W
         self.dt = dtype
@@ -839,6 +878,12 @@ class UNet:
         self.specs.append(out.norm_spec)
         return out
 
+    def _resample(self, kind, name, src):
+        H, W = (src.H // 2, src.W // 2) if kind == "avgpool2" else (2 * src.H, 2 * src.W)
+        out = self._act(name, H, W, src.C)
+        self.specs.append(_Resample(self, kind, src, out))
+        return out
+
     def _resblock(self, pre, x0, x1, Cout):               # ResidualBlock (unet6.py:336-362) / diffusers' ResnetBlock2D
         Cin = x0.C + (x1.C if x1 else 0)
         slot = self.fc_total
@@ -891,8 +936,10 @@ class UNet:
             cur = mult[l] * hid
             for j in range(nres):
                 hs.append(block(f"downsamples.level_{l}.{j}", hs[-1], None, cur, attn[l]))
-            if l != levels - 1:
+            if l != levels - 1 and self.resample_with_conv:
                 hs.append(conv(f"downsamples.level_{l}.{nres}.1", hs[-1], None, cur, stride=2))
+            elif l != levels - 1:                         # unet6.py:441-442
+                hs.append(self._resample("avgpool2", f"downsamples.level_{l}.{nres}", hs[-1]))
         h = res("middle.0", hs[-1], None, hs[-1].C)       # unet6.py:494
         h = att("middle.1", h)
         h = res("middle.2", h, None, h.C)
@@ -900,8 +947,10 @@ class UNet:
             cur = mult[l] * hid
             for j in range(nres + 1):
                 h = block(f"upsamples.level_{l}.{j}", h, hs.pop(), cur, attn[l])
-            if l != 0:
+            if l != 0 and self.resample_with_conv:
                 h = conv(f"upsamples.level_{l}.{nres + 1}.1", h, None, cur, ups=1)
+            elif l != 0:                                  # unet6.py:472-475
+                h = self._resample("nearest2", f"upsamples.level_{l}.{nres + 1}", h)
         assert not hs
         h = norm("out_conv.0", h, None, True)             # unet6.py:505
         self.y_out = conv("out_conv.2", h, None, self.cout_p, rshape=(cout, hid, 3, 3))
@@ -1172,6 +1221,8 @@ class UNet:
             elif isinstance(s, _AttnCore):
                 N, L, C = s.qkv.N, s.qkv.P, s.out.C
                 a_out += 2 * N * L * L + 2 * N * L * C
+            elif isinstance(s, _Resample):
+                a_out += s.out.N * s.out.P * s.out.C         # nn.AvgPool2d / nn.Upsample output
             elif isinstance(s, _Temb):
                 a_out += self.N * (s.hid + 4 * s.temb)
         return a_out
