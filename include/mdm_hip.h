@@ -102,7 +102,7 @@ typedef struct mdm_gemm_desc {
      * whether this descriptor qualifies): the contraction result is d(z), z = silu?(GroupNorm(x)); instead of storing
      * it, the epilogue reads x, stats (mean, rstd per image and group), gamma, beta and writes dx into D0 (acc0 honoured),
      * adds dgamma / dbeta, and optionally the column sums of dx (gnb_sum_img[n * gnb_sum_ld + c] = sum_p dx,
-     * gnb_sum_all[c] += sum_{n,p} dx) like mdm_groupnorm_bwd_sums.  gnb_add (with acc0 == 0): a tensor laid out like D0
+     * gnb_sum_all[c] += sum_{n,p} dx) like sum_img / sum_all of mdm_gn_desc.  gnb_add (with acc0 == 0): a tensor laid out like D0
      * whose values are added to dx (the gradient arriving over the residual branch, unet6.py:362).  NULL gnb_x = plain epilogue. */
     const void* gnb_x; const float* gnb_stats; const float* gnb_gamma; const float* gnb_beta;
     float* gnb_dgamma; float* gnb_dbeta; float* gnb_sum_img; float* gnb_sum_all;
@@ -204,66 +204,67 @@ const char* mdm_wgrad_split_last_route(void);
 
 /* ------------------------------------------------------------------------- *
  * GroupNorm(32, eps) [+ SiLU]  (unet6.py:291-293, 358, 360, 330, 505)
- * x = concat(src0[C0], src1[C1]) along channels, NHWC, P = H*W pixels per image.
- * stats: [N][G][2] fp32 (mean, rstd).  One kernel per call, every sum in a fixed order (no float atomics); `ws` is
- * not used by the forward (may be NULL).
+ * x = concat(src0[C0], src1[C1]) along channels, NHWC, P = H*W pixels per image.  One descriptor drives both directions; it is
+ * read on the host at call time and its fields become kernel arguments by value (nothing on the device sees the struct).  A
+ * zeroed descriptor is a plain GroupNorm with nothing optional: every field a call does not use stays 0 / NULL.
+ * One kernel per call (the fp32 backward: two); inside a workgroup every sum has a fixed order.
  * ------------------------------------------------------------------------- */
-int mdm_groupnorm_fwd(int dtype, const void* src0, int C0, const void* src1, int C1,
-                      int N, int P, int G, float eps, const float* gamma, const float* beta,
-                      int silu, void* y, float* stats, float* ws, void* stream);
-/* dx -> dst0/dst1 (channel split like the sources), acc flags add into them;
- * dgamma/dbeta are ACCUMULATED: bf16, one fp32 atomic per channel per image; fp32 (dtype MDM_F32), NO atomics -- per-image partial
- * sums go to `ws` (REQUIRED there, >= 3*N*C floats) and a second launch adds them in image order, so the fp32 path gives the same bits
- * on every run.  (bf16: `ws` may be NULL.) */
-int mdm_groupnorm_bwd(int dtype, const void* src0, int C0, const void* src1, int C1,
-                      int N, int P, int G, const float* gamma, const float* beta, int silu,
-                      const void* dy, const float* stats, void* dst0, int acc0, void* dst1, int acc1,
-                      float* dgamma, float* dbeta, float* ws, void* stream);
+typedef struct mdm_gn_desc {
+    const void* src0; const void* src1; /* the sources (dtype); src1 may be NULL with C1 == 0 */
+    const float* gamma; const float* beta; /* [C0 + C1] */
+    float* stats;               /* [N][G][2] fp32 (mean, rstd): written by the forward, read by the backward */
+    float* ws;                  /* fp32 backward: REQUIRED, >= mdm_groupnorm_bwd_ws_floats() floats -- per-image partial sums that a
+                                 * second launch adds in image order: the same bits on every run.  Elsewhere unused, may be NULL */
+    /* forward */
+    void* y;                    /* [N][P][C0 + C1] (dtype) = silu?(GroupNorm_G(x) * gamma + beta) */
+    /* backward: dx goes to dst0 / dst1 (channel split like the sources); dgamma / dbeta are ACCUMULATED (bf16: one fp32 atomic per
+     * channel per image; fp32: no atomics, see ws) */
+    const void* dy;             /* [N][P][C0 + C1] (dtype) */
+    void* dst0;                 /* [N][P][C0]: dst0 = add0 + add0b + dx */
+    const void* add0;           /* NULL = none; a tensor laid out like dst0.  dst0 itself gives the accumulating form dst0 += dx; another
+                                 * tensor adds the gradient that arrives over a residual branch (x + block(x), unet6.py:333, 362) WITHOUT
+                                 * modifying that tensor, which a later (grouped) weight gradient still reads */
+    const void* add0b;          /* NULL = none; a SECOND tensor laid out like dst0 that is added too -- an activation with two forward
+                                 * consumers and a residual join receives dst0 (accumulate) + the residual branch's dY + dx in one pass */
+    void* dst1;                 /* [N][P][C1]: dst1 = add1 + dx; may be NULL with C1 == 0 */
+    const void* add1;           /* NULL = none; like add0 */
+    float* dgamma; float* dbeta; /* [C0 + C1] fp32, += */
+    /* column sums of the dx it writes (the complete gradient of a conv output); one source only (C1 == 0); either may be NULL */
+    float* sum_img;             /* sum_img[n * sum_ld + c] = sum_p dx (the time-embedding gradient, unet6.py:359) */
+    float* sum_all;             /* sum_all[c] += sum_{n,p} dx (that conv's bias gradient) */
+    /* Dropout on the GroupNorm output, fused into the same kernels (nn.Dropout between silu(norm2(.)) and conv2 of a ResidualBlock,
+     * unet6.py:354, 360): y = silu?(GN(x)) * keep * scale in the forward, dz = dy * keep * scale right behind the load of dy in the
+     * backward -- no extra pass over memory, no stored mask.  rng == NULL: no dropout (drop_base and ctl are ignored).  Otherwise one
+     * source only (C1 == 0), ctl != NULL and drop_base % 8 == 0.  Element e = (n*P + p)*C + c has the global index g = drop_base + e
+     * (drop_base: the caller's running element count of the dropout sites before this one); its random word is the 16-bit lane g & 7 of
+     * Philox4x32-10(key = rng[0], counter = {g >> 3, rng[1] * 8 + 5}) (lane j = half j & 1 of 32-bit word j >> 1, low half first).
+     * An element is kept iff its lane >= thr, kept values are multiplied by scale (thr = clamp(round(rate * 65536), 0, 65535),
+     * scale = 65536 / (65536 - thr)), dropped ones are exact zeros; thr == 0 (eval mode: {0, 1.0f}) draws nothing and gives the bits
+     * of a descriptor without rng. */
+    const uint64_t* rng;        /* {seed, offset} as for mdm_rng_advance: forward and backward of one step must see the same offset */
+    uint64_t drop_base;
+    const uint32_t* ctl;        /* {uint32 thr, float scale} in device memory */
+    int32_t dtype;              /* MDM_F32 | MDM_BF16: element type of the sources, y, dy, dst and add tensors */
+    int32_t N, P, G;            /* images, pixels per image, groups */
+    int32_t C0, C1;             /* channels taken from src0 / src1 (multiples of 8) */
+    int32_t silu;               /* != 0: SiLU behind the normalisation */
+    int32_t sum_ld;             /* row pitch of sum_img in floats */
+    float eps;                  /* forward only */
+    int32_t _pad;
+} mdm_gn_desc;
 
-/* floats the three backward entry points write into `ws` for an [N][P][C] problem of this dtype (0: `ws` may be NULL).  Replaces the
- * sizes quoted in prose above: the entry points cannot check a size they are not given. */
+/* reads src0, src1, gamma, beta; writes y and stats */
+int mdm_groupnorm_fwd(const mdm_gn_desc* desc_host, void* stream);
+/* reads src0, src1, gamma, beta, stats, dy and the add tensors; writes dst0, dst1, sum_img and adds to dgamma, dbeta, sum_all */
+int mdm_groupnorm_bwd(const mdm_gn_desc* desc_host, void* stream);
+
+/* floats mdm_groupnorm_bwd writes into `ws` for an [N][P][C] problem of this dtype (0: `ws` may be NULL): the entry point cannot check
+ * a size it is not given. */
 int64_t mdm_groupnorm_bwd_ws_floats(int dtype, int N, int C);
 
-/* Same, and the column sums of the dx it writes (dx = the complete gradient of a conv output: acc0 == 0, one
- * source): sum_img[n*sum_ld + c] = sum_p dx (the time-embedding gradient, unet6.py:359) and
- * sum_all[c] += sum_{n,p} dx (that conv's bias gradient).  Either may be NULL. */
-int mdm_groupnorm_bwd_sums(int dtype, const void* src0, int C0, const void* src1, int C1,
-                           int N, int P, int G, const float* gamma, const float* beta, int silu,
-                           const void* dy, const float* stats, void* dst0, int acc0, void* dst1, int acc1,
-                           float* dgamma, float* dbeta, float* sum_img, int sum_ld, float* sum_all, float* ws,
-                           void* stream);
-/* The general form: dst = add + dx, where add0 / add1 (NULL = none) are tensors laid out like dst0 / dst1 -- dst itself
- * gives the accumulating form above; another tensor adds the gradient that arrives over a residual branch
- * (x + block(x), unet6.py:333, 362) WITHOUT modifying that tensor, which a later (grouped) weight gradient still reads. */
-int mdm_groupnorm_bwd_add(int dtype, const void* src0, int C0, const void* src1, int C1,
-                          int N, int P, int G, const float* gamma, const float* beta, int silu,
-                          const void* dy, const float* stats, void* dst0, const void* add0, void* dst1, const void* add1,
-                          float* dgamma, float* dbeta, float* sum_img, int sum_ld, float* sum_all, float* ws,
-                          const void* add0b, void* stream);
-
-/* Dropout on a GroupNorm output, fused into the kernels above (nn.Dropout between silu(norm2(.)) and conv2 of a ResidualBlock,
- * unet6.py:354, 360): y = silu?(GN(x)) * keep * scale in the forward, dz = dy * keep * scale right behind the load of dy in the
- * backward -- no extra pass over memory, no stored mask.  Element e = (n*P + p)*C + c has the global index g = base + e (`base`: the
- * caller's running element count of the dropout sites before this one, a multiple of 8); its random word is the 16-bit lane g & 7 of
- * Philox4x32-10(key = rng[0], counter = {g >> 3, rng[1] * 8 + 5}) (lane j = half j & 1 of 32-bit word j >> 1, low half first).
- * ctl = {uint32 thr, float scale} in device memory: an element is kept iff its lane >= thr, kept values are multiplied by scale
- * (thr = clamp(round(rate * 65536), 0, 65535), scale = 65536 / (65536 - thr)), dropped ones are exact zeros; thr == 0 (eval mode:
- * {0, 1.0f}) draws nothing and gives the bits of the plain entry points.  rng = {seed, offset} as for mdm_rng_advance: forward and
- * backward of one step must see the same offset.  One source only (C1 == 0).  Other arguments: mdm_groupnorm_fwd / _bwd_add. */
-int mdm_groupnorm_fwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1,
-                              int N, int P, int G, float eps, const float* gamma, const float* beta,
-                              int silu, void* y, float* stats, float* ws,
-                              const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream);
-int mdm_groupnorm_bwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1,
-                              int N, int P, int G, const float* gamma, const float* beta, int silu,
-                              const void* dy, const float* stats, void* dst0, const void* add0, void* dst1, const void* add1,
-                              float* dgamma, float* dbeta, float* sum_img, int sum_ld, float* sum_all, float* ws,
-                              const void* add0b, const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream);
-/* keep[i] = 1 / 0 for the n consecutive elements from global index `base` on (any base): the mask the two entry points above
- * apply, for tests and debugging. */
+/* keep[i] = 1 / 0 for the n consecutive elements from global index `base` on (any base): the mask a descriptor with this rng / ctl
+ * applies, for tests and debugging. */
 int mdm_dropout_mask(const uint64_t* rng, uint64_t base, const uint32_t* ctl, int64_t n, uint8_t* keep, void* stream);
-/* add0b (NULL = none): a SECOND tensor laid out like dst0 that is added too -- an activation with two forward consumers and a
- * residual join receives dst0 (accumulate) + the residual branch's dY + dx in one pass. */
 
 /* ------------------------------------------------------------------------- *
  * Fused single-head attention of AttentionBlock.qkv (unet6.py:316-324): o = softmax(q k^T * scale) v over L tokens,

@@ -546,12 +546,15 @@ static int gn_cblk(int C, int G, int N, int P) {
 }
 // (A pixel-chunked statistics + apply pair of launches -- MODE 1 / 2 of the register kernels -- was measured no faster
 // than the single launch at cfg2: 13.4 vs 13.7 us forward, 25.3 vs 24.1 us backward on 32x32x128; it is not dispatched.)
-// DROP: the dropout variants of the same kernels (mdm_groupnorm_fwd_dropout); one route choice for both, so a dropout site runs
+// DROP: the dropout variants of the same kernels (desc.rng != NULL); one route choice for both, so a dropout site runs
 // on the kernel its plain GroupNorm runs on
 template <bool DROP>
-static int gn_fwd_dispatch(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                           float eps, const float* gamma, const float* beta, int silu, void* y, float* stats,
-                           float* ws, const uint64_t* rng, uint64_t dbase, const uint32_t* ctl, void* stream) {
+static int gn_fwd_dispatch(const mdm_gn_desc& d, void* stream) {
+    const int dtype = d.dtype, C0 = d.C0, C1 = d.C1, N = d.N, P = d.P, G = d.G, silu = d.silu;
+    const void *src0 = d.src0, *src1 = d.src1;
+    const float eps = d.eps, *gamma = d.gamma, *beta = d.beta;
+    void* y = d.y;
+    float *stats = d.stats, *ws = d.ws;
     if (int rc = gn_check(C0, C1, G, N, P)) return rc;
     const int C = C0 + C1;
     int cblk = gn_cblk(C, G, N, P);
@@ -569,7 +572,7 @@ static int gn_fwd_dispatch(int dtype, const void* src0, int C0, const void* src1
     do {                                                                                                                                             \
         if constexpr (DROP)                                                                                                                          \
             hipLaunchKernelGGL((gn_fwd_reg_kernel_drop<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0,                \
-                               (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws, rng, dbase, ctl);                 \
+                               (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws, d.rng, d.drop_base, d.ctl);       \
         else                                                                                                                                         \
             hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0,                     \
                                (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws);                                  \
@@ -584,7 +587,7 @@ static int gn_fwd_dispatch(int dtype, const void* src0, int C0, const void* src1
     do {                                                                                                                                             \
         if constexpr (DROP)                                                                                                                          \
             hipLaunchKernelGGL((gn_fwd_reg_kernel_drop<NPV, 0, NT, float>), grid, dim3(NT), 0, (hipStream_t)stream, (const float*)src0, C0,          \
-                               (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws, rng, dbase, ctl);                   \
+                               (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws, d.rng, d.drop_base, d.ctl);         \
         else                                                                                                                                         \
             hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT, float>), grid, dim3(NT), 0, (hipStream_t)stream, (const float*)src0, C0,               \
                                (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws);                                    \
@@ -596,28 +599,23 @@ static int gn_fwd_dispatch(int dtype, const void* src0, int C0, const void* src1
     }
     if constexpr (DROP)
         DISPATCH_T(dtype, hipLaunchKernelGGL((gn_fwd_kernel_drop<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
-                                             (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats, rng, dbase, ctl));
+                                             (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats, d.rng, d.drop_base, d.ctl));
     else
         DISPATCH_T(dtype, hipLaunchKernelGGL((gn_fwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
                                              (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats));
     return launch_status("groupnorm_fwd");
 }
-extern "C" int mdm_groupnorm_fwd(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                 float eps, const float* gamma, const float* beta, int silu, void* y, float* stats,
-                                 float* ws, void* stream) {
-    return gn_fwd_dispatch<false>(dtype, src0, C0, src1, C1, N, P, G, eps, gamma, beta, silu, y, stats, ws, nullptr, 0, nullptr, stream);
-}
-static int drop_check(const char* what, int C1, const uint64_t* rng, uint64_t base, const uint32_t* ctl) {
-    MDM_REQUIRE(C1 == 0, "%s: a dropout site has one source (C1=%d)", what, C1);
-    MDM_REQUIRE(rng && ctl, "%s: null rng / ctl", what);
-    MDM_REQUIRE(base % 8 == 0, "%s: base must be a multiple of 8", what);
+static int drop_check(const char* what, const mdm_gn_desc& d) {
+    MDM_REQUIRE(d.C1 == 0, "%s: a dropout site has one source (C1=%d)", what, d.C1);
+    MDM_REQUIRE(d.rng && d.ctl, "%s: null rng / ctl", what);
+    MDM_REQUIRE(d.drop_base % 8 == 0, "%s: base must be a multiple of 8", what);
     return 0;
 }
-extern "C" int mdm_groupnorm_fwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                         float eps, const float* gamma, const float* beta, int silu, void* y, float* stats,
-                                         float* ws, const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream) {
-    if (int rc = drop_check("groupnorm_fwd_dropout", C1, rng, base, ctl)) return rc;
-    return gn_fwd_dispatch<true>(dtype, src0, C0, src1, C1, N, P, G, eps, gamma, beta, silu, y, stats, ws, rng, base, ctl, stream);
+extern "C" int mdm_groupnorm_fwd(const mdm_gn_desc* desc_host, void* stream) {
+    MDM_REQUIRE(desc_host != nullptr, "groupnorm_fwd: null descriptor");
+    if (!desc_host->rng) return gn_fwd_dispatch<false>(*desc_host, stream);
+    if (int rc = drop_check("groupnorm_fwd_dropout", *desc_host)) return rc;
+    return gn_fwd_dispatch<true>(*desc_host, stream);
 }
 extern "C" int mdm_dropout_mask(const uint64_t* rng, uint64_t base, const uint32_t* ctl, int64_t n, uint8_t* keep, void* stream) {
     MDM_REQUIRE(rng && ctl && keep && n > 0 && n < (1ll << 36), "dropout_mask: bad arguments");
@@ -633,11 +631,12 @@ extern "C" int64_t mdm_groupnorm_bwd_ws_floats(int dtype, int N, int C) {
 }
 
 template <bool DROP>
-static int gn_bwd_dispatch(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                           const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
-                           void* dst0, const void* add0, void* dst1, const void* add1, float* dgamma, float* dbeta,
-                           float* sum_img, int sum_ld, float* sum_all, float* ws, const void* add0b,
-                           const uint64_t* rng, uint64_t dbase, const uint32_t* ctl, void* stream) {
+static int gn_bwd_dispatch(const mdm_gn_desc& d, void* stream) {
+    const int dtype = d.dtype, C0 = d.C0, C1 = d.C1, N = d.N, P = d.P, G = d.G, silu = d.silu, sum_ld = d.sum_ld;
+    const void *src0 = d.src0, *src1 = d.src1, *dy = d.dy, *add0 = d.add0, *add0b = d.add0b, *add1 = d.add1;
+    void *dst0 = d.dst0, *dst1 = d.dst1;
+    const float *gamma = d.gamma, *beta = d.beta, *stats = d.stats;
+    float *dgamma = d.dgamma, *dbeta = d.dbeta, *sum_img = d.sum_img, *sum_all = d.sum_all, *ws = d.ws;
     if (int rc = gn_check(C0, C1, G, N, P)) return rc;
     const int C = C0 + C1, cblk = gn_cblk(C, G, N, P);
     MDM_REQUIRE(cblk <= 64 && cblk / (C / G) <= 64, "groupnorm: unsupported channel/group combination C=%d G=%d", C, G);
@@ -650,7 +649,7 @@ static int gn_bwd_dispatch(int dtype, const void* src0, int C0, const void* src1
 #define GN_BWD_REG(NPV, NT)                                                                                                                          \
     do {                                                                                                                                             \
         if constexpr (DROP)                                                                                                                          \
-            hipLaunchKernelGGL((gn_bwd_reg_kernel_drop<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, GN_BWD_ARGS, rng, dbase, ctl);          \
+            hipLaunchKernelGGL((gn_bwd_reg_kernel_drop<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, GN_BWD_ARGS, d.rng, d.drop_base, d.ctl); \
         else                                                                                                                                         \
             hipLaunchKernelGGL((gn_bwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, GN_BWD_ARGS);                                \
     } while (0)
@@ -667,7 +666,7 @@ static int gn_bwd_dispatch(int dtype, const void* src0, int C0, const void* src1
         DISPATCH_T(dtype, hipLaunchKernelGGL((gn_bwd_kernel_drop<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
                                              (const T*)src1, C1, P, G, cblk, gamma, beta, silu, (const T*)dy, stats, (T*)dst0,
                                              (const T*)add0, (T*)dst1, (const T*)add1, (const T*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, part,
-                                             rng, dbase, ctl));
+                                             d.rng, d.drop_base, d.ctl));
     else
         DISPATCH_T(dtype, hipLaunchKernelGGL((gn_bwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
                                              (const T*)src1, C1, P, G, cblk, gamma, beta, silu, (const T*)dy, stats, (T*)dst0,
@@ -676,38 +675,11 @@ static int gn_bwd_dispatch(int dtype, const void* src0, int C0, const void* src1
         hipLaunchKernelGGL(gn_param_reduce_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, part, N, C, dgamma, dbeta, sum_all);
     return launch_status("groupnorm_bwd");
 }
-extern "C" int mdm_groupnorm_bwd_add(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                     const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
-                                     void* dst0, const void* add0, void* dst1, const void* add1, float* dgamma, float* dbeta,
-                                     float* sum_img, int sum_ld, float* sum_all, float* ws, const void* add0b, void* stream) {
-    return gn_bwd_dispatch<false>(dtype, src0, C0, src1, C1, N, P, G, gamma, beta, silu, dy, stats, dst0, add0, dst1, add1, dgamma, dbeta,
-                                  sum_img, sum_ld, sum_all, ws, add0b, nullptr, 0, nullptr, stream);
-}
-extern "C" int mdm_groupnorm_bwd_dropout(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                         const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
-                                         void* dst0, const void* add0, void* dst1, const void* add1, float* dgamma, float* dbeta,
-                                         float* sum_img, int sum_ld, float* sum_all, float* ws, const void* add0b,
-                                         const uint64_t* rng, uint64_t base, const uint32_t* ctl, void* stream) {
-    if (int rc = drop_check("groupnorm_bwd_dropout", C1, rng, base, ctl)) return rc;
-    return gn_bwd_dispatch<true>(dtype, src0, C0, src1, C1, N, P, G, gamma, beta, silu, dy, stats, dst0, add0, dst1, add1, dgamma, dbeta,
-                                 sum_img, sum_ld, sum_all, ws, add0b, rng, base, ctl, stream);
-}
-
-extern "C" int mdm_groupnorm_bwd_sums(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                      const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
-                                      void* dst0, int acc0, void* dst1, int acc1, float* dgamma, float* dbeta,
-                                      float* sum_img, int sum_ld, float* sum_all, float* ws, void* stream) {
-    MDM_REQUIRE(!(sum_img || sum_all) || acc0 == 0, "groupnorm_bwd_sums: column sums need a plain (non-accumulating) dx");
-    return mdm_groupnorm_bwd_add(dtype, src0, C0, src1, C1, N, P, G, gamma, beta, silu, dy, stats, dst0, acc0 ? dst0 : nullptr,
-                                 dst1, acc1 ? dst1 : nullptr, dgamma, dbeta, sum_img, sum_ld, sum_all, ws, nullptr, stream);
-}
-
-extern "C" int mdm_groupnorm_bwd(int dtype, const void* src0, int C0, const void* src1, int C1, int N, int P, int G,
-                                 const float* gamma, const float* beta, int silu, const void* dy, const float* stats,
-                                 void* dst0, int acc0, void* dst1, int acc1, float* dgamma, float* dbeta, float* ws,
-                                 void* stream) {
-    return mdm_groupnorm_bwd_sums(dtype, src0, C0, src1, C1, N, P, G, gamma, beta, silu, dy, stats, dst0, acc0, dst1, acc1,
-                                  dgamma, dbeta, nullptr, 0, nullptr, ws, stream);
+extern "C" int mdm_groupnorm_bwd(const mdm_gn_desc* desc_host, void* stream) {
+    MDM_REQUIRE(desc_host != nullptr, "groupnorm_bwd: null descriptor");
+    if (!desc_host->rng) return gn_bwd_dispatch<false>(*desc_host, stream);
+    if (int rc = drop_check("groupnorm_bwd_dropout", *desc_host)) return rc;
+    return gn_bwd_dispatch<true>(*desc_host, stream);
 }
 
 #ifdef MDM_STAMP

@@ -37,6 +37,19 @@ class GemmDesc(C.Structure):
         ("gnf_out", vp), ("gnf_gamma", vp), ("gnf_beta", vp), ("gnf_stats", vp), ("gnf_G", i32), ("gnf_silu", i32), ("gnf_eps", f32), ("_p4", i32),
         ("B_split", vp),
     ]
+    _defaults = dict(alpha=1.0, batch=1)
+
+
+class GnDesc(C.Structure):
+    """Mirror of `mdm_gn_desc` (include/mdm_hip.h)."""
+    _fields_ = [
+        ("src0", vp), ("src1", vp), ("gamma", vp), ("beta", vp), ("stats", vp), ("ws", vp), ("y", vp),
+        ("dy", vp), ("dst0", vp), ("add0", vp), ("add0b", vp), ("dst1", vp), ("add1", vp), ("dgamma", vp), ("dbeta", vp),
+        ("sum_img", vp), ("sum_all", vp), ("rng", vp), ("drop_base", u64), ("ctl", vp),
+        ("dtype", i32), ("N", i32), ("P", i32), ("G", i32), ("C0", i32), ("C1", i32), ("silu", i32), ("sum_ld", i32),
+        ("eps", f32), ("_pad", i32),
+    ]
+    _defaults = {}
 
 
 _PROTOS = {
@@ -55,14 +68,9 @@ _PROTOS = {
     "mdm_gemm_route_of": ([C.POINTER(GemmDesc)], C.c_char_p),
     "mdm_gemm_pair_route_of": ([C.POINTER(GemmDesc), C.POINTER(GemmDesc)], C.c_char_p),
     "mdm_gemm_route_names": ([C.POINTER(C.c_char_p), i32], i32),
-    "mdm_groupnorm_fwd": ([i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, vp, vp], i32),
-    "mdm_groupnorm_bwd": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp], i32),
-    "mdm_groupnorm_bwd_sums": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp], i32),
+    "mdm_groupnorm_fwd": ([C.POINTER(GnDesc), vp], i32),
+    "mdm_groupnorm_bwd": ([C.POINTER(GnDesc), vp], i32),
     "mdm_groupnorm_bwd_ws_floats": ([i32, i32, i32], i64),
-    "mdm_groupnorm_bwd_add": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp], i32),
-    "mdm_groupnorm_fwd_dropout": ([i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, i32, vp, vp, vp, vp, u64, vp, vp], i32),
-    "mdm_groupnorm_bwd_dropout": ([i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
-                                   vp, u64, vp, vp], i32),
     "mdm_dropout_mask": ([vp, u64, vp, i64, vp, vp], i32),
     "mdm_attn_supported": ([i32, i32, i32], i32),
     "mdm_attn_fwd": ([i32, vp, vp, vp, i32, i32, i32, f32, vp], i32),
@@ -309,10 +317,9 @@ def torch_dtype(dt):
     return torch.float32 if dt == F32 else torch.bfloat16
 
 
-def _desc(kw):
-    d = GemmDesc()
-    d.alpha = 1.0
-    d.batch = 1
+def _desc(kw, cls=GemmDesc):
+    """A `cls` descriptor from keyword fields: tensors become device pointers, None a null pointer, the rest stays zero."""
+    d = cls(**cls._defaults)
     for k, v in kw.items():
         if isinstance(v, torch.Tensor):
             v = v.data_ptr()
@@ -451,4 +458,13 @@ def gemm(**kw):
         # algorithmic FLOPs of this launch, keyed by its index in the recording (bench.py roofline)
         _recording.flops[len(_recording.calls)] = (flops if flops is not None else 2.0 * d.M * d.N * d.K * d.batch, d.dtype)
     call("mdm_gemm", C.byref(d), stream())
+    return d
+
+
+def groupnorm(name, **kw):
+    """Fill a `GnDesc` from keyword fields like `gemm()` and launch / record `name` (mdm_groupnorm_fwd | mdm_groupnorm_bwd)."""
+    d = _desc(kw, GnDesc)
+    if _recording is not None:
+        _recording.keep.append((d, kw))
+    call(name, C.byref(d), stream())
     return d

@@ -264,25 +264,40 @@ def silu_bwd_sum(pre, slabs, nslab, n, dx):
     call("mdm_silu_bwd_sum", ptr(pre), ptr(slabs), nslab, n, ptr(dx), stream())
 
 
+def _gn_fields(dt, src0, C0, src1, C1, N, P, G, gamma, beta, silu, stats, ws, drop=None, **rest):
+    """`mdm_gn_desc` fields: the ones both directions share, then `rest`.  `drop` = (rng, base, ctl) of a dropout site; a site without
+    rng is refused here, because a null rng in the descriptor means a plain GroupNorm."""
+    f = dict(rest, dtype=dt, src0=src0, C0=C0, src1=src1, C1=C1, N=N, P=P, G=G, gamma=gamma, beta=beta, silu=int(silu), stats=stats, ws=ws)
+    if drop is not None:
+        if drop[0] is None:
+            raise RuntimeError("groupnorm dropout: null rng / ctl")
+        f.update(rng=drop[0], drop_base=int(drop[1]), ctl=drop[2])
+    return f
+
+
+def _groupnorm_bwd(what, f, dst0, acc0, add0, dst1=None, acc1=0, add1=None):
+    """Launch the backward of the fields `f` with dst = (acc ? dst : add or 0) + dx: the workspace check and the acc / add -> add0 /
+    add0b / add1 mapping of both backward wrappers."""
+    need, ws = _lib.load().mdm_groupnorm_bwd_ws_floats(f["dtype"], f["N"], f["C0"] + f["C1"]), f["ws"]
+    if need and (ws is None or ws.numel() < need):
+        raise ValueError(f"{what}: workspace of {0 if ws is None else ws.numel()} floats, {need} needed")
+    assert not (acc1 and add1 is not None), f"{what}: the second source takes one addend"
+    _lib.groupnorm("mdm_groupnorm_bwd", dst0=dst0, add0=dst0 if acc0 else add0,
+                   add0b=add0 if acc0 else None,            # accumulate AND a pending addend: both are added
+                   dst1=dst1, add1=dst1 if acc1 else add1, **f)
+
+
 def groupnorm_fwd(dt, src0, C0, src1, C1, N, P, gamma, beta, silu, y, stats, ws, G=32, eps=1e-6):
-    call("mdm_groupnorm_fwd", dt, ptr(src0), C0, ptr(src1), C1, N, P, G, eps, ptr(gamma), ptr(beta), int(silu),
-         ptr(y), ptr(stats), ptr(ws), stream())
+    _lib.groupnorm("mdm_groupnorm_fwd", **_gn_fields(dt, src0, C0, src1, C1, N, P, G, gamma, beta, silu, stats, ws, y=y, eps=eps))
 
 
 def groupnorm_bwd(dt, src0, C0, src1, C1, N, P, gamma, beta, silu, dy, stats, dst0, acc0, dst1, acc1,
                   dgamma, dbeta, ws, G=32, sum_img=None, sum_ld=0, sum_all=None, add0=None, add1=None):
     """dst = (acc ? dst : add or 0) + dx.  add0 / add1: tensors laid out like dst0 / dst1 that are added without being
     modified (the gradient arriving over a residual branch)."""
-    need = _lib.load().mdm_groupnorm_bwd_ws_floats(dt, N, C0 + C1)
-    if need and (ws is None or ws.numel() < need):
-        raise ValueError(f"groupnorm_bwd: workspace of {0 if ws is None else ws.numel()} floats, {need} needed")
-    a0 = dst0 if acc0 else add0
-    a0b = add0 if acc0 else None            # accumulate AND a pending addend: both are added
-    assert not (acc1 and add1 is not None), "groupnorm_bwd: the second source takes one addend"
-    a1 = dst1 if acc1 else add1
-    call("mdm_groupnorm_bwd_add", dt, ptr(src0), C0, ptr(src1), C1, N, P, G, ptr(gamma), ptr(beta), int(silu), ptr(dy),
-         ptr(stats), ptr(dst0), ptr(a0), ptr(dst1), ptr(a1), ptr(dgamma), ptr(dbeta), ptr(sum_img), sum_ld,
-         ptr(sum_all), ptr(ws), ptr(a0b), stream())
+    f = _gn_fields(dt, src0, C0, src1, C1, N, P, G, gamma, beta, silu, stats, ws, dy=dy, dgamma=dgamma, dbeta=dbeta,
+                   sum_img=sum_img, sum_ld=sum_ld, sum_all=sum_all)
+    _groupnorm_bwd("groupnorm_bwd", f, dst0, acc0, add0, dst1, acc1, add1)
 
 
 def dropout_ctl_words(rate):
@@ -293,23 +308,18 @@ def dropout_ctl_words(rate):
 
 
 def groupnorm_fwd_dropout(dt, src0, C0, N, P, gamma, beta, silu, y, stats, ws, rng, base, ctl, G=32, eps=1e-6):
-    """groupnorm_fwd of ONE source with y *= keep * scale (mdm_groupnorm_fwd_dropout): rng = int64[2] {seed, offset}, base = the
+    """groupnorm_fwd of ONE source with y *= keep * scale (mdm_gn_desc.rng / drop_base / ctl): rng = int64[2] {seed, offset}, base = the
     site's first global element index, ctl = int32[2] holding {thr, bits of the fp32 scale} -- all three in device memory."""
-    call("mdm_groupnorm_fwd_dropout", dt, ptr(src0), C0, None, 0, N, P, G, eps, ptr(gamma), ptr(beta), int(silu),
-         ptr(y), ptr(stats), ptr(ws), ptr(rng), int(base), ptr(ctl), stream())
+    _lib.groupnorm("mdm_groupnorm_fwd", **_gn_fields(dt, src0, C0, None, 0, N, P, G, gamma, beta, silu, stats, ws, (rng, base, ctl),
+                                                     y=y, eps=eps))
 
 
 def groupnorm_bwd_dropout(dt, src0, C0, N, P, gamma, beta, silu, dy, stats, dst0, acc0, dgamma, dbeta, ws, rng, base, ctl, G=32,
                           sum_img=None, sum_ld=0, sum_all=None, add0=None):
-    """groupnorm_bwd of ONE source on dz = dy * keep * scale (mdm_groupnorm_bwd_dropout); the mask is drawn again from (rng, base)."""
-    need = _lib.load().mdm_groupnorm_bwd_ws_floats(dt, N, C0)
-    if need and (ws is None or ws.numel() < need):
-        raise ValueError(f"groupnorm_bwd_dropout: workspace of {0 if ws is None else ws.numel()} floats, {need} needed")
-    a0 = dst0 if acc0 else add0
-    a0b = add0 if acc0 else None
-    call("mdm_groupnorm_bwd_dropout", dt, ptr(src0), C0, None, 0, N, P, G, ptr(gamma), ptr(beta), int(silu), ptr(dy),
-         ptr(stats), ptr(dst0), ptr(a0), None, None, ptr(dgamma), ptr(dbeta), ptr(sum_img), sum_ld,
-         ptr(sum_all), ptr(ws), ptr(a0b), ptr(rng), int(base), ptr(ctl), stream())
+    """groupnorm_bwd of ONE source on dz = dy * keep * scale; the mask is drawn again from (rng, base)."""
+    f = _gn_fields(dt, src0, C0, None, 0, N, P, G, gamma, beta, silu, stats, ws, (rng, base, ctl), dy=dy, dgamma=dgamma, dbeta=dbeta,
+                   sum_img=sum_img, sum_ld=sum_ld, sum_all=sum_all)
+    _groupnorm_bwd("groupnorm_bwd_dropout", f, dst0, acc0, add0)
 
 
 def dropout_mask(rng, base, ctl, n, keep):

@@ -27,7 +27,8 @@ import torch  # noqa: E402
 
 from bench import make_args  # noqa: E402
 
-GN = ("mdm_groupnorm_fwd", "mdm_groupnorm_bwd_add", "mdm_groupnorm_fwd_dropout", "mdm_groupnorm_bwd_dropout")
+GN = ("mdm_groupnorm_fwd", "mdm_groupnorm_bwd")
+GN_KEYS = GN + tuple(n + "_dropout" for n in GN)      # per_launch reports a launch whose descriptor has rng under NAME_dropout
 CONV = ("mdm_gemm", "mdm_gemm_pair", "mdm_wgrad_group_launch")
 
 
@@ -62,7 +63,7 @@ def per_launch(model, reps=5):
     for rec in (model.forward_plan, model.backward_plan):
         ov = rec.event_overhead(st, lambda i, name: name == "mdm_gemm") if rec is model.forward_plan else sums[0][1]
         runs = [rec.run_timed(st, pick, ov) for _ in range(reps + 1)][1:]
-        names = [rec.calls[i][0] for i, _ in runs[0]]
+        names = [rec.calls[i][0] + ("_dropout" if rec.calls[i][0] in GN and rec.calls[i][2][0]._obj.rng else "") for i, _ in runs[0]]
         med = [statistics.median(r[k][1] for r in runs) for k in range(len(names))]
         sums.append((list(zip(names, med)), ov))
     out = {}
@@ -70,7 +71,7 @@ def per_launch(model, reps=5):
         c, t = out.get(name, (0, 0.0))
         out[name] = (c + 1, t + ms)
     tot = lambda group: (sum(out[n][0] for n in group if n in out), round(sum(out[n][1] for n in group if n in out), 4))
-    return {"groupnorm": dict(zip(("launches", "ms"), tot(GN))), "conv": dict(zip(("launches", "ms"), tot(CONV))),
+    return {"groupnorm": dict(zip(("launches", "ms"), tot(GN_KEYS))), "conv": dict(zip(("launches", "ms"), tot(CONV))),
             "by_entry_point": {k: {"launches": v[0], "ms": round(v[1], 4)} for k, v in sorted(out.items())},
             "event_overhead_ms": round(sums[0][1], 5)}
 

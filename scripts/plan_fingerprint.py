@@ -4,7 +4,7 @@
     python scripts/plan_fingerprint.py OUT.json [--tree DIR] [--only NAME_SUBSTRING]
 
 For every net of the matrix, `forward_plan` and `backward_plan` become a list with one entry per recorded call: the entry
-point and every argument.  `mdm_gemm_desc` arguments are expanded field by field (`GemmDesc._fields_`), a grouped weight
+point and every argument.  `mdm_gemm_desc` / `mdm_gn_desc` arguments are expanded field by field (`_fields_`), a grouped weight
 gradient into the descriptors of its group, `note` entries appear by name only.  A descriptor is written as a dict WITHOUT its
 zero / null fields (a field that is absent is zero), which keeps the file a few megabytes.  Every pointer is rewritten as
 [index of the buffer that holds it, byte offset]; buffers are `net._bufs` in allocation order, then the store's P, G, Pb,
@@ -60,7 +60,7 @@ class Buffers:
 
 def desc_fields(_lib, d, bufs, what):
     out = {}
-    for name, typ in _lib.GemmDesc._fields_:
+    for name, typ in type(d)._fields_:
         v = getattr(d, name)
         if v:
             out[name] = bufs.ref(v, f"{what}.{name}") if typ is _lib.vp else v
@@ -135,8 +135,8 @@ def summary(path):
                         c["sums_by_wgrad"] += "dbias" in d
                     if bwd and nm == "mdm_gemm" and d.get("conv") and "B_split" in d:
                         c["dgrad_split"] += 1
-                if nm == "mdm_groupnorm_bwd_add":
-                    c["sums_by_norm"] += args[21] is not None          # sum_all
+                if nm == "mdm_groupnorm_bwd":
+                    c["sums_by_norm"] += "sum_all" in args[0]
                 if nm == "mdm_colsum" and args[2] > 1 or (nm == "mdm_colsum" and args[5] is not None):
                     c["sums_by_colsum"] += 1                            # a convolution's (the time-embedding path sums ONE image)
                 c["attn_fused"] += nm == "mdm_attn_fwd"

@@ -138,13 +138,21 @@ def test_plan_of_a_dropout_net():
 
 
 # ----------------------------------------------------------------------------- 5: the C ABI
-NEW_SYMBOLS = ("mdm_groupnorm_fwd_dropout", "mdm_groupnorm_bwd_dropout", "mdm_dropout_mask")
+DROP_FIELDS = ("rng", "drop_base", "ctl")       # of mdm_gn_desc: non-null rng selects the dropout kernels of both GroupNorm entry points
 
 
 def test_header_declares_and_library_exports_the_new_symbols():
     from mdm import _lib
     header = open(os.path.join(ROOT, "include", "mdm_hip.h")).read()
     lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"^int " + name + r"\(", header, re.M), name
+    assert re.search(r"^int mdm_dropout_mask\(", header, re.M)
+    assert "mdm_dropout_mask" in _lib.EXPORTS and lib.mdm_dropout_mask is not None
+    struct = re.search(r"typedef struct mdm_gn_desc \{(.*?)\} mdm_gn_desc;", header, re.S).group(1)
+    fields = dict(_lib.GnDesc._fields_)
+    decls = (r"const uint64_t\* rng;", r"uint64_t drop_base;", r"const uint32_t\* ctl;")
+    for name, ctype, decl in zip(DROP_FIELDS, (_lib.vp, _lib.u64, _lib.vp), decls):
+        assert re.search(r"^\s*" + decl, struct, re.M), name
+        assert fields[name] is ctype, name
+    for name in ("mdm_groupnorm_fwd", "mdm_groupnorm_bwd"):
+        assert re.search(r"^int " + name + r"\(const mdm_gn_desc\* desc_host, void\* stream\);", header, re.M), name
         assert name in _lib.EXPORTS and getattr(lib, name) is not None

@@ -31,18 +31,127 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_descriptor_layout_matches_the_header(tmp_path):
-    from mdm._lib import GemmDesc
+    """mdm_gemm_desc at a sample of offsets; mdm_gn_desc completely: sizeof, then offset and size of EVERY field of GnDesc against
+    the header as a C compiler lays it out, and the field sizes add up to sizeof: no implicit padding, and no member that only one
+    side has."""
+    from mdm._lib import GemmDesc, GnDesc
+    gn = [name for name, _ in GnDesc._fields_]
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu",'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu\\n",'
                    'sizeof(mdm_gemm_desc),offsetof(mdm_gemm_desc,A),offsetof(mdm_gemm_desc,conv),offsetof(mdm_gemm_desc,src0),'
-                   'offsetof(mdm_gemm_desc,D0),offsetof(mdm_gemm_desc,bias),offsetof(mdm_gemm_desc,dtap));return 0;}\n'
-                   % os.path.join(ROOT, "include", "mdm_hip.h"))
+                   'offsetof(mdm_gemm_desc,D0),offsetof(mdm_gemm_desc,bias),offsetof(mdm_gemm_desc,dtap));\n'
+                   'printf("%%zu\\n",sizeof(mdm_gn_desc));\n%sreturn 0;}\n'
+                   % (os.path.join(ROOT, "include", "mdm_hip.h"),
+                      "".join('printf("%s %%zu %%zu\\n",offsetof(mdm_gn_desc,%s),sizeof(((mdm_gn_desc*)0)->%s));\n' % (f, f, f) for f in gn)))
     exe = tmp_path / "sz"
     subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
-    got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
+    got = [int(v) for v in lines[0].split()]
     want = [ctypes.sizeof(GemmDesc), GemmDesc.A.offset, GemmDesc.conv.offset, GemmDesc.src0.offset, GemmDesc.D0.offset,
             GemmDesc.bias.offset, GemmDesc.dtap.offset]
     assert got == want
+    assert int(lines[1]) == ctypes.sizeof(GnDesc)
+    c_fields = [(ln.split()[0], int(ln.split()[1]), int(ln.split()[2])) for ln in lines[2:]]
+    assert c_fields == [(f, getattr(GnDesc, f).offset, getattr(GnDesc, f).size) for f in gn]
+    assert sum(size for _, _, size in c_fields) == int(lines[1]) == sum(getattr(GnDesc, f).size for f in gn)
+
+
+def _gn_desc(**kw):
+    """A descriptor both GroupNorm entry points would accept (fake non-null pointers: never dereferenced on the host), then `kw`."""
+    from mdm import _lib
+    f = dict(dtype=_lib.BF16, N=2, P=16, G=32, C0=64, C1=0, silu=1, eps=1e-6, src0=16, gamma=16, beta=16, stats=16, y=16,
+             dy=16, dst0=16, dgamma=16, dbeta=16)
+    f.update(kw)
+    return _lib._desc(f, _lib.GnDesc)
+
+
+FWD, BWD = "mdm_groupnorm_fwd", "mdm_groupnorm_bwd"
+DROP = dict(rng=16, ctl=16, drop_base=8)
+GN_REFUSALS = [      # descriptor fields, entry points, substring of mdm_last_error
+    (dict(dtype=7), (FWD, BWD), "bad dtype"),
+    (dict(C0=60), (FWD, BWD), "channel counts must be multiples of 8"),
+    (dict(C0=64, C1=8, src1=16, dst1=16), (FWD, BWD), "not divisible by G"),
+    (dict(N=0), (FWD, BWD), "bad N/P"),
+    (dict(C0=32, C1=32, src1=16, dst1=16, sum_all=16), (BWD,), "column sums need a single-source dx"),
+    (dict(dtype=0, N=1, C0=32, P=2304), (BWD,), "the fp32 path needs ws"),
+    (dict(DROP, C0=32, C1=32, src1=16, dst1=16), (FWD, BWD), "a dropout site has one source"),
+    (dict(DROP, ctl=None), (FWD, BWD), "null rng / ctl"),
+    (dict(DROP, drop_base=2 ** 33 + 4), (FWD, BWD), "base must be a multiple of 8"),
+]
+
+
+@pytest.mark.parametrize("fields,entries,message", GN_REFUSALS, ids=[m for _, _, m in GN_REFUSALS])
+def test_groupnorm_refuses_bad_descriptors_on_the_host(fields, entries, message):
+    """Every argument check of the two GroupNorm entry points runs before their first launch: the descriptors below come back
+    non-zero with their message on a box without a device (and nothing is launched on one that has a device)."""
+    from mdm import _lib
+    lib = _lib.load()
+    for name in entries:
+        d = _gn_desc(**fields)
+        assert getattr(lib, name)(ctypes.byref(d), None) != 0, name
+        assert message in lib.mdm_last_error().decode(), (name, lib.mdm_last_error().decode())
+
+
+def test_groupnorm_refuses_a_null_descriptor():
+    from mdm import _lib
+    lib = _lib.load()
+    for name in (FWD, BWD):
+        assert getattr(lib, name)(None, None) != 0
+        assert "null descriptor" in lib.mdm_last_error().decode()
+
+
+def test_groupnorm_wrappers_fill_the_descriptor():
+    """What ops.groupnorm_* record (nothing launches inside a Recording): the accumulate / addend arguments become add0 / add0b /
+    add1 as the C ABI defines them, drop_base keeps its 64 bits, eps defaults to 1e-6."""
+    from mdm import _lib, ops
+    src0, src1, gamma, beta, dy, stats, dst0, dst1, pend, pend1, dgamma, dbeta, rng, ctl, y = ts = [torch.empty(8) for _ in range(15)]
+    assert len({t.data_ptr() for t in ts}) == len(ts)
+    p = lambda t: None if t is None else t.data_ptr()
+
+    def bwd(acc0, add0, acc1=0, add1=None, two=True, drop=False):
+        with _lib.Recording() as rec:
+            if drop:
+                ops.groupnorm_bwd_dropout(_lib.BF16, src0, 64, 2, 16, gamma, beta, 1, dy, stats, dst0, acc0, dgamma, dbeta, None,
+                                          rng, 2 ** 33 + 8, ctl, add0=add0, sum_ld=7)
+            else:
+                ops.groupnorm_bwd(_lib.BF16, src0, 32, src1 if two else None, 32 if two else 0, 2, 16, gamma, beta, 1, dy, stats,
+                                  dst0, acc0, dst1 if two else None, acc1, dgamma, dbeta, None, add0=add0, add1=add1)
+        (name, _, args), = rec.calls
+        assert name == BWD
+        d = args[0]._obj
+        assert any(k[0] is d for k in rec.keep if isinstance(k, tuple))       # the recording owns the descriptor
+        return d
+
+    for drop in (False, True):
+        d = bwd(1, None, drop=drop)                 # accumulate, no addend
+        assert (d.dst0, d.add0, d.add0b) == (p(dst0), p(dst0), None)
+        d = bwd(1, pend, drop=drop)                 # accumulate and a pending addend
+        assert (d.dst0, d.add0, d.add0b) == (p(dst0), p(dst0), p(pend))
+        d = bwd(0, pend, drop=drop)                 # overwrite, pending addend
+        assert (d.dst0, d.add0, d.add0b) == (p(dst0), p(pend), None)
+        d = bwd(0, None, drop=drop)                 # overwrite
+        assert (d.dst0, d.add0, d.add0b) == (p(dst0), None, None)
+    assert (d.rng, d.drop_base, d.ctl, d.sum_ld, d.C1, d.dst1, d.add1) == (p(rng), 2 ** 33 + 8, p(ctl), 7, 0, None, None)
+    assert (bwd(0, None).rng, bwd(0, None).drop_base, bwd(0, None).ctl) == (None, 0, None)
+    d = bwd(0, None, acc1=1)
+    assert (d.dst1, d.add1) == (p(dst1), p(dst1))
+    d = bwd(0, None, add1=pend1)
+    assert (d.dst1, d.add1) == (p(dst1), p(pend1))
+    with pytest.raises(AssertionError, match="one addend"):
+        bwd(0, None, acc1=1, add1=pend1)
+    d = bwd(0, None, two=False)                     # one source: a null dst1 is legal
+    assert (d.C1, d.src1, d.dst1, d.add1) == (0, None, None, None)
+    assert (d.src0, d.gamma, d.beta, d.dy, d.stats, d.dgamma, d.dbeta, d.ws) == \
+           tuple(map(p, (src0, gamma, beta, dy, stats, dgamma, dbeta, None)))
+    assert (d.dtype, d.N, d.P, d.G, d.C0, d.silu) == (_lib.BF16, 2, 16, 32, 32, 1)
+    with _lib.Recording() as rec:
+        ops.groupnorm_fwd(_lib.F32, src0, 32, src1, 32, 2, 16, gamma, beta, 0, y, stats, None)
+        ops.groupnorm_fwd_dropout(_lib.F32, src0, 64, 2, 16, gamma, beta, 1, y, stats, None, rng, 2 ** 33 + 8, ctl)
+    (n0, _, a0), (n1, _, a1) = rec.calls
+    d0, d1 = a0[0]._obj, a1[0]._obj
+    assert n0 == n1 == FWD and d0.eps == d1.eps == ctypes.c_float(1e-6).value
+    assert (d0.y, d0.src1, d0.C1, d0.rng, d0.silu) == (p(y), p(src1), 32, None, 0)
+    assert (d1.y, d1.src1, d1.C1, d1.rng, d1.drop_base, d1.ctl, d1.silu) == (p(y), None, 0, p(rng), 2 ** 33 + 8, p(ctl), 1)
 
 
 def test_errors_come_back_as_exceptions_not_crashes():
