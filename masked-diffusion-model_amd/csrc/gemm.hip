@@ -3493,65 +3493,6 @@ constexpr int kBigMinTiles = 200;      // a tile shape is used when it still yie
 constexpr int kWgradBlocks = 256;      // per-layer weight-gradient launch (mdm_gemm): aim at this many workgroups
 constexpr int kWgradMinSlabs = 4;      // ... of at least this many 64-deep k-slabs each
 
-// ---- route record (mdm_gemm_last_route): which kernel and which second stage the last call on this host thread launched.
-// One table: X(enum, kernel name, second stages it can take: T = tap-split epilogue, K = split-K reduce).  A route is
-// kernel * 3 + stage; the names of all three stages exist, mdm_gemm_route_names lists the ones the mask allows.
-enum RouteStage { S_NONE = 0, S_TAPSPLIT = 1, S_SPLITK = 2 };
-constexpr int TSPLIT = 1 << S_TAPSPLIT, KSPLIT = 1 << S_SPLITK;
-#define MDM_GEMM_ROUTES(X)                                                                                                      \
-    X(R_SKINNY_F32, "linear_skinny_f32", 0) X(R_TN_SKINNY_F32, "tn_skinny_f32", 0)                                              \
-    X(R_LIN_SPLIT_128, "lin_split<128>", 0) X(R_LIN_SPLIT_64, "lin_split<64>", 0)                                               \
-    X(R_HS_256_6_32, "halo<256,6,2,32,f32,split>", 0) X(R_HS_256_6_128, "halo<256,6,4,128,f32,split>", 0)                       \
-    X(R_HS_MIXED, "halo_mixed<256|128,f32,split>", 0) X(R_HS_256_6, "halo<256,6,NSB,64,f32,split>", 0)                          \
-    X(R_HS_128_3, "halo<128,3,3,64,f32,split>", 0) X(R_HS_128_4, "halo<128,4,3,64,f32,split>", 0)                               \
-    X(R_HS_128_6, "halo<128,6,3,64,f32,split>", 0)                                                                              \
-    X(R_HS_64_2_32, "halo<64,2,3,32,f32,split>", 0) X(R_HS_64_3_32, "halo<64,3,3,32,f32,split>", 0)                             \
-    X(R_HS_64_2_64, "halo<64,2,3,64,f32,split>", 0) X(R_HS_64_3_64, "halo<64,3,3,64,f32,split>", 0)                             \
-    X(R_HF_256_6, "halo<256,6,2,64,f32>", 0) X(R_HF_128_3, "halo<128,3,3,64,f32>", 0)                                           \
-    X(R_HF_128_4, "halo<128,4,3,64,f32>", 0) X(R_HF_128_6, "halo<128,6,3,64,f32>", 0)                                           \
-    X(R_HF_64_2_32, "halo<64,2,3,32,f32>", 0) X(R_HF_64_3_32, "halo<64,3,3,32,f32>", 0)                                         \
-    X(R_HF_64_2_64, "halo<64,2,3,64,f32>", 0) X(R_HF_64_3_64, "halo<64,3,3,64,f32>", 0)                                         \
-    X(R_F32_128, "f32_mfma<128>", KSPLIT) X(R_F32_128_SPLIT, "f32_mfma<128,split>", KSPLIT) X(R_F32_64, "f32_mfma<64>", KSPLIT) \
-    X(R_THIN_1, "conv_thin_k<1>", 0) X(R_THIN_2, "conv_thin_k<2>", 0) X(R_THIN_4, "conv_thin_k<4>", 0)                          \
-    X(R_THIN_8, "conv_thin_k<8>", 0)                                                                                            \
-    X(R_H256_6, "halo<256,6,NSB,64>", 0)                                                                                        \
-    X(R_H128_3, "halo<128,3,3,64>", 0) X(R_H128_4, "halo<128,4,3,64>", 0) X(R_H128_6, "halo<128,6,3,64>", 0)                    \
-    X(R_H64_2_32, "halo<64,2,3,32>", 0) X(R_H64_3_32, "halo<64,3,3,32>", 0)                                                     \
-    X(R_H64_2_64, "halo<64,2,3,64>", 0) X(R_H64_3_64, "halo<64,3,3,64>", 0)                                                     \
-    X(R_SMALL_4, "conv_small<4,64,32>", 0) X(R_SMALL_5, "conv_small<5,64,32>", 0)                                               \
-    X(R_SMALL_3, "conv_small<3,32,16>", 0)                                                                                      \
-    X(R_LIN2_128, "lin2<128,128>", 0) X(R_LIN2_64x128, "lin2<64,128>", TSPLIT) X(R_LIN2_64, "lin2<64,64>", TSPLIT)              \
-    X(R_WGRAD_LIN_128, "wgrad_lin<128>", KSPLIT) X(R_WGRAD_LIN_64, "wgrad_lin<64>", KSPLIT)                                     \
-    X(R_RING_128, "ring<128>", KSPLIT) X(R_RING_64, "ring<64>", TSPLIT | KSPLIT)                                                \
-    X(R_BF16_128, "bf16<128>", KSPLIT) X(R_BF16_64, "bf16<64>", KSPLIT)                                                         \
-    X(R_PAIR_SMALL_4, "pair_small<4>", 0) X(R_PAIR_SMALL_5, "pair_small<5>", 0)                                                 \
-    X(R_PAIR_SMALL_3, "pair_small<3,32,16>", 0)                                                                                 \
-    X(R_PAIR_64_2, "pair<halo<64,2,3,32>,lin2<64,64>>", 0) X(R_PAIR_64_3, "pair<halo<64,3,3,32>,lin2<64,64>>", 0)               \
-    X(R_PAIR_128_L64x128, "pair<halo<128,3,3,64>,lin2<64,128>>", 0)                                                             \
-    X(R_PAIR_128_L64, "pair<halo<128,3,3,64>,lin2<64,64>>", 0)                                                                  \
-    X(R_PAIR_256_L128, "pair<halo<256,6,NSB,64>,lin2<128,128>>", 0)                                                             \
-    X(R_PAIR_TWO, "pair:two launches", 0)                                                                                       \
-    X(R_WGROUP, "wgrad_group", KSPLIT) X(R_WGROUP_TAPS, "wgrad_taps_group", KSPLIT)
-enum GemmRoute {
-#define MDM_ROUTE_ENUM(e, n, m) e,
-    MDM_GEMM_ROUTES(MDM_ROUTE_ENUM)
-#undef MDM_ROUTE_ENUM
-    R_COUNT
-};
-static const char* const kRouteName[R_COUNT * 3] = {
-#define MDM_ROUTE_NAME(e, n, m) n, n "+tapsplit", n "+splitk",
-    MDM_GEMM_ROUTES(MDM_ROUTE_NAME)
-#undef MDM_ROUTE_NAME
-};
-static const int kRouteStages[R_COUNT] = {
-#define MDM_ROUTE_MASK(e, n, m) 1 | (m),
-    MDM_GEMM_ROUTES(MDM_ROUTE_MASK)
-#undef MDM_ROUTE_MASK
-};
-static thread_local int g_route = -1;
-static inline void route(GemmRoute r) { g_route = 3 * r; }
-static inline void route_stage(RouteStage st) { if (g_route >= 0) g_route = g_route / 3 * 3 + st; }
-
 // Opt KERNEL in to `bytes` of dynamic LDS.  One high-water mark per kernel instantiation, process-wide (one process drives one
 // device): hipFuncSetAttribute runs on the first launch and when a later launch asks for more, never once per launch -- so it
 // falls into the eager warm-up call of an instantiation, not into a graph capture.
@@ -3565,6 +3506,23 @@ static int lds_opt_in(int bytes) {
     return 0;
 }
 
+// What mdm_gemm decides before it launches: the tile family, the reduction split, where split-K partials go.
+struct Resolved {
+    mdm_gemm_desc d;
+    bool big, tap_split;
+    int zouter;
+    int64_t tiles, slab;        // output tiles of the chosen shape; bytes of one dense fp32 copy of the output
+};
+// The grid of a launch: tiles of the shape resolve chose -- or of the BM x BN shape a route took instead -- by the batch / tap / split count
+static dim3 grid_of(const Resolved& r) { return dim3((unsigned)r.tiles, 1, (unsigned)(r.zouter * r.d.splitk)); }
+template <int BM, int BN>
+static dim3 grid_of(const Resolved& r) {
+    return dim3((unsigned)((int64_t)cdiv(r.d.M, BM) * cdiv(r.d.N, BN)), 1, (unsigned)(r.zouter * r.d.splitk));
+}
+// LDS floor of the fused GroupNorm-backward epilogue (epilogue_tile_gnb, 64-pixel tiles): the fp32 tile (16 KiB), the column-sum
+// scratch [32 quantities][512] behind it (64 KiB), the partial sums [32 x 8 columns][4 parts] (4 KiB), the group sums [4][16][2] (512 B)
+constexpr int kGnbLdsBytes = 16384 + 65536 + 4096 + 512;
+
 template <int BM, int BN, int LAYOUT, int NSTAGE, bool CONV>
 static int launch_ring_one(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
     constexpr int bytes = NSTAGE * (BM + BN) * 64 * 2;
@@ -3573,7 +3531,9 @@ static int launch_ring_one(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
     return 0;
 }
 template <int BM, int BN, int NSTAGE>
-static int launch_ring(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
+static int launch_ring(const Resolved& r, hipStream_t s) {
+    const mdm_gemm_desc& d = r.d;
+    const dim3 grid = grid_of(r);
     const bool c = d.conv != 0;
     switch (d.layout) {
         case 0: return c ? launch_ring_one<BM, BN, 0, NSTAGE, true>(d, grid, s) : launch_ring_one<BM, BN, 0, NSTAGE, false>(d, grid, s);
@@ -3586,22 +3546,24 @@ static int launch_ring(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
 template <int BM, int BN, int NSTAGE>
 static int lin2_lds_bytes(const mdm_gemm_desc& d) {
     int bytes = NSTAGE * (BM + BN) * 64 * 2;
-    if (d.gnb_x && bytes < 16384 + 65536 + 4096 + 512) bytes = 16384 + 65536 + 4096 + 512;      // fused GroupNorm backward (64 x 64 tiles)
-    return bytes;
+    return d.gnb_x && bytes < kGnbLdsBytes ? kGnbLdsBytes : bytes;      // fused GroupNorm backward (64 x 64 tiles)
 }
 template <int BM, int BN, int NSTAGE, int WR, int WC>
-static int launch_lin2(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {         // the software-pipelined variant
+static int launch_lin2(const Resolved& r, hipStream_t s) {         // the software-pipelined variant
+    const mdm_gemm_desc& d = r.d;
     const int bytes = lin2_lds_bytes<BM, BN, NSTAGE>(d);
+    const dim3 grid = BM == 64 && BN == 128 ? grid_of<64, 128>(r) : grid_of(r);      // (64 x 128 is not a tile shape of resolve)
     if (int rc = lds_opt_in<&conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>>(bytes)) return rc;
     hipLaunchKernelGGL((conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>), grid, dim3(64 * WR * WC), bytes, s, d);
     return 0;
 }
 
 template <int BM, int BN, int NSTAGE, int NW>
-static int launch_wgrad_lin(const mdm_gemm_desc& d, int tiles_x, int items, hipStream_t s) {
+static int launch_wgrad_lin(const Resolved& r, hipStream_t s) {      // a flat grid: one work item per (tile, tap / split)
     constexpr int bytes = NSTAGE * (BM + BN) * 64 * 2;
+    const dim3 g = grid_of(r);
     if (int rc = lds_opt_in<&wgrad_lin_kernel<BM, BN, NSTAGE, NW>>(bytes)) return rc;
-    hipLaunchKernelGGL((wgrad_lin_kernel<BM, BN, NSTAGE, NW>), dim3((unsigned)items), dim3(64 * NW), bytes, s, d, tiles_x);
+    hipLaunchKernelGGL((wgrad_lin_kernel<BM, BN, NSTAGE, NW>), dim3((unsigned)(int)(g.x * g.z)), dim3(64 * NW), bytes, s, r.d, (int)g.x);
     return 0;
 }
 static bool wgrad_lin_eligible(const mdm_gemm_desc& d) {
@@ -3637,11 +3599,14 @@ template <int BM, int NSB, int BN, int TG>
 static int halo_lds_bytes(const mdm_gemm_desc& d) {
     int bytes = 2 * halo_pieces(BM, d.OH, d.OW) * 1024 + NSB * TG * BN * 128 + 1024;
     if (bytes < BM * BN * 4) bytes = BM * BN * 4;                 // the tile epilogue parks the fp32 tile there
-    if (BM == 64 && d.gnb_x && bytes < 16384 + 65536 + 4096 + 512) bytes = 16384 + 65536 + 4096 + 512;   // fused GroupNorm backward
+    if (BM == 64 && d.gnb_x && bytes < kGnbLdsBytes) bytes = kGnbLdsBytes;   // fused GroupNorm backward
     return bytes;
 }
-template <int BM, int NPW, int NSB, int BN = 64, typename T = bf16_t, bool SPLIT = false, int TG = 3>
-static int launch_halo(const mdm_gemm_desc& d, hipStream_t s) {      // TG = 3: one filter row (3 taps) per barrier
+// The launcher's arguments are the ones a halo route's name spells.  One filter row (3 taps) per barrier; the 128-channel tile one tap.
+template <int BM, int NPW, int NSB, int BN, typename T, bool SPLIT>
+static int launch_halo(const Resolved& r, hipStream_t s) {
+    constexpr int TG = BN == 128 ? 1 : 3;
+    const mdm_gemm_desc& d = r.d;
     const int NPA = halo_pieces(BM, d.OH, d.OW), bytes = halo_lds_bytes<BM, NSB, BN, TG>(d);
     MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_halo: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
     if (int rc = lds_opt_in<&conv_halo_kernel<BM, NPW, BN, NSB, TG, T, SPLIT>>(bytes)) return rc;
@@ -3660,64 +3625,69 @@ static int small_lds_bytes(const mdm_gemm_desc& d, int bm = 64, int bn = 32) {
 // C / G of the GroupNorm fused into a convolution's epilogue (8 without one): conv_small's 32 x 16 tiles have the register epilogue
 // only, which needs C / G == 8 and N0 % 8 == 0 (the 64 x 32 tiles fall back to the LDS epilogues)
 static int fused_gn_cpg(const mdm_gemm_desc& d) { return d.gnb_x ? d.N / d.gnb_G : (d.gnf_out ? d.N / d.gnf_G : 8); }
-template <int NPW, int BM = 64, int BN = 32>
-static int launch_small(const mdm_gemm_desc& d, hipStream_t s) {
+template <int NPW, int BM, int BN>
+static int launch_small(const Resolved& r, hipStream_t s) {
+    const mdm_gemm_desc& d = r.d;
     const int bytes = small_lds_bytes(d, BM, BN);
-    MDM_REQUIRE(small_pieces(d, BM) <= 8 * NPW && bytes <= 160 * 1024 && (BM != 64 || bytes >= 16384 + 65536 + 4096 + 512),
+    MDM_REQUIRE(small_pieces(d, BM) <= 8 * NPW && bytes <= 160 * 1024 && (BM != 64 || bytes >= kGnbLdsBytes),
                 "conv_small: tile does not fit (%d bytes)", bytes);
     MDM_REQUIRE(BM == 64 || (fused_gn_cpg(d) == 8 && d.N0 % 8 == 0), "conv_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
     if (int rc = lds_opt_in<&conv_small_kernel<NPW, BM, BN>>(bytes)) return rc;
     hipLaunchKernelGGL((conv_small_kernel<NPW, BM, BN>), dim3((unsigned)((int64_t)(d.M / BM) * cdiv(d.N, BN))), dim3(512), bytes, s, d);
     return 0;
 }
-// 0: not eligible, else the pixel tile (64, 128 or 256)
+// ---- the 3x3 "same" convolutions of the halo kernels: one geometry rule (halo_same3), one "does this tile fit" rule (halo_fits,
+// halo_small_map); halo_tile / halo_tile_f32 / halo_tile_f32_split / halo_small_n_split / halo_mixed_tiling add their own terms and
+// their own tile policy.  (ops.split_grad_reason asks mdm_gemm_route_of: nothing outside this file restates them.)
+// 3x3, stride 1, pad 1, layout 0, optionally with the x2 nearest upsample folded in (one source, not transposed); channel counts of
+// both sources in whole `chan_mult` slabs; OH a power of two (the kernel shifts by log2(OH))
+static bool halo_same3(const mdm_gemm_desc& d, int chan_mult) {
+    return d.layout == 0 && d.conv && d.KH == 3 && d.KW == 3 && d.stride == 1 && (d.ups == 0 || d.ups == 1) &&
+           !(d.ups && (d.transposed || d.C1)) && d.pad_t == 1 && d.pad_l == 1 && d.IH == d.OH && d.IW == d.OW &&
+           d.C0 % chan_mult == 0 && d.C1 % chan_mult == 0 && d.Ck == d.C0 + d.C1 && d.N0 % 8 == 0 && (d.OH & (d.OH - 1)) == 0;
+}
+// a bm-pixel tile (bm >= OW > 0) is whole rows of one image or whole images, cuts M evenly and its halo is at most 6 pieces per wave
+static bool halo_fits(const mdm_gemm_desc& d, int bm) {
+    return bm % d.OW == 0 && d.OH % (bm / d.OW) == 0 && d.M % bm == 0 && halo_pieces(bm, d.OH, d.OW) <= 48;
+}
+static bool halo_wide_map(const mdm_gemm_desc& d) { return d.OW == 16 || d.OW == 32 || d.OW == 64; }      // 256- / 128-pixel tiles
+// small maps (4x4, 8x8): 64-pixel tiles of whole images.  Too few workgroups to fill the chip, but a workgroup's
+// time is set by the filter bytes it streams (64 channels x 9 C: the same for every tile size), one launch
+// replaces the tap-split conv + its epilogue launch, and the tile holds whole images (GroupNorm-fusable)
+// (4x4 maps with > 256 input channels: level with the tap-split conv + its epilogue launch since the tiles are 32 channels
+//  wide -- 3.977 vs 3.976 ms/step -- and six launches fewer)
+static bool halo_small_map(const mdm_gemm_desc& d) {
+    return (d.OW == 4 || d.OW == 8) && d.OH == d.OW && 64 % (d.OH * d.OW) == 0 && d.M % 64 == 0;
+}
+// bf16: 0 = not eligible, else the pixel tile (64, 128 or 256) -- the largest that still yields about one workgroup per CU
 static int halo_tile(const mdm_gemm_desc& d) {
-    if (!(d.dtype == MDM_BF16 && d.layout == 0 && d.conv && d.KH == 3 && d.KW == 3 && d.stride == 1 && (d.ups == 0 || d.ups == 1) &&
-          !(d.ups && (d.transposed || d.C1)) && d.pad_t == 1 && d.pad_l == 1 && d.IH == d.OH && d.IW == d.OW &&
-          d.C0 % 64 == 0 && d.C1 % 64 == 0 && d.Ck == d.C0 + d.C1 && d.N % 64 == 0 && d.N0 % 8 == 0 && !d.out_f32 &&
-          (d.OH & (d.OH - 1)) == 0))          // the kernel shifts by log2(OW), log2(OH)
-        return 0;
-    if (d.OW == 16 || d.OW == 32 || d.OW == 64) {
-        for (int bm : {256, 128}) {
-            if (bm % d.OW || d.OH % (bm / d.OW) || d.M % bm) continue;
-            if (halo_pieces(bm, d.OH, d.OW) > 48) continue;
-            if ((int64_t)(d.M / bm) * (d.N / 64) >= kBigMinTiles) return bm;
-        }
+    if (!(d.dtype == MDM_BF16 && !d.out_f32 && d.N % 64 == 0 && halo_same3(d, 64))) return 0;
+    if (halo_wide_map(d)) {
+        for (int bm : {256, 128})
+            if (halo_fits(d, bm) && (int64_t)(d.M / bm) * (d.N / 64) >= kBigMinTiles) return bm;
         return 0;
     }
-    // small maps (4x4, 8x8): 64-pixel tiles of whole images.  Too few workgroups to fill the chip, but a workgroup's
-    // time is set by the filter bytes it streams (64 channels x 9 C: the same for every tile size), one launch
-    // replaces the tap-split conv + its epilogue launch, and the tile holds whole images (GroupNorm-fusable)
-    // (4x4 maps with > 256 input channels: level with the tap-split conv + its epilogue launch since the tiles are 32 channels
-    //  wide -- 3.977 vs 3.976 ms/step -- and six launches fewer)
-    if ((d.OW == 4 || d.OW == 8) && d.OH == d.OW && 64 % (d.OH * d.OW) == 0 && d.M % 64 == 0) return 64;
-    return 0;
+    return halo_small_map(d) ? 64 : 0;
 }
 
-// The exact-fp32 path on the halo kernel (conv_halo_body<..., float>): 0 = not eligible, else the pixel tile.  Same geometry
-// rules as halo_tile; channel counts in 32-channel slabs.  The fp32 loop is MFMA-bound, so the tile is picked for the fewest
+// The exact-fp32 path on the halo kernel (conv_halo_body<..., float>): 0 = not eligible, else the pixel tile.  Channel counts in
+// 32-channel slabs.  The fp32 loop is MFMA-bound, so the tile is picked for the fewest
 // idle slots in the last round of workgroups (one workgroup per CU): at sample_num = 100 a 32x32 layer is 800 tiles of 256 pixels
 // (3.1 rounds: 78 % of the slots busy) or 1600 of 128 (6.25 rounds: 89 %).
 static int halo_tile_f32(const mdm_gemm_desc& d) {
-    if (!(d.dtype == MDM_F32 && d.layout == 0 && d.conv && d.KH == 3 && d.KW == 3 && d.stride == 1 && (d.ups == 0 || d.ups == 1) &&
-          !(d.ups && (d.transposed || d.C1)) && d.pad_t == 1 && d.pad_l == 1 && d.IH == d.OH && d.IW == d.OW &&
-          d.C0 % 32 == 0 && d.C1 % 32 == 0 && d.Ck == d.C0 + d.C1 && d.N % 64 == 0 && d.N0 % 8 == 0 && d.splitk <= 1 &&
-          (d.OH & (d.OH - 1)) == 0 && (d.OW & (d.OW - 1)) == 0))
-        return 0;
-    if (d.OW == 16 || d.OW == 32 || d.OW == 64) {
+    if (!(d.dtype == MDM_F32 && d.N % 64 == 0 && d.splitk <= 1 && (d.OW & (d.OW - 1)) == 0 && halo_same3(d, 32))) return 0;
+    if (halo_wide_map(d)) {
         int best = 0;
         double best_eff = 0.0;
         for (int bm : {256, 128}) {
-            if (bm % d.OW || d.OH % (bm / d.OW) || d.M % bm) continue;
-            if (halo_pieces(bm, d.OH, d.OW) > 48) continue;
+            if (!halo_fits(d, bm)) continue;
             const int64_t tiles = (int64_t)(d.M / bm) * (d.N / 64);
             const double eff = (double)tiles / (double)(((tiles + 255) / 256) * 256);
             if (eff > best_eff + 1e-9) { best_eff = eff; best = bm; }
         }
         return best;
     }
-    if ((d.OW == 4 || d.OW == 8) && d.OH == d.OW && 64 % (d.OH * d.OW) == 0 && d.M % 64 == 0) return 64;
-    return 0;
+    return halo_small_map(d) ? 64 : 0;
 }
 
 // conv_halo_mixed_kernel: whole rounds of 256-pixel tiles, the remainder as 128-pixel tiles -- taken when the remainder is at most one
@@ -3729,12 +3699,13 @@ static bool halo_mixed_tiling(const mdm_gemm_desc& d, HaloMixed& t) {      // do
     const int64_t tiles = (int64_t)(d.M / 256) * tn;
     const int64_t big_m = (tiles / 256) * 256 / tn;                // M tiles of 256 pixels in whole rounds (all their channel tiles)
     const int64_t rest = (d.M / 256 - big_m) * 2 * tn;             // 128-pixel tiles behind them
-    if (d.OW != 32 || d.OH % 8 || big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return false;
-    if (halo_pieces(256, d.OH, d.OW) > 48 || halo_pieces(128, d.OH, d.OW) > 32) return false;
+    if (d.OW != 32 || !halo_fits(d, 256) || halo_pieces(128, d.OH, d.OW) > 32) return false;      // (128 pixels: four pieces per wave)
+    if (big_m < 1 || rest < 1 || rest > 256 || tiles % 256 == 0) return false;
     t = {(int)(big_m * tn), (int)(big_m * 256), (int)rest};
     return true;
 }
-static int launch_halo_mixed(const mdm_gemm_desc& d, hipStream_t s) {
+static int launch_halo_mixed(const Resolved& r, hipStream_t s) {
+    const mdm_gemm_desc& d = r.d;
     HaloMixed t;
     MDM_REQUIRE(halo_mixed_tiling(d, t), "conv_halo_mixed: the mixed tiling does not apply");
     const int npa = halo_pieces(256, d.OH, d.OW), npb = halo_pieces(128, d.OH, d.OW);
@@ -3750,10 +3721,8 @@ static int launch_halo_mixed(const mdm_gemm_desc& d, hipStream_t s) {
 // kernel its 64-wide tiles were 8 real channels each and it took 172 us of the reverse step -- more than a 128 -> 128 layer.  On the
 // 256-pixel halo tiles with a 32-channel tile (one 16-wide MFMA column per wave, rows beyond N zero): 0 = not eligible, else 256.
 static int halo_small_n_split(const mdm_gemm_desc& d) {
-    if (!(d.dtype == MDM_F32 && d.B_split != nullptr && d.layout == 0 && d.conv && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.ups == 0 &&
-          !d.transposed && d.pad_t == 1 && d.pad_l == 1 && d.IH == d.OH && d.IW == d.OW && d.C0 % 32 == 0 && d.C1 % 32 == 0 &&
-          d.Ck == d.C0 + d.C1 && d.N % 8 == 0 && d.N <= 32 && d.N0 % 8 == 0 && d.splitk <= 1 && (d.OH & (d.OH - 1)) == 0 &&
-          (d.OW == 16 || d.OW == 32) && d.OH % (256 / d.OW) == 0 && d.M % 256 == 0 && halo_pieces(256, d.OH, d.OW) <= 48 && d.M / 256 >= 128))
+    if (!(d.dtype == MDM_F32 && d.B_split != nullptr && halo_same3(d, 32) && d.ups == 0 && !d.transposed &&
+          d.N % 8 == 0 && d.N <= 32 && d.splitk <= 1 && (d.OW == 16 || d.OW == 32) && halo_fits(d, 256) && d.M / 256 >= 128))
         return 0;
     return 256;
 }
@@ -3771,7 +3740,8 @@ static int lin_split_tile(const mdm_gemm_desc& d) {
     return 64;
 }
 template <int BN>
-static int launch_lin_split(const mdm_gemm_desc& d, hipStream_t s) {
+static int launch_lin_split(const Resolved& r, hipStream_t s) {
+    const mdm_gemm_desc& d = r.d;
     constexpr int NS = BN == 64 ? MDM_LIN_SPLIT_NS64 : 4;
     constexpr int bytes = NS * (128 * 128 + BN * 128);
     static_assert(bytes <= 160 * 1024 && bytes >= 128 * BN * 4, "lin_split: ring / epilogue tile do not fit");
@@ -3794,8 +3764,7 @@ static int halo_tile_f32_split(const mdm_gemm_desc& d, int exact_choice) {
     int best = exact_choice;
     double best_t = 1e30;
     for (int bm : {256, 128}) {
-        if (bm % d.OW || d.OH % (bm / d.OW) || d.M % bm) continue;
-        if (halo_pieces(bm, d.OH, d.OW) > 48) continue;
+        if (!halo_fits(d, bm)) continue;
         const int64_t tiles = (int64_t)(d.M / bm) * (d.N / 64);
         const double tm = (double)((tiles + 255) / 256) * (bm == 256 ? 1.46 : 1.0);
         if (tm < best_t - 1e-9) { best_t = tm; best = bm; }
@@ -3828,16 +3797,21 @@ static int launch_f32_mfma_one(const mdm_gemm_desc& d, dim3 grid, hipStream_t s)
     return 0;
 }
 template <int BM, int BN>
-static int launch_f32_mfma(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {      // exact products (split ones: choose_route)
-    switch (d.layout) {
-        case 0: return launch_f32_mfma_one<BM, BN, 0>(d, grid, s);
-        case 1: return launch_f32_mfma_one<BM, BN, 1>(d, grid, s);
-        default: return launch_f32_mfma_one<BM, BN, 2>(d, grid, s);
+static int launch_f32_mfma(const Resolved& r, hipStream_t s) {      // exact products, on BM x BN tiles (resolve counts 64 x 64 ones)
+    switch (r.d.layout) {
+        case 0: return launch_f32_mfma_one<BM, BN, 0>(r.d, grid_of<BM, BN>(r), s);
+        case 1: return launch_f32_mfma_one<BM, BN, 1>(r.d, grid_of<BM, BN>(r), s);
+        default: return launch_f32_mfma_one<BM, BN, 2>(r.d, grid_of<BM, BN>(r), s);
     }
+}
+static int launch_f32_mfma_split(const Resolved& r, hipStream_t s) {      // split products: layout 0, 128 x 128 tiles only (choose_route)
+    return launch_f32_mfma_one<128, 128, 0, true>(r.d, grid_of<128, 128>(r), s);
 }
 
 template <int BM, int BN>
-static int launch_bf16(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
+static int launch_bf16(const Resolved& r, hipStream_t s) {
+    const mdm_gemm_desc& d = r.d;
+    const dim3 grid = grid_of(r);
     switch (d.layout) {
         case 0: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0>), grid, dim3(256), 0, s, d); break;
         case 1: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1>), grid, dim3(256), 0, s, d); break;
@@ -3846,19 +3820,61 @@ static int launch_bf16(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
     return 0;
 }
 
-// What mdm_gemm decides before it launches: the tile family, the reduction split, where split-K partials go.
-struct Resolved {
-    mdm_gemm_desc d;
-    bool big, tap_split;
-    int zouter;
-    int64_t tiles, slab;        // output tiles of the chosen shape; bytes of one dense fp32 copy of the output
-};
+template <int NJ>
+static int launch_thin(const Resolved& r, hipStream_t s) {
+    const unsigned nb = (unsigned)std::min(cdiv(cdiv(r.d.M, 16), 4), 1024);
+    hipLaunchKernelGGL((conv_thin_k_kernel<NJ>), dim3(nb), dim3(256), 0, s, r.d);
+    return 0;
+}
+static int launch_skinny_f32(const Resolved& r, hipStream_t s) {      // opts in to its largest tile (K = 512) on first use, whatever K is
+    const mdm_gemm_desc& d = r.d;
+    if (int rc = lds_opt_in<&linear_skinny_f32_kernel>(32 * 512 * 4)) return rc;
+    hipLaunchKernelGGL(linear_skinny_f32_kernel, dim3((unsigned)cdiv(d.N, 16)), dim3(256), 32 * (d.K > 16 * 17 ? d.K : 16 * 17) * 4, s, d);
+    return 0;
+}
+static int launch_tn_skinny_f32(const Resolved& r, hipStream_t s) {
+    const mdm_gemm_desc& d = r.d;
+    if (int rc = lds_opt_in<&tn_skinny_f32_kernel>(d.K * 128 * 4)) return rc;
+    hipLaunchKernelGGL(tn_skinny_f32_kernel, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 64))), dim3(256), d.K * 128 * 4, s, d);
+    return 0;
+}
+
+// ---- two independent convolutions in one launch (conv_pair_kernel): workgroups of `b` on the tile shape resolve chose
+template <int BM, int NPW, int BN, int NSB, int LBM, int LBN, int LNS, int LWR, int LWC>
+static int launch_pair(const Resolved& ra, const Resolved& rb, hipStream_t s) {
+    const mdm_gemm_desc &a = ra.d, &b = rb.d;
+    const int nb = LBM == 64 && LBN == 128 ? (int)grid_of<64, 128>(rb).x : (int)rb.tiles;      // (64 x 128 is not a tile shape of resolve)
+    const int NPA = halo_pieces(BM, a.OH, a.OW);
+    const int bytes = std::max(halo_lds_bytes<BM, NSB, BN, 3>(a), lin2_lds_bytes<LBM, LBN, LNS>(b));
+    MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_pair: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
+    if (int rc = lds_opt_in<&conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>>(bytes)) return rc;
+    const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
+    hipLaunchKernelGGL((conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
+    return 0;
+}
+
+template <int NPW, int BM, int BN>
+static int launch_pair_small(const Resolved& ra, const Resolved& rb, hipStream_t s) {
+    const mdm_gemm_desc &a = ra.d, &b = rb.d;
+    const int nb = (int)rb.tiles;
+    const int bytes = std::max(small_lds_bytes(a, BM, BN), lin2_lds_bytes<64, 64, 4>(b));
+    MDM_REQUIRE(small_pieces(a, BM) <= 8 * NPW && bytes <= 160 * 1024, "conv_pair_small: tile does not fit (%d bytes)", bytes);
+    MDM_REQUIRE(BM == 64 || (fused_gn_cpg(a) == 8 && a.N0 % 8 == 0), "conv_pair_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
+    if (int rc = lds_opt_in<&conv_pair_small_kernel<NPW, BM, BN>>(bytes)) return rc;
+    const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
+    hipLaunchKernelGGL((conv_pair_small_kernel<NPW, BM, BN>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
+    return 0;
+}
+
+static mdm_gemm_desc with_n0(mdm_gemm_desc d) {      // N0 == 0 means one destination: N0 = N
+    if (d.N0 == 0) d.N0 = d.N;
+    return d;
+}
 static int resolve(const mdm_gemm_desc* dh, bool planning, Resolved& r) {
     MDM_REQUIRE(dh != nullptr, "gemm: null descriptor");
     mdm_gemm_desc& d = r.d;
-    d = *dh;
+    d = with_n0(*dh);
     if (planning) { d.ws = reinterpret_cast<void*>(16); d.ws_bytes = (int64_t)1 << 60; }   // "unlimited": never dereferenced
-    if (d.N0 == 0) d.N0 = d.N;
     if (int rc = validate(d)) return rc;
     r.zouter = d.batch;
     if (d.layout == 2 && d.conv) r.zouter = d.KH * d.KW;
@@ -3908,6 +3924,81 @@ static int resolve(const mdm_gemm_desc* dh, bool planning, Resolved& r) {
     return 0;
 }
 
+// ---- the routes (mdm_gemm_last_route): which kernel and which second stage the last call on this host thread launched.
+// ONE table: X(enum, kernel name, second stages it can take: T = tap-split epilogue, K = split-K reduce, its launcher from mdm_gemm,
+// its launcher from mdm_gemm_pair).  A route is kernel * 3 + stage; the names of all three stages exist, mdm_gemm_route_names lists
+// the ones the mask allows.  launch_route / launch_pair_route are one indexed call; the routes without a launcher are entry points
+// of their own.  The halo, conv_small and conv_thin_k rows spell their template arguments once: the name is those arguments
+// (two rows excepted, whose filter-stage count is a tuning constant that the name calls NSB).
+enum RouteStage { S_NONE = 0, S_TAPSPLIT = 1, S_SPLITK = 2 };
+constexpr int TSPLIT = 1 << S_TAPSPLIT, KSPLIT = 1 << S_SPLITK;
+#define HALO_ARGS(BM, NPW, NSB, BN) "halo<" #BM "," #NPW "," #NSB "," #BN
+#define HB(X, e, BM, NPW, NSB, BN) X(e, HALO_ARGS(BM, NPW, NSB, BN) ">", 0, (launch_halo<BM, NPW, NSB, BN, bf16_t, false>))
+#define HF(X, e, BM, NPW, NSB, BN) X(e, HALO_ARGS(BM, NPW, NSB, BN) ",f32>", 0, (launch_halo<BM, NPW, NSB, BN, float, false>))
+#define HS(X, e, BM, NPW, NSB, BN) X(e, HALO_ARGS(BM, NPW, NSB, BN) ",f32,split>", 0, (launch_halo<BM, NPW, NSB, BN, float, true>))
+#define SMALL(X, e, NPW, BM, BN) X(e, "conv_small<" #NPW "," #BM "," #BN ">", 0, (launch_small<NPW, BM, BN>))
+#define THIN(X, e, NJ) X(e, "conv_thin_k<" #NJ ">", 0, launch_thin<NJ>)
+#define PAIR(X, e, n, ...) X(e, n, 0, nullptr, (__VA_ARGS__))
+#define MDM_GEMM_ROUTES(X)                                                                                                      \
+    X(R_SKINNY_F32, "linear_skinny_f32", 0, launch_skinny_f32) X(R_TN_SKINNY_F32, "tn_skinny_f32", 0, launch_tn_skinny_f32)     \
+    X(R_LIN_SPLIT_128, "lin_split<128>", 0, launch_lin_split<128>) X(R_LIN_SPLIT_64, "lin_split<64>", 0, launch_lin_split<64>)  \
+    HS(X, R_HS_256_6_32, 256, 6, 2, 32) HS(X, R_HS_256_6_128, 256, 6, 4, 128)                                                   \
+    X(R_HS_MIXED, "halo_mixed<256|128,f32,split>", 0, launch_halo_mixed)                                                        \
+    X(R_HS_256_6, "halo<256,6,NSB,64,f32,split>", 0, (launch_halo<256, 6, MDM_SPLIT_NSB256, 64, float, true>))                  \
+    HS(X, R_HS_128_3, 128, 3, 3, 64) HS(X, R_HS_128_4, 128, 4, 3, 64) HS(X, R_HS_128_6, 128, 6, 3, 64)                          \
+    HS(X, R_HS_64_2_32, 64, 2, 3, 32) HS(X, R_HS_64_3_32, 64, 3, 3, 32)                                                         \
+    HS(X, R_HS_64_2_64, 64, 2, 3, 64) HS(X, R_HS_64_3_64, 64, 3, 3, 64)                                                         \
+    HF(X, R_HF_256_6, 256, 6, 2, 64)                                                                                            \
+    HF(X, R_HF_128_3, 128, 3, 3, 64) HF(X, R_HF_128_4, 128, 4, 3, 64) HF(X, R_HF_128_6, 128, 6, 3, 64)                          \
+    HF(X, R_HF_64_2_32, 64, 2, 3, 32) HF(X, R_HF_64_3_32, 64, 3, 3, 32)                                                         \
+    HF(X, R_HF_64_2_64, 64, 2, 3, 64) HF(X, R_HF_64_3_64, 64, 3, 3, 64)                                                         \
+    X(R_F32_128, "f32_mfma<128>", KSPLIT, (launch_f32_mfma<128, 128>))                                                          \
+    X(R_F32_128_SPLIT, "f32_mfma<128,split>", KSPLIT, launch_f32_mfma_split)                                                    \
+    X(R_F32_64, "f32_mfma<64>", KSPLIT, (launch_f32_mfma<64, 64>))                                                              \
+    THIN(X, R_THIN_1, 1) THIN(X, R_THIN_2, 2) THIN(X, R_THIN_4, 4) THIN(X, R_THIN_8, 8)                                         \
+    X(R_H256_6, "halo<256,6,NSB,64>", 0, (launch_halo<256, 6, MDM_NSB256, 64, bf16_t, false>))                                  \
+    HB(X, R_H128_3, 128, 3, 3, 64) HB(X, R_H128_4, 128, 4, 3, 64) HB(X, R_H128_6, 128, 6, 3, 64)                                \
+    HB(X, R_H64_2_32, 64, 2, 3, 32) HB(X, R_H64_3_32, 64, 3, 3, 32)                                                             \
+    HB(X, R_H64_2_64, 64, 2, 3, 64) HB(X, R_H64_3_64, 64, 3, 3, 64)                                                             \
+    SMALL(X, R_SMALL_4, 4, 64, 32) SMALL(X, R_SMALL_5, 5, 64, 32) SMALL(X, R_SMALL_3, 3, 32, 16)                                \
+    X(R_LIN2_128, "lin2<128,128>", 0, (launch_lin2<128, 128, 3, 4, 2>))                                                         \
+    X(R_LIN2_64x128, "lin2<64,128>", TSPLIT, (launch_lin2<64, 128, 3, 2, 4>))                                                   \
+    X(R_LIN2_64, "lin2<64,64>", TSPLIT, (launch_lin2<64, 64, 4, 4, 2>))                                                         \
+    X(R_WGRAD_LIN_128, "wgrad_lin<128>", KSPLIT, (launch_wgrad_lin<128, 128, 3, 8>))                                            \
+    X(R_WGRAD_LIN_64, "wgrad_lin<64>", KSPLIT, (launch_wgrad_lin<64, 64, 4, 8>))                                                \
+    X(R_RING_128, "ring<128>", KSPLIT, (launch_ring<128, 128, 3>)) X(R_RING_64, "ring<64>", TSPLIT | KSPLIT, (launch_ring<64, 64, 4>)) \
+    X(R_BF16_128, "bf16<128>", KSPLIT, (launch_bf16<128, 128>)) X(R_BF16_64, "bf16<64>", KSPLIT, (launch_bf16<64, 64>))         \
+    PAIR(X, R_PAIR_SMALL_4, "pair_small<4>", launch_pair_small<4, 64, 32>)                                                      \
+    PAIR(X, R_PAIR_SMALL_5, "pair_small<5>", launch_pair_small<5, 64, 32>)                                                      \
+    PAIR(X, R_PAIR_SMALL_3, "pair_small<3,32,16>", launch_pair_small<3, 32, 16>)                                                \
+    PAIR(X, R_PAIR_64_2, "pair<halo<64,2,3,32>,lin2<64,64>>", launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>)                       \
+    PAIR(X, R_PAIR_64_3, "pair<halo<64,3,3,32>,lin2<64,64>>", launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>)                       \
+    PAIR(X, R_PAIR_128_L64x128, "pair<halo<128,3,3,64>,lin2<64,128>>", launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>)            \
+    PAIR(X, R_PAIR_128_L64, "pair<halo<128,3,3,64>,lin2<64,64>>", launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>)                  \
+    PAIR(X, R_PAIR_256_L128, "pair<halo<256,6,NSB,64>,lin2<128,128>>", launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>)  \
+    X(R_PAIR_TWO, "pair:two launches", 0, nullptr)                                                                              \
+    X(R_WGROUP, "wgrad_group", KSPLIT, nullptr) X(R_WGROUP_TAPS, "wgrad_taps_group", KSPLIT, nullptr)
+enum GemmRoute {
+#define MDM_ROUTE_ENUM(e, ...) e,
+    MDM_GEMM_ROUTES(MDM_ROUTE_ENUM)
+#undef MDM_ROUTE_ENUM
+    R_COUNT
+};
+static const struct RouteRow {
+    const char* name[3];        // by RouteStage
+    int stages;                 // mask of the stages it can take
+    int (*launch)(const Resolved&, hipStream_t);
+    int (*launch_pair)(const Resolved&, const Resolved&, hipStream_t);
+} kRoutes[R_COUNT] = {
+#define MDM_ROUTE_ROW(e, n, m, ...) {{n, n "+tapsplit", n "+splitk"}, 1 | (m), __VA_ARGS__},
+    MDM_GEMM_ROUTES(MDM_ROUTE_ROW)
+#undef MDM_ROUTE_ROW
+};
+static const char* route_name(int route) { return kRoutes[route / 3].name[route % 3]; }
+static thread_local int g_route = -1;
+static inline void route(GemmRoute r) { g_route = 3 * r; }
+static inline void route_stage(RouteStage st) { if (g_route >= 0) g_route = g_route / 3 * 3 + st; }
+
 // Which kernel of the conv_halo / conv_lin2 family a bf16 forward / data-gradient convolution takes (conv_family + conv_variant).
 // Tile choice (measured per shape): the largest tile that still gives the chip ~one workgroup per CU -- whole-row halo tiles
 // of 256 / 128 pixels on the 32x32 / 16x16 maps; 64-pixel whole-image tiles on 4x4 / 8x8 (the loop there is the filter stream
@@ -3927,15 +4018,24 @@ static bool conv_family(const mdm_gemm_desc& d) {           // does the convolut
            (d.stride == 1 || (d.stride == 2 && !d.transposed && d.ups == 0)) && d.C0 <= 4096 && d.C1 <= 4096 &&
            (d.ups == 0 || (d.splitk <= 1 && halo_tile(d) != 0)) && d.KH * d.KW <= 9 && (d.KH * d.KW) % d.splitk == 0;
 }
+// The tile -> route ladder of the three halo families: 256 pixels take the six-piece kernel, 128 pixels the one for their pieces per
+// wave, 64 pixels 32-channel tiles (`half_n`) or 64-channel ones
+enum HaloKind { HK_BF16, HK_F32, HK_F32_SPLIT };
+static GemmRoute halo_route(HaloKind kind, int bm, int npw, bool half_n) {
+    static const GemmRoute ladder[3][8] = {
+        {R_H256_6, R_H128_3, R_H128_4, R_H128_6, R_H64_2_32, R_H64_3_32, R_H64_2_64, R_H64_3_64},
+        {R_HF_256_6, R_HF_128_3, R_HF_128_4, R_HF_128_6, R_HF_64_2_32, R_HF_64_3_32, R_HF_64_2_64, R_HF_64_3_64},
+        {R_HS_256_6, R_HS_128_3, R_HS_128_4, R_HS_128_6, R_HS_64_2_32, R_HS_64_3_32, R_HS_64_2_64, R_HS_64_3_64}};
+    const int rung = bm == 256 ? 0 : bm == 128 ? (npw <= 3 ? 1 : npw <= 4 ? 2 : 3) : (half_n ? 4 : 6) + (npw <= 2 ? 0 : 1);
+    return ladder[kind][rung];
+}
 static GemmRoute conv_variant(const Resolved& r) {          // ... and which one (conv_family holds)
     const mdm_gemm_desc& d = r.d;
     const int64_t t_mid = (int64_t)cdiv(d.M, 64) * cdiv(d.N, 128) * (r.zouter * d.splitk);
     const int hb = d.splitk <= 1 ? halo_tile(d) : 0;
     if (hb) {
-        const int npw = halo_npw(hb, d);
-        if (hb == 256) return R_H256_6;
-        if (hb == 128) return npw <= 3 ? R_H128_3 : npw <= 4 ? R_H128_4 : R_H128_6;
-        if (d.N % 32 == 0 && (!(d.gnb_x || d.gnf_out) || d.N / (d.gnb_x ? d.gnb_G : d.gnf_G) <= 32)) {
+        const bool half_n = hb == 64 && d.N % 32 == 0 && (!(d.gnb_x || d.gnf_out) || d.N / (d.gnb_x ? d.gnb_G : d.gnf_G) <= 32);
+        if (half_n) {
             // 128-channel superslabs with the reduction split over the waves (conv_small_body) where the channel counts allow
             const int spw = (small_pieces(d) + 7) / 8;
             if (d.Ck % 128 == 0 && d.C0 % 128 == 0 && d.C1 % 128 == 0 && spw <= 5) {
@@ -3946,9 +4046,8 @@ static GemmRoute conv_variant(const Resolved& r) {          // ... and which one
                     return R_SMALL_3;
                 return spw <= 4 ? R_SMALL_4 : R_SMALL_5;
             }
-            return npw <= 2 ? R_H64_2_32 : R_H64_3_32;
         }
-        return npw <= 2 ? R_H64_2_64 : R_H64_3_64;
+        return halo_route(HK_BF16, hb, halo_npw(hb, d), half_n);
     }
     if ((d.gnb_x || d.gnf_out) && lin2_gn_tile(d)) return R_LIN2_64;      // the fused epilogues live on the 64 x 64 tile
     if (r.big) return R_LIN2_128;
@@ -3982,30 +4081,21 @@ static GemmRoute choose_route(const Resolved& r) {
     if (const int lsb = lin_split_tile(d)) return lsb == 128 ? R_LIN_SPLIT_128 : R_LIN_SPLIT_64;
     if (halo_small_n_split(d)) return R_HS_256_6_32;
     if (const int hb_exact = halo_tile_f32(d)) {
-        // exact-fp32 3x3 convolutions on the halo kernel (forward, folded upsample, transposed shadow): MFMA-bound
+        // 3x3 convolutions in fp32 storage on the halo kernel (forward, folded upsample, transposed shadow).  Exact products are
+        // MFMA-bound; with a split shadow the products run as bf16 hi / lo pairs on the bf16 matrix pipe (conv_halo_body<..., SPLIT>)
+        // and the tile is the split-products one
         const bool half_n = (int64_t)(d.M / 64) * (d.N / 64) < kBigMinTiles && d.N % 32 == 0;   // 4x4 maps: 32-channel tiles, twice the workgroups
-        if (d.B_split != nullptr && !d.transposed) {
-            // fp32 storage, products as bf16 hi / lo pairs on the bf16 matrix pipe (conv_halo_body<..., SPLIT>); this arm decides
-            // with the split-products tile, the exact arm below with the exact one
-            const int hb = halo_tile_f32_split(d, hb_exact), npw = halo_npw(hb, d);
-            if (hb == 256) {
-                // 256 pixels x 128 channels (one tap per barrier, four filter stages): the halo is staged and split once for twice the
-                // channels and a wave multiplies 4 x 4 fragments per tap -- 16 fragment reads for 48 MFMAs where the 64-channel tile reads
-                // 12 for 24; half as many tiles, so a 16x16 layer at sample_num = 100 is ONE round of workgroups instead of 1.56 in two
-                if (d.N % 128 == 0 && (d.OW == 16 || d.OW == 32) && (int64_t)(d.M / 256) * (d.N / 128) >= MDM_SPLIT_BN128) return R_HS_256_6_128;
-                HaloMixed t;
-                if (halo_mixed_tiling(d, t)) return R_HS_MIXED;      // whole rounds of 256-pixel tiles + a short round of 128-pixel ones
-                return R_HS_256_6;
-            }
-            if (hb == 128) return npw <= 3 ? R_HS_128_3 : npw <= 4 ? R_HS_128_4 : R_HS_128_6;
-            if (half_n) return npw <= 2 ? R_HS_64_2_32 : R_HS_64_3_32;
-            return npw <= 2 ? R_HS_64_2_64 : R_HS_64_3_64;
+        const bool split = d.B_split != nullptr && !d.transposed;
+        const int hb = split ? halo_tile_f32_split(d, hb_exact) : hb_exact;
+        if (split && hb == 256) {
+            // 256 pixels x 128 channels (one tap per barrier, four filter stages): the halo is staged and split once for twice the
+            // channels and a wave multiplies 4 x 4 fragments per tap -- 16 fragment reads for 48 MFMAs where the 64-channel tile reads
+            // 12 for 24; half as many tiles, so a 16x16 layer at sample_num = 100 is ONE round of workgroups instead of 1.56 in two
+            if (d.N % 128 == 0 && (d.OW == 16 || d.OW == 32) && (int64_t)(d.M / 256) * (d.N / 128) >= MDM_SPLIT_BN128) return R_HS_256_6_128;
+            HaloMixed t;
+            if (halo_mixed_tiling(d, t)) return R_HS_MIXED;      // whole rounds of 256-pixel tiles + a short round of 128-pixel ones
         }
-        const int npw = halo_npw(hb_exact, d);
-        if (hb_exact == 256) return R_HF_256_6;
-        if (hb_exact == 128) return npw <= 3 ? R_HF_128_3 : npw <= 4 ? R_HF_128_4 : R_HF_128_6;
-        if (half_n) return npw <= 2 ? R_HF_64_2_32 : R_HF_64_3_32;
-        return npw <= 2 ? R_HF_64_2_64 : R_HF_64_3_64;
+        return halo_route(split ? HK_F32_SPLIT : HK_F32, hb, halo_npw(hb, d), half_n);
     }
     if (d.dtype == MDM_F32) {
         // exact-fp32 MFMA kernel; 128 x 128 tiles when that still gives about one workgroup per CU
@@ -4039,75 +4129,9 @@ static int plan_route(const mdm_gemm_desc* dh, Resolved& r, GemmRoute& rt) {
     return 0;
 }
 
-template <int NJ>
-static int launch_thin(const mdm_gemm_desc& d, hipStream_t s) {
-    const unsigned nb = (unsigned)std::min(cdiv(cdiv(d.M, 16), 4), 1024);
-    hipLaunchKernelGGL((conv_thin_k_kernel<NJ>), dim3(nb), dim3(256), 0, s, d);
-    return 0;
-}
-static int launch_route(GemmRoute rt, const Resolved& r, hipStream_t s) {
-    const mdm_gemm_desc& d = r.d;
-    const dim3 grid((unsigned)r.tiles, 1, (unsigned)(r.zouter * d.splitk));      // tiles of the shape resolve chose
-    switch (rt) {
-        case R_SKINNY_F32:      // opts in to its largest tile (K = 512) on first use, whatever K is
-            if (int rc = lds_opt_in<&linear_skinny_f32_kernel>(32 * 512 * 4)) return rc;
-            hipLaunchKernelGGL(linear_skinny_f32_kernel, dim3((unsigned)cdiv(d.N, 16)), dim3(256), 32 * (d.K > 16 * 17 ? d.K : 16 * 17) * 4, s, d);
-            return 0;
-        case R_TN_SKINNY_F32:
-            if (int rc = lds_opt_in<&tn_skinny_f32_kernel>(d.K * 128 * 4)) return rc;
-            hipLaunchKernelGGL(tn_skinny_f32_kernel, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 64))), dim3(256), d.K * 128 * 4, s, d);
-            return 0;
-        case R_LIN_SPLIT_128: return launch_lin_split<128>(d, s);
-        case R_LIN_SPLIT_64: return launch_lin_split<64>(d, s);
-        case R_HS_256_6_32: return launch_halo<256, 6, 2, 32, float, true>(d, s);
-        case R_HS_256_6_128: return launch_halo<256, 6, 4, 128, float, true, 1>(d, s);
-        case R_HS_MIXED: return launch_halo_mixed(d, s);
-        case R_HS_256_6: return launch_halo<256, 6, MDM_SPLIT_NSB256, 64, float, true>(d, s);
-        case R_HS_128_3: return launch_halo<128, 3, 3, 64, float, true>(d, s);
-        case R_HS_128_4: return launch_halo<128, 4, 3, 64, float, true>(d, s);
-        case R_HS_128_6: return launch_halo<128, 6, 3, 64, float, true>(d, s);
-        case R_HS_64_2_32: return launch_halo<64, 2, 3, 32, float, true>(d, s);
-        case R_HS_64_3_32: return launch_halo<64, 3, 3, 32, float, true>(d, s);
-        case R_HS_64_2_64: return launch_halo<64, 2, 3, 64, float, true>(d, s);
-        case R_HS_64_3_64: return launch_halo<64, 3, 3, 64, float, true>(d, s);
-        case R_HF_256_6: return launch_halo<256, 6, 2, 64, float>(d, s);
-        case R_HF_128_3: return launch_halo<128, 3, 3, 64, float>(d, s);
-        case R_HF_128_4: return launch_halo<128, 4, 3, 64, float>(d, s);
-        case R_HF_128_6: return launch_halo<128, 6, 3, 64, float>(d, s);
-        case R_HF_64_2_32: return launch_halo<64, 2, 3, 32, float>(d, s);
-        case R_HF_64_3_32: return launch_halo<64, 3, 3, 32, float>(d, s);
-        case R_HF_64_2_64: return launch_halo<64, 2, 3, 64, float>(d, s);
-        case R_HF_64_3_64: return launch_halo<64, 3, 3, 64, float>(d, s);
-        case R_F32_128: return launch_f32_mfma<128, 128>(d, dim3((unsigned)((int64_t)cdiv(d.M, 128) * cdiv(d.N, 128)), 1, grid.z), s);
-        case R_F32_128_SPLIT:
-            return launch_f32_mfma_one<128, 128, 0, true>(d, dim3((unsigned)((int64_t)cdiv(d.M, 128) * cdiv(d.N, 128)), 1, grid.z), s);
-        case R_F32_64: return launch_f32_mfma<64, 64>(d, grid, s);
-        case R_THIN_1: return launch_thin<1>(d, s);
-        case R_THIN_2: return launch_thin<2>(d, s);
-        case R_THIN_4: return launch_thin<4>(d, s);
-        case R_THIN_8: return launch_thin<8>(d, s);
-        case R_H256_6: return launch_halo<256, 6, MDM_NSB256>(d, s);
-        case R_H128_3: return launch_halo<128, 3, 3>(d, s);
-        case R_H128_4: return launch_halo<128, 4, 3>(d, s);
-        case R_H128_6: return launch_halo<128, 6, 3>(d, s);
-        case R_H64_2_32: return launch_halo<64, 2, 3, 32>(d, s);
-        case R_H64_3_32: return launch_halo<64, 3, 3, 32>(d, s);
-        case R_H64_2_64: return launch_halo<64, 2, 3>(d, s);
-        case R_H64_3_64: return launch_halo<64, 3, 3>(d, s);
-        case R_SMALL_4: return launch_small<4>(d, s);
-        case R_SMALL_5: return launch_small<5>(d, s);
-        case R_SMALL_3: return launch_small<3, 32, 16>(d, s);
-        case R_LIN2_128: return launch_lin2<128, 128, 3, 4, 2>(d, grid, s);
-        case R_LIN2_64x128: return launch_lin2<64, 128, 3, 2, 4>(d, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 128)), 1, grid.z), s);
-        case R_LIN2_64: return launch_lin2<64, 64, 4, 4, 2>(d, grid, s);
-        case R_WGRAD_LIN_128: return launch_wgrad_lin<128, 128, 3, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s);
-        case R_WGRAD_LIN_64: return launch_wgrad_lin<64, 64, 4, 8>(d, (int)grid.x, (int)(grid.x * grid.z), s);
-        case R_RING_128: return launch_ring<128, 128, 3>(d, grid, s);
-        case R_RING_64: return launch_ring<64, 64, 4>(d, grid, s);
-        case R_BF16_128: return launch_bf16<128, 128>(d, grid, s);
-        case R_BF16_64: return launch_bf16<64, 64>(d, grid, s);
-        default: set_error("gemm: route %d is not an mdm_gemm route", (int)rt); return -1;   // (pairs and groups: entry points of their own)
-    }
+static int launch_route(GemmRoute rt, const Resolved& r, hipStream_t s) {      // (pairs and groups: entry points of their own)
+    MDM_REQUIRE(rt >= 0 && rt < R_COUNT && kRoutes[rt].launch, "gemm: route %d is not an mdm_gemm route", (int)rt);
+    return kRoutes[rt].launch(r, s);
 }
 
 static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
@@ -4154,46 +4178,23 @@ using namespace mdm;
 
 extern "C" int mdm_gemm(const mdm_gemm_desc* desc_host, void* stream) { return gemm_launch(desc_host, pick_stream(stream)); }
 
-extern "C" const char* mdm_gemm_last_route(void) { return g_route >= 0 ? kRouteName[g_route] : "none"; }
+extern "C" const char* mdm_gemm_last_route(void) { return g_route >= 0 ? route_name(g_route) : "none"; }
 
 extern "C" const char* mdm_gemm_route_of(const mdm_gemm_desc* desc_host) {
     Resolved r;
     GemmRoute rt;
     if (plan_route(desc_host, r, rt)) return "none";
-    return kRouteName[3 * rt + second_stage(r)];
+    return route_name(3 * rt + second_stage(r));
 }
 
 extern "C" int mdm_gemm_route_names(const char** out, int cap) {
     int n = 0;
     for (int i = 0; i < R_COUNT * 3; ++i) {
-        if (!(kRouteStages[i / 3] & (1 << (i % 3)))) continue;
-        if (out && n < cap) out[n] = kRouteName[i];
+        if (!(kRoutes[i / 3].stages & (1 << (i % 3)))) continue;
+        if (out && n < cap) out[n] = route_name(i);
         ++n;
     }
     return n;
-}
-
-// ---- two independent convolutions in one launch (conv_pair_kernel)
-template <int BM, int NPW, int BN, int NSB, int LBM, int LBN, int LNS, int LWR, int LWC>
-static int launch_pair(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int nb, hipStream_t s) {
-    const int NPA = halo_pieces(BM, a.OH, a.OW);
-    const int bytes = std::max(halo_lds_bytes<BM, NSB, BN, 3>(a), lin2_lds_bytes<LBM, LBN, LNS>(b));
-    MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_pair: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
-    if (int rc = lds_opt_in<&conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>>(bytes)) return rc;
-    const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
-    hipLaunchKernelGGL((conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
-    return 0;
-}
-
-template <int NPW, int BM = 64, int BN = 32>
-static int launch_pair_small(const mdm_gemm_desc& a, const mdm_gemm_desc& b, int nb, hipStream_t s) {
-    const int bytes = std::max(small_lds_bytes(a, BM, BN), lin2_lds_bytes<64, 64, 4>(b));
-    MDM_REQUIRE(small_pieces(a, BM) <= 8 * NPW && bytes <= 160 * 1024, "conv_pair_small: tile does not fit (%d bytes)", bytes);
-    MDM_REQUIRE(BM == 64 || (fused_gn_cpg(a) == 8 && a.N0 % 8 == 0), "conv_pair_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
-    if (int rc = lds_opt_in<&conv_pair_small_kernel<NPW, BM, BN>>(bytes)) return rc;
-    const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
-    hipLaunchKernelGGL((conv_pair_small_kernel<NPW, BM, BN>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
-    return 0;
 }
 
 static int plan_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, Resolved& ra, Resolved& rb) {
@@ -4222,19 +4223,8 @@ static GemmRoute choose_pair_route(const Resolved& ra, const Resolved& rb) {
     return R_PAIR_TWO;
 }
 static int launch_pair_route(GemmRoute rt, const Resolved& ra, const Resolved& rb, hipStream_t s) {
-    const mdm_gemm_desc &a = ra.d, &b = rb.d;
-    const int nb = (int)rb.tiles;            // workgroups of `b` on the tile shape resolve chose
-    switch (rt) {
-        case R_PAIR_SMALL_4: return launch_pair_small<4>(a, b, nb, s);
-        case R_PAIR_SMALL_5: return launch_pair_small<5>(a, b, nb, s);
-        case R_PAIR_SMALL_3: return launch_pair_small<3, 32, 16>(a, b, nb, s);
-        case R_PAIR_64_2: return launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>(a, b, nb, s);
-        case R_PAIR_64_3: return launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>(a, b, nb, s);
-        case R_PAIR_128_L64x128: return launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>(a, b, (int)((int64_t)cdiv(b.M, 64) * cdiv(b.N, 128)), s);
-        case R_PAIR_128_L64: return launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>(a, b, nb, s);
-        case R_PAIR_256_L128: return launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>(a, b, nb, s);
-        default: set_error("gemm_pair: route %d is not a fused pair", (int)rt); return -1;
-    }
+    MDM_REQUIRE(rt >= 0 && rt < R_COUNT && kRoutes[rt].launch_pair, "gemm_pair: route %d is not a fused pair", (int)rt);
+    return kRoutes[rt].launch_pair(ra, rb, s);
 }
 
 extern "C" int mdm_gemm_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, void* stream) {
@@ -4257,26 +4247,26 @@ extern "C" int mdm_gemm_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b
 extern "C" const char* mdm_gemm_pair_route_of(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host) {
     Resolved ra, rb;
     if (plan_pair(a_host, b_host, ra, rb)) return "none";
-    return kRouteName[3 * choose_pair_route(ra, rb)];
+    return route_name(3 * choose_pair_route(ra, rb));
 }
 
-extern "C" int mdm_gemm_can_fuse_gn_bwd(const mdm_gemm_desc* desc_host, int G) {
-    if (!desc_host || G <= 0) return 0;
-    mdm_gemm_desc d = *desc_host;
-    if (d.N0 == 0) d.N0 = d.N;
-    if (!(d.transposed && d.N % G == 0 && d.N0 == d.N && d.C1 == 0 && !d.D1 && !d.bias && !d.rowvec && !d.resid && d.alpha == 1.0f)) return 0;
+// the tail of both predicates: whole channel groups of 4 .. 64 channels on a tile of whole images
+static int fused_gn_tile(const mdm_gemm_desc& d, int G) {
     const int cpg = d.N / G;
     if (!(cpg == 4 || cpg == 8 || cpg == 16 || cpg == 32 || cpg == 64)) return 0;
     return (halo_tile(d) == 64 || lin2_gn_tile(d)) ? 1 : 0;
+}
+extern "C" int mdm_gemm_can_fuse_gn_bwd(const mdm_gemm_desc* desc_host, int G) {
+    if (!desc_host || G <= 0) return 0;
+    const mdm_gemm_desc d = with_n0(*desc_host);
+    if (!(d.transposed && d.N % G == 0 && d.N0 == d.N && d.C1 == 0 && !d.D1 && !d.bias && !d.rowvec && !d.resid && d.alpha == 1.0f)) return 0;
+    return fused_gn_tile(d, G);
 }
 extern "C" int mdm_gemm_can_fuse_gn_fwd(const mdm_gemm_desc* desc_host, int G) {
     if (!desc_host || G <= 0) return 0;
-    mdm_gemm_desc d = *desc_host;
-    if (d.N0 == 0) d.N0 = d.N;
+    const mdm_gemm_desc d = with_n0(*desc_host);
     if (!(!d.transposed && d.N % G == 0 && d.N0 == d.N && !d.D1 && !d.out_f32 && !d.acc0 && d.ldd0 == d.N)) return 0;
-    const int cpg = d.N / G;
-    if (!(cpg == 4 || cpg == 8 || cpg == 16 || cpg == 32 || cpg == 64)) return 0;
-    return (halo_tile(d) == 64 || lin2_gn_tile(d)) ? 1 : 0;
+    return fused_gn_tile(d, G);
 }
 extern "C" int mdm_gemm_plan(const mdm_gemm_desc* desc_host, int* splitk_out, int64_t* ws_bytes_out) {
     if (!splitk_out || !ws_bytes_out) { set_error("gemm_plan: null output"); return -1; }
@@ -4289,8 +4279,7 @@ extern "C" int mdm_gemm_plan(const mdm_gemm_desc* desc_host, int* splitk_out, in
 
 extern "C" int mdm_wgrad_group_accepts(const mdm_gemm_desc* desc_host) {
     if (!desc_host) return 0;
-    mdm_gemm_desc d = *desc_host;
-    if (d.N0 == 0) d.N0 = d.N;
+    const mdm_gemm_desc d = with_n0(*desc_host);
     return wgrad_lin_eligible(d) && d.out_f32 && d.N0 == d.N && d.ldd0 == d.N && d.dtap == (int64_t)d.M * d.N ? 1 : 0;
 }
 // Schedule of a group's nine-tap layers: ONE queue per CU, walked by one persistent workgroup (grid = CUs, table[round][queue]).

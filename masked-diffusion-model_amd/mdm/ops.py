@@ -177,7 +177,9 @@ def split_grad_reason(g: ConvGeom, which):
     """None if the `which` ("dgrad" | "wgrad") gradient of this convolution runs with split products under
     UNet(grad_products="split"), else why it stays exact fp32.  Both need whole 32-channel blocks on either side (the
     8-channel ends of the net stay exact); the data gradient as a forward convolution of dY through the flipped, transposed
-    shadow (mdm_split_shadow_t) exists for stride-1 3x3 "same" and 1x1 convolutions whose Cin is a whole 64-channel tile."""
+    shadow (mdm_split_shadow_t) exists for stride-1 3x3 "same" and 1x1 convolutions whose Cin is a whole 64-channel tile.
+    Whether the map then fits a split route is the library's rule (csrc/gemm.hip halo_tile_f32 / lin_split_tile): it is asked
+    (mdm_gemm_route_of on the descriptor the gradient would launch), not restated here."""
     if g.Cin % 32 or g.Cout % 32:
         return "channels"
     if which == "wgrad":
@@ -190,22 +192,8 @@ def split_grad_reason(g: ConvGeom, which):
         return "geometry"
     if g.Cin % 64:
         return "channels"
-    M = g.N * g.VH * g.VW
-    if same3:           # the pixel tiles of the halo kernel (csrc/gemm.hip halo_tile_f32): whole rows, whole images on small maps
-        pow2 = lambda v: v > 0 and (v & (v - 1)) == 0
-        pieces = lambda bm: ((bm // (g.VH * g.VW) if bm > g.VH * g.VW else 1) * ((g.VH if bm > g.VH * g.VW else bm // g.VW) + 2) *
-                             (g.VW + 2) + 7) // 8
-        if not (pow2(g.VH) and pow2(g.VW)):
-            return "geometry"
-        if g.VW in (4, 8):
-            if g.VH != g.VW or M % 64:
-                return "geometry"
-        elif g.VW not in (16, 32, 64) or not any(bm % g.VW == 0 and g.VH % (bm // g.VW) == 0 and M % bm == 0 and pieces(bm) <= 48
-                                                 for bm in (256, 128)):
-            return "geometry"
-    elif M < 64:
-        return "geometry"
-    return None
+    fields = conv_dgrad_split_fields(g, 16, 16, 16, 0, 16 if g.C1 else None, 0)      # dummy non-null pointers: no launch
+    return None if "split" in _lib.route_of(**fields) else "geometry"
 
 
 def conv_dgrad_split_fields(g: ConvGeom, dy, wT_split, dst0, acc0, dst1=None, acc1=0):

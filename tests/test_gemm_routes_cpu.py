@@ -49,3 +49,39 @@ def test_refused_descriptor_has_no_route():
     assert "N=60" in _lib.load().mdm_last_error().decode()
     assert _lib.pair_route_of(dict(f, N=60), f) == "none"
     assert _lib.pair_route_of(f, f) == "pair:two launches"
+
+
+# ---- the whole dispatch, differentially: scripts/route_sweep.py asks the library about a fixed grid of ~22 000 descriptors (route,
+# plan, both GroupNorm-fusion predicates, pair route).  The digests below were recorded from the parent of the change that made
+# launch_route an indexed call into the route table and gave the halo tiles one geometry rule (profiles/r09_route_table.md): a
+# host-side refactor of csrc/gemm.hip leaves them as they are, a change of the dispatch rule re-records them on purpose.
+SWEEP_CASES, SWEEP_SHA256 = 21890, "acbf675c38408ee594e59488c4c4aaac43d15b2d377241c74c507539c95fb43d"
+# ops.split_grad_reason of both gradients over the sweep's convolution geometries, recorded from the parent's mdm/ops.py (which
+# restated the tile rule in Python; it now asks mdm_gemm_route_of)
+REASON_ROWS, REASON_SHA256 = 5433, "89d1a19e206d444a7a4c65bf4a8049bc673efda265b35b5a4aa22fd8b080fd93"
+
+
+@pytest.fixture(scope="module")
+def route_sweep():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "route_sweep.py")
+    spec = importlib.util.spec_from_file_location("route_sweep", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_sweep_matches_the_recorded_dispatch(route_sweep):
+    from mdm import _lib, ops
+    lines, seen = route_sweep.sweep(_lib, ops)
+    missing = [n for n in _lib.route_names() if n not in seen and n.split("+")[0] not in route_sweep.NOT_FROM_MDM_GEMM]
+    assert not missing, f"the sweep never reaches {missing}"
+    assert (len(lines), route_sweep.digest(lines)) == (SWEEP_CASES, SWEEP_SHA256)
+
+
+def test_split_grad_reason_matches_the_recorded_table(route_sweep):
+    from mdm import ops
+    lines = route_sweep.reasons(ops)
+    assert {ln.split(" | ")[1] for ln in lines} == {"dgrad None", "dgrad channels", "dgrad stride2", "dgrad geometry"}
+    assert (len(lines), route_sweep.digest(lines)) == (REASON_ROWS, REASON_SHA256)
