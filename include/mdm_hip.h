@@ -408,6 +408,31 @@ int mdm_loss_fwd_bwd(int dtype, const void* pred, const float* x_in, const float
                      const float* w, int N, int C, int H, int W, int Cp, float gscale,
                      void* dpred, int64_t* loss_q40, void* stream);
 
+/* mdm_loss_fwd_bwd plus the sums behind the four per-step means the reference logs next to the loss
+ * (trainer_masked_mean_shift.py:176-179; trainer_masked.py:161-162 are two of them):
+ *   mon_q40[0] += mean((x_in + pred) - s)   inverse_reconstruct_train_mean  (x_in + pred when s is NULL)
+ *   mon_q40[1] += mean(x_in + pred)         reconstruct_train_mean
+ *   mon_q40[2] += mean(x_in)                shifted_degrade_img_mean
+ *   mon_q40[3] += mean(x_t)                 degraded_train_mean            (x_t: the degraded image, NCHW fp32)
+ * each in fp32 registers in the reference's order, summed thread -> wave -> workgroup like the loss and added as
+ * (partial / numel) in the same Q23.40 fixed point through integer atomics: bit-identical from run to run.
+ * mon_q40[4] counts partials that were not finite or >= 2^22; mon_q40[5] is reserved and stays 0.  mon_q40 is SIX int64
+ * words, zero before the step (mdm_monitor_commit leaves them so).  dpred and loss_q40 come out bit-identical to
+ * mdm_loss_fwd_bwd on the same arguments. */
+int mdm_loss_fwd_bwd_mon(int dtype, const void* pred, const float* x_in, const float* s, const float* x0,
+                         const float* w, int N, int C, int H, int W, int Cp, float gscale,
+                         void* dpred, int64_t* loss_q40, const float* x_t, int64_t* mon_q40, void* stream);
+/* Last launch of a monitored step: writes row (ctr[0] mod cap) of ring[cap][8] --
+ *   loss, the four means above in that order, sqrt(*gnorm_sq), mon_q40[4] (the flag count), 0
+ * -- then ++ctr[0] and mon_q40[0..5] = 0.  This is what trainer_masked_mean_shift.py:175-179 computes with five
+ * `.mean()` calls and :193 / :321-334 read with a host sync per value; here the host reads rows when it wants them.
+ * The loss is (double)loss_q40[0] * 2^-40 rounded to fp32, NaN when loss_q40[1] != 0 (loss_q40 is only read).  gnorm_sq: the
+ * squared gradient norm the optimizer kernel clipped with, or NULL (a micro-step without an update): the column is NaN.
+ * The row index lives in device memory, so a captured step replays with no host work (as mdm_sampler_step_params).
+ * ctr[0] counts modulo 2^32. */
+int mdm_monitor_commit(const int64_t* loss_q40, int64_t* mon_q40, const float* gnorm_sq, int32_t* ctr, float* ring,
+                       int cap, void* stream);
+
 /* Reverse-step pieces (sampler.py:146-152, 199-216):
  *   x0_hat = (x_in + pred) - s                                              (mdm_sampler_x0)
  *   x_t   <- x_t + (d_next - d_t)  [momentum]  |  x_t <- d_next  [base]     (mdm_sampler_update) */

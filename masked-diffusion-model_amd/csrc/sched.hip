@@ -3,7 +3,7 @@
 // reverse update.  NCHW fp32 like the reference's tensors; pure HBM streaming.
 //
 // Replaces reference scheduler.py:286-323, 438-477, 572-598 (degrade), :612-732, 757-777
-// (shift), trainer_masked_mean_shift.py:142-159 (loss), sampler.py:146-152, 199-216.
+// (shift), trainer_masked_mean_shift.py:142-159 (loss), :175-179 (the per-step monitors), sampler.py:146-152, 199-216.
 #include "common.h"
 
 namespace mdm {
@@ -190,13 +190,19 @@ __global__ void zero_pad_channels_kernel(T* x_nhwc, int C, int Cp, int64_t npix)
 // One thread per PIXEL (n, p): its Cp padded channels of pred / dpred are contiguous (NHWC), the fp32 operands are NCHW planes
 // that neighbouring threads read at neighbouring addresses, and every load of a thread is independent of the others (the
 // element-per-thread version walked 8 dependent iterations of three scattered loads: 15 us for 100 k elements).
-template <typename T>
+//
+// MON: the same launch also sums the four tensors the reference logs a mean of after every step
+// (trainer_masked_mean_shift.py:176-179) -- (x_in + pred) - s, x_in + pred, x_in and x_t -- from the registers the loss
+// already holds (one more plane, x_t, is read).  The loss arithmetic is the same expression tree in both instantiations:
+// dpred and the loss words do not depend on MON.
+template <typename T, bool MON>
 __global__ __launch_bounds__(256) void loss_kernel(const T* pred, const float* x_in, const float* s, const float* x0,
                                                    const float* w, int N, int C, int HW, int Cp, float gscale, T* dpred,
-                                                   unsigned long long* loss_q40) {
+                                                   unsigned long long* loss_q40, const float* x_t, unsigned long long* mon_q40) {
     const int64_t npix = (int64_t)N * HW;
     const float inv_numel = 1.f / ((float)N * (float)C * (float)HW);
     float local = 0.f;
+    float mon[4] = {0.f, 0.f, 0.f, 0.f};      // inverse-shifted reconstruction, reconstruction, x_in, x_t
     for (int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pix < npix; pix += (int64_t)gridDim.x * blockDim.x) {
         const int n = (int)(pix / HW), p = (int)(pix - (int64_t)n * HW);
         const float wn = w ? w[n] : 1.f;
@@ -216,8 +222,11 @@ __global__ __launch_bounds__(256) void loss_kernel(const T* pred, const float* x
                 if (c < C) {
                     const int64_t o = ((int64_t)n * C + c) * HW + p;
                     // fp32 registers, reference order: (x_in + pred) - s - x0
-                    float r = x_in[o] + pv[e];
+                    const float xi = x_in[o];
+                    float r = xi + pv[e];
+                    if (MON) mon[1] += r;
                     if (s) r -= s[o];
+                    if (MON) { mon[0] += r; mon[2] += xi; mon[3] += x_t[o]; }
                     r -= x0[o];
                     local = fmaf(wn * r, r, local);
                     g[e] = 2.f * wn * r * inv_numel * gscale;
@@ -241,6 +250,41 @@ __global__ __launch_bounds__(256) void loss_kernel(const T* pred, const float* x
         if (fabsf(v) < 4194304.f) atomicAdd(loss_q40, (unsigned long long)__float2ll_rn(v * 1099511627776.f));
         else atomicAdd(loss_q40 + 1, 1ull);
     }
+    if (MON) {
+        // the same tree for each of the four sums: thread (serial) -> wave -> the workgroup's four waves -> Q23.40
+        __shared__ float mpart[4][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float mv = wave_sum(mon[q]);
+            if ((threadIdx.x & 63) == 0) mpart[q][threadIdx.x >> 6] = mv;
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            const int q = threadIdx.x;
+            const float v = ((mpart[q][0] + mpart[q][1]) + (mpart[q][2] + mpart[q][3])) * inv_numel;
+            if (fabsf(v) < 4194304.f) atomicAdd(mon_q40 + q, (unsigned long long)__float2ll_rn(v * 1099511627776.f));
+            else atomicAdd(mon_q40 + 4, 1ull);
+        }
+    }
+}
+
+// Last launch of a monitored step: one ring row from the step's accumulators.  One wave; lanes 0..7 each store one column.
+// The row index comes from a counter in device memory, so a captured step replays with no host work (sampler_step_kernel).
+__global__ __launch_bounds__(64) void monitor_commit_kernel(const long long* loss_q40, long long* mon_q40, const float* gnorm_sq,
+                                                            unsigned int* ctr, float* ring, unsigned int cap) {
+    const int t = threadIdx.x;
+    const unsigned int c = ctr[0];
+    const double q40 = 9.094947017729282379150390625e-13;      // 2^-40
+    const float qnan = __builtin_nanf("");
+    float v = 0.f;
+    if (t == 0) v = loss_q40[1] ? qnan : (float)((double)loss_q40[0] * q40);
+    else if (t <= 4) v = (float)((double)mon_q40[t - 1] * q40);
+    else if (t == 5) v = gnorm_sq ? __fsqrt_rn(gnorm_sq[0]) : qnan;
+    else if (t == 6) v = (float)mon_q40[4];
+    if (t < 8) ring[(int64_t)(c % cap) * 8 + t] = v;
+    __syncthreads();                       // every lane has read the counter and its accumulator word
+    if (t < 6) mon_q40[t] = 0;
+    if (t == 0) ctr[0] = c + 1u;
 }
 
 template <typename T>
@@ -363,19 +407,45 @@ extern "C" int mdm_zero_pad_channels(int dtype, void* x_nhwc, int64_t npix, int 
     return launch_status("zero_pad_channels");
 }
 
-extern "C" int mdm_loss_fwd_bwd(int dtype, const void* pred, const float* x_in, const float* s, const float* x0, const float* w,
-                                int N, int C, int H, int W, int Cp, float gscale, void* dpred, int64_t* loss_q40, void* stream) {
-    MDM_REQUIRE(pred && x_in && x0 && loss_q40 && Cp >= C && Cp % 8 == 0, "loss: bad arguments (Cp must be a multiple of 8)");
+template <bool MON>
+static int launch_loss(int dtype, const void* pred, const float* x_in, const float* s, const float* x0, const float* w, int N, int C,
+                       int H, int W, int Cp, float gscale, void* dpred, int64_t* loss_q40, const float* x_t, int64_t* mon_q40,
+                       void* stream) {
     unsigned long long* loss_accum = reinterpret_cast<unsigned long long*>(loss_q40);
+    unsigned long long* mon_accum = reinterpret_cast<unsigned long long*>(mon_q40);
     int grid = sgrid((int64_t)N * H * W);
     if (grid > 256) grid = 256;            // one same-address atomic per workgroup at the end: keep them few
     if (dtype == MDM_BF16)
-        hipLaunchKernelGGL((loss_kernel<bf16_t>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, x_in, s, x0, w,
-                           N, C, H * W, Cp, gscale, (bf16_t*)dpred, loss_accum);
+        hipLaunchKernelGGL((loss_kernel<bf16_t, MON>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, x_in, s,
+                           x0, w, N, C, H * W, Cp, gscale, (bf16_t*)dpred, loss_accum, x_t, mon_accum);
     else
-        hipLaunchKernelGGL((loss_kernel<float>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)pred, x_in, s, x0, w, N,
-                           C, H * W, Cp, gscale, (float*)dpred, loss_accum);
+        hipLaunchKernelGGL((loss_kernel<float, MON>), dim3(grid), dim3(256), 0, (hipStream_t)stream, (const float*)pred, x_in, s, x0,
+                           w, N, C, H * W, Cp, gscale, (float*)dpred, loss_accum, x_t, mon_accum);
     return launch_status("loss");
+}
+
+extern "C" int mdm_loss_fwd_bwd(int dtype, const void* pred, const float* x_in, const float* s, const float* x0, const float* w,
+                                int N, int C, int H, int W, int Cp, float gscale, void* dpred, int64_t* loss_q40, void* stream) {
+    MDM_REQUIRE(pred && x_in && x0 && loss_q40 && Cp >= C && Cp % 8 == 0, "loss: bad arguments (Cp must be a multiple of 8)");
+    return launch_loss<false>(dtype, pred, x_in, s, x0, w, N, C, H, W, Cp, gscale, dpred, loss_q40, nullptr, nullptr, stream);
+}
+
+extern "C" int mdm_loss_fwd_bwd_mon(int dtype, const void* pred, const float* x_in, const float* s, const float* x0, const float* w,
+                                    int N, int C, int H, int W, int Cp, float gscale, void* dpred, int64_t* loss_q40,
+                                    const float* x_t, int64_t* mon_q40, void* stream) {
+    MDM_REQUIRE(pred && x_in && x0 && loss_q40 && Cp >= C && Cp % 8 == 0, "loss: bad arguments (Cp must be a multiple of 8)");
+    MDM_REQUIRE(dtype == MDM_F32 || dtype == MDM_BF16, "loss_mon: bad dtype %d", dtype);
+    MDM_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "loss_mon: bad shape");
+    MDM_REQUIRE(x_t && mon_q40, "loss_mon: x_t and mon_q40 are required");
+    return launch_loss<true>(dtype, pred, x_in, s, x0, w, N, C, H, W, Cp, gscale, dpred, loss_q40, x_t, mon_q40, stream);
+}
+
+extern "C" int mdm_monitor_commit(const int64_t* loss_q40, int64_t* mon_q40, const float* gnorm_sq, int32_t* ctr, float* ring, int cap,
+                                  void* stream) {
+    MDM_REQUIRE(loss_q40 && mon_q40 && ctr && ring && cap > 0, "monitor_commit: bad arguments");
+    hipLaunchKernelGGL(monitor_commit_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(loss_q40),
+                       reinterpret_cast<long long*>(mon_q40), gnorm_sq, reinterpret_cast<unsigned int*>(ctr), ring, (unsigned int)cap);
+    return launch_status("monitor_commit");
 }
 
 extern "C" int mdm_sampler_x0(int dtype, const void* pred_nhwc, int Cp, const float* x_in, const float* s, int N, int C, int H,

@@ -12,6 +12,7 @@ from .dist import GradComm  # noqa: F401
 from .optim import EMA, SGD, Accelerator, Adam, AdamW, get_lr_scheduler, get_optimizer  # noqa: F401
 from .sampler import Sampler  # noqa: F401
 from .scheduler import Scheduler  # noqa: F401
+from .train_step import MonitorRing  # noqa: F401
 from .trainer import BaseTrainer, Trainer  # noqa: F401
 from .unet import UNet, unet6_config  # noqa: F401
 from .unet2d import UNet2D, my_model_config  # noqa: F401

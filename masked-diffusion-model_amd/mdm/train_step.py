@@ -17,6 +17,10 @@ Two ways to run it:
                         backward is cut at the gradient-bucket boundaries (front / pieces / tail graphs) and
                         each bucket's all-reduce is issued behind the piece that completes it.
 
+Monitors (`args.monitor`): the loss launch also sums the four tensors whose means the reference logs after every step
+(ms:175-179) and a last launch, mdm_monitor_commit, writes them with the loss and the pre-clip gradient norm into one
+row of a device-side ring (MonitorRing) -- one row per micro-step, in both modes and every graph form.
+
 Gradient accumulation (`grad_accum` > 1; `accelerator.accumulate` + `sync_gradients` upstream, ms:139-172): a
 micro-step runs forward + loss (gradient scaled by 1 / grad_accum, what `accelerator.backward` does) + backward and
 adds its gradient buffer to `Gacc`; the step that syncs adds `Gacc` to its own gradient, exchanges (data parallel:
@@ -50,6 +54,72 @@ class LossCell:
     __float__ = item
 
 
+class MonitorRing:
+    """Device-side log of the per-step scalars the reference computes with five `.mean()` calls and reads with a host sync each
+    (trainer_masked_mean_shift.py:175-179, 193): mdm_loss_fwd_bwd_mon sums them inside the loss kernel into `mon_q40`, and
+    mdm_monitor_commit -- the last launch of a step -- writes one row of `ring[cap][8]` at a counter that lives on the device, so a
+    captured step graph replays without host work.  The host reads when it wants to: `last()` one row (32 bytes), `read()` the
+    counter and the whole ring in ONE device-to-host copy.
+
+    `buf` is that one allocation: int32 words, [0] the commit counter (modulo 2^32), [8:] the rows as fp32.  `cursor` counts the
+    rows `read()` has handed out, `issued` the commits the host has enqueued (TrainStep bumps it; `read()` resynchronises it)."""
+
+    COLUMNS = ("train_loss", "inverse_reconstruct_train_mean", "reconstruct_train_mean", "shifted_degrade_img_mean",
+               "degraded_train_mean", "grad_norm", "flags", "reserved")
+
+    def __init__(self, device, cap=4096):
+        self.cap = int(cap)
+        if self.cap < 1:
+            raise ValueError(f"monitor_cap={cap}")
+        self.buf = torch.zeros(8 + 8 * self.cap, device=device, dtype=torch.int32)
+        self.ctr = self.buf[:1]
+        self.ring = self.buf[8:].view(torch.float32).view(self.cap, 8)
+        self.mon_q40 = torch.zeros(6, device=device, dtype=torch.int64)
+        self.cursor = 0
+        self.issued = 0
+
+    def _snapshot(self):
+        h = self.buf.cpu().numpy()                      # the one copy (synchronises)
+        return int(h[0]) & 0xFFFFFFFF, h[8:].view("float32").reshape(self.cap, 8)
+
+    def read(self):
+        """-> (rows, dropped): the rows committed since the last `read()`, oldest first, as a float32 array [n, 8], and the number
+        of rows that were overwritten before they were read (they are not in `rows`)."""
+        ctr, ring = self._snapshot()
+        new = (ctr - self.cursor) & 0xFFFFFFFF
+        dropped = max(0, new - self.cap)
+        first = ctr - (new - dropped)               # commit numbers are modulo 2^32, like the device's unsigned counter
+        rows = ring[[((first + i) & 0xFFFFFFFF) % self.cap for i in range(new - dropped)]].copy()
+        self.cursor = self.issued = ctr
+        return rows, dropped
+
+    def last(self):
+        """The newest row the host has enqueued a commit for (a 32-byte copy; synchronises)."""
+        if self.issued == 0:
+            raise RuntimeError("MonitorRing.last(): no step has been committed")
+        return self.ring[((self.issued - 1) & 0xFFFFFFFF) % self.cap].cpu().numpy()
+
+    def row(self, seq):
+        """Row of commit number `seq` (0-based, as `issued` stood before the step); raises once it has been overwritten."""
+        if (self.issued - seq) > self.cap:
+            raise RuntimeError(f"MonitorRing: row {seq} was overwritten before it was read ({self.issued - seq - self.cap} rows "
+                               f"dropped; monitor_cap={self.cap})")
+        return self.ring[(seq & 0xFFFFFFFF) % self.cap].cpu().numpy()
+
+
+class DeferredLoss:
+    """What `Trainer._run_batch` returns under `args.defer_loss`: the step's place in the monitor ring.  `float()` / `.item()`
+    read it there (and synchronise); until then the host has not waited for the step."""
+
+    def __init__(self, ring, seq, column=0):
+        self.ring, self.seq, self.column = ring, seq, column
+
+    def item(self):
+        return float(self.ring.row(self.seq)[self.column])
+
+    __float__ = item
+
+
 class TrainStep:
     def __init__(self, model, scheduler, args, optimizer, ema=None, mean_shift=True, comm=None, max_norm=1.0, grad_accum=1):
         self.model, self.S, self.args, self.opt, self.ema = model, scheduler, args, optimizer, ema
@@ -74,6 +144,8 @@ class TrainStep:
         self.mean_pixel = f(N, C)
         self.w = f(N)
         self.loss = LossCell(dev)
+        # per-step monitors (MonitorRing): off = nothing allocated, the launches below are exactly the unmonitored ones
+        self.mon = MonitorRing(dev, getattr(args, "monitor_cap", 4096)) if getattr(args, "monitor", False) else None
         self.amount = torch.zeros(N, device=dev, dtype=torch.float64)
         self.ratio = torch.zeros(N, device=dev, dtype=torch.float64)
         self.tidx = torch.zeros(N, device=dev, dtype=torch.int32)
@@ -103,8 +175,26 @@ class TrainStep:
              float(getattr(a, "noise_mean", 0.0)), per_col, N, C, H, W, ptr(self.s), ptr(self.x_in), m.dt,
              ptr(m.x_in.data), m.cin_p, stream())
         m.forward_plan.run() if _lib._recording is None else _lib._recording.extend(m.forward_plan)
-        call("mdm_loss_fwd_bwd", m.dt, ptr(m.y_out.data), ptr(self.x_in), ptr(self.s) if kind != 0 else None, ptr(self.x0),
-             ptr(self.w) if weights_on else None, N, C, H, W, m.cout_p, 1.0 / self.grad_accum, ptr(m.y_out.grad), ptr(self.loss.raw), stream())
+        head = (m.dt, ptr(m.y_out.data), ptr(self.x_in), ptr(self.s) if kind != 0 else None, ptr(self.x0),
+                ptr(self.w) if weights_on else None, N, C, H, W, m.cout_p, 1.0 / self.grad_accum, ptr(m.y_out.grad), ptr(self.loss.raw))
+        if self.mon is None:
+            call("mdm_loss_fwd_bwd", *head, stream())
+        else:
+            call("mdm_loss_fwd_bwd_mon", *head, ptr(self.x_t), ptr(self.mon.mon_q40), stream())
+
+    def _emit_commit(self, with_norm):
+        """The monitored step's last launch: one ring row.  `with_norm`: the optimizer update ran (its squared norm is current)."""
+        mon = self.mon
+        if mon is None:
+            return
+        call("mdm_monitor_commit", ptr(self.loss.raw), ptr(mon.mon_q40), ptr(self.opt.sqnorm) if with_norm else None,
+             ptr(mon.ctr), ptr(mon.ring), mon.cap, stream())
+
+    def _committed(self, loss):
+        """Every step -- whatever path it took below -- has enqueued exactly one commit: the host's count follows here, once."""
+        if self.mon is not None:
+            self.mon.issued += 1
+        return loss
 
     def _hyper(self):
         d = self.ema.next_decay() if self.ema is not None else 0.0
@@ -112,6 +202,12 @@ class TrainStep:
 
     # ---- replay mode (parity) --------------------------------------------------------------
     def run_replay(self, x0, used, sync=True):
+        return self._committed(self._run_replay(x0, used, sync))
+
+    def run_device(self, x0, used, sync=True):
+        return self._committed(self._run_device(x0, used, sync))
+
+    def _run_replay(self, x0, used, sync=True):
         """Eager step with the reference's host RNG order. Returns the loss cell.  `sync`: this micro-step
         ends in the optimizer update (always, unless grad_accum > 1)."""
         m, S, a = self.model, self.S, self.args
@@ -158,10 +254,12 @@ class TrainStep:
         self.last = dict(timeindex=timeindex, t=t)
         if self.grad_accum > 1 and not sync:
             ops.add_(_lib.F32, self.Gacc, m.store.G)
+            self._emit_commit(False)
             return self.loss
         if self.grad_accum > 1:
             ops.add_(_lib.F32, m.store.G, self.Gacc)
         self._finish_update()
+        self._emit_commit(True)
         if self.grad_accum > 1:
             ops.fill(self.Gacc, 0.0)
         return self.loss
@@ -228,6 +326,7 @@ class TrainStep:
         with _lib.Recording() as tail:
             gmul = 1.0 / self.comm.world if self.comm is not None else 1.0
             self.opt.emit_update(self.ema.shadow if self.ema is not None else None, self.max_norm, gmul)
+            self._emit_commit(True)
         mk = (lambda r: _lib.GraphExec(r)) if self.use_graph else (lambda r: r)
 
         def rec(cs):
@@ -256,7 +355,7 @@ class TrainStep:
         rest = mk(rec(calls[lo:])) if lo < len(calls) else None
         self._graphs = ("cut", mk(front), pieces, rest, mk(tail))
 
-    def run_device(self, x0, used, sync=True):
+    def _run_device(self, x0, used, sync=True):
         """Device-RNG step as hipGraph replays.  `x0` None = reuse the batch already in `self.x0`.  `sync`: see run_replay."""
         if x0 is not None:
             self.x0.copy_(x0.to(torch.float32), non_blocking=True)
@@ -271,6 +370,7 @@ class TrainStep:
             go(front); go(bwd)
             if not sync:
                 ops.add_(_lib.F32, self.Gacc, G)
+                self._emit_commit(False)
                 return self.loss
             ops.add_(_lib.F32, G, self.Gacc)
             if self.comm is not None:

@@ -6,18 +6,27 @@
 broken upstream (D2) -- the arithmetic is mean-shift with no shift, int timesteps and three return
 values.  Image grids / wandb / matplotlib output of the reference are out of scope:
 samples are saved as tensors.
+
+`args.monitor` turns on the reference's per-step logging surface (ms:61-64, 175-179, 249-250, 321-334): `loss_names` is
+its five names, the five attributes hold the step's values after every `_run_batch`, `get_current_losses()` /
+`get_current_mean()` return its OrderedDicts and `train()` hands them to `visualizer.plot_current_losses`.  The values
+come from the device-side ring of mdm.MonitorRing, not from torch reductions.  Under data parallelism they are THIS
+rank's (upstream logs the main process's local values too: ms:249 runs on the main process over its own tensors).
+`args.defer_loss` (needs `monitor`): `_run_batch` returns a handle instead of a float and `_run_epoch` reads the ring once
+per epoch (once per `monitor_cap` steps when the dataloader is longer), so an epoch runs without a host sync per step.
 """
 from __future__ import annotations
 
 import os
 import statistics
+from collections import OrderedDict
 
 import torch
 
 from .dist import GradComm
 from .sampler import Sampler
 from .scheduler import Scheduler
-from .train_step import TrainStep
+from .train_step import DeferredLoss, MonitorRing, TrainStep
 
 
 class Trainer:
@@ -36,7 +45,12 @@ class Trainer:
         ema = ema_model if getattr(args, "use_ema", False) else None
         self.step = TrainStep(model, self.Scheduler, args, optimizer, ema, mean_shift=self.mean_shift, comm=comm,
                               grad_accum=getattr(accelerator, "gradient_accumulation_steps", 1))
-        self.loss_names = ["train_loss"]
+        self.monitor = self.step.mon is not None
+        self.defer_loss = bool(getattr(args, "defer_loss", False))
+        if self.defer_loss and not self.monitor:
+            raise ValueError("args.defer_loss needs args.monitor: a deferred loss is read from the monitor ring")
+        self.loss_names = list(MonitorRing.COLUMNS[:5]) if self.monitor else ["train_loss"]          # ms:61
+        self.mean_names = ["ema_sample_mean"]                                                        # ms:64
         # what `accelerator.save_state(path)` / `load_state(path)` cover (main_train_masked.py:195-225 hooks)
         reg = getattr(accelerator, "register_for_checkpointing", None)
         if reg is not None:
@@ -71,22 +85,80 @@ class Trainer:
         self.reconstruct_loss = loss
         return loss
 
+    def _set_monitors(self, row):
+        """ms:175-179: the five attributes of `loss_names`, as Python floats, from one ring row."""
+        for name, v in zip(MonitorRing.COLUMNS[:5], row[:5]):
+            setattr(self, name, float(v))
+        if row[6] != 0:                            # a partial sum was not representable and is missing from some mean: say so
+            for name in MonitorRing.COLUMNS[1:5]:
+                setattr(self, name, float("nan"))
+
+    def _monitored(self, columns):
+        """What `_run_batch` returns under `monitor`: ring columns of the step just issued -- read now (one 32-byte copy: the
+        step's one sync, like ms:193), or as handles under `defer_loss` (no sync)."""
+        ring = self.step.mon
+        if self.defer_loss:
+            return [DeferredLoss(ring, ring.issued - 1, c) for c in columns]
+        row = ring.last()
+        self._set_monitors(row)
+        return [float(row[c]) for c in columns]
+
     def _run_batch(self, batch, input, epoch, epoch_length, resume_step, dirs, visualizer):
         loss = self._step(input)
         s = self.step
         self.input, self.degraded_img, self.degrade_binary_masks = s.x0, s.x_t, s.mask
         self.shift, self.shifted_degrade_img = s.s, s.x_in
-        return loss.item()                         # the reference syncs here too (ms:193)
+        if self.monitor:
+            return self._monitored((0,))[0]
+        self.train_loss = loss.item()              # the reference syncs here too (ms:175, 193)
+        return self.train_loss
+
+    def _deferred_rows(self, epoch, epoch_length, resume_step, dirs, visualizer):
+        """The batch loop of an epoch under `defer_loss`: every step is issued without a host sync and the ring is read once at the
+        end -- or every `monitor_cap` steps when the dataloader is longer than the ring.  -> the epoch's rows [n, 8]."""
+        import numpy as np
+        ring = self.step.mon
+        ring.read()                                # rows of earlier steps (direct `_run_batch` calls) are read here and left out:
+        chunks, pending = [], 0                    # they are not this epoch's -- one sync per epoch, before its first step
+
+        def drain():
+            rows, dropped = ring.read()
+            if dropped:
+                raise RuntimeError(f"monitor ring overran: {dropped} rows were overwritten before they were read (monitor_cap={ring.cap})")
+            chunks.append(rows)
+        for i, input in enumerate(self.dataloader, 0):
+            self._mark_end_of_dataloader(i)
+            self._run_batch(i, input, epoch, epoch_length, resume_step, dirs, visualizer)
+            pending += 1
+            if pending == ring.cap:
+                drain()
+                pending = 0
+        drain()
+        rows = np.concatenate(chunks)
+        if len(rows):
+            self._set_monitors(rows[-1])
+        return rows
 
     def _run_epoch(self, epoch, epoch_length, resume_step, dirs, visualizer):
         loss_batch = []
         self.timesteps_used_epoch = self.Scheduler.get_timesteps_epoch(epoch, epoch_length)
+        if self.defer_loss:
+            rows = self._deferred_rows(epoch, epoch_length, resume_step, dirs, visualizer)
+            return [float(v) for v in rows[:, 0]] if self.accelerator.is_main_process else loss_batch
         for i, input in enumerate(self.dataloader, 0):
             self._mark_end_of_dataloader(i)
             loss = self._run_batch(i, input, epoch, epoch_length, resume_step, dirs, visualizer)
             if self.accelerator.is_main_process:
                 loss_batch.append(loss)
         return loss_batch
+
+    def get_current_losses(self):
+        """ms:321-327."""
+        return OrderedDict((name, float(getattr(self, name))) for name in self.loss_names if isinstance(name, str))
+
+    def get_current_mean(self):
+        """ms:329-334.  As upstream, `ema_sample_mean` exists once `_save_ema_momentum_sample` has run."""
+        return OrderedDict((name, float(getattr(self, name))) for name in self.mean_names if isinstance(name, str))
 
     def _mark_end_of_dataloader(self, i):
         """accelerate's prepared dataloader flags its last batch, and `accumulate` syncs there whatever the micro-step
@@ -108,6 +180,8 @@ class Trainer:
             loss = self._epoch_losses(self._run_epoch(epoch, epoch_length, resume_step, dirs, visualizer))
             if self.accelerator.is_main_process:
                 loss_mean_epoch.append(statistics.mean(loss))
+                if self.monitor and visualizer is not None:
+                    visualizer.plot_current_losses(epoch, self.get_current_losses(), 'value')        # ms:249-250
             last = epoch == (epoch_start + epoch_length - 1)
             if (epoch > 0 and (epoch + 1) % a.save_images_epochs == 0) or last or \
                     (epoch + 1) % (epoch_length / a.scheduler_num_scale_timesteps) == 0:      # ms:252
@@ -149,17 +223,25 @@ class BaseTrainer(Trainer):
         loss = self._step(input)
         s = self.step
         self.input, self.degraded_img, self.degrade_binary_masks = s.x0, s.x_t, s.mask
+        if self.monitor:
+            # base:161-162 from the ring: mean(x_t + pred) and mean(x_t) are the reconstruction and degraded columns (no shift:
+            # x_in is x_t).  No layout kernel, no torch arithmetic, one sync; `mask` / `reconstructed_img` are not materialised.
+            return tuple(self._monitored((0, 2, 4)))
         pred = torch.empty_like(s.x0)
         from . import ops
         m = self.model
         ops.nhwc_to_nchw(m.dt, m.y_out.data, pred, m.N, m.cout, m.H, m.W, m.cout_p)
         self.mask = pred
         self.reconstructed_img = s.x_t + pred                                               # base:126
-        return loss.item(), self.reconstructed_img.mean().item(), s.x_t.mean().item()       # base:183
+        self.train_loss = loss.item()
+        return self.train_loss, self.reconstructed_img.mean().item(), s.x_t.mean().item()   # base:183
 
     def _run_epoch(self, epoch, epoch_length, resume_step, dirs, visualizer):
         out = ([], [], [])
         self.timesteps_used_epoch = self.Scheduler.get_timesteps_epoch(epoch, epoch_length)
+        if self.defer_loss:
+            rows = self._deferred_rows(epoch, epoch_length, resume_step, dirs, visualizer)
+            return tuple([float(v) for v in rows[:, c]] for c in (0, 2, 4)) if self.accelerator.is_main_process else out
         for i, input in enumerate(self.dataloader, 0):
             self._mark_end_of_dataloader(i)
             r = self._run_batch(i, input, epoch, epoch_length, resume_step, dirs, visualizer)
