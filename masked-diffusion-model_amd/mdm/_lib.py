@@ -1,12 +1,18 @@
-"""ctypes binding of libmdm_hip.so (include/mdm_hip.h).
+"""ctypes binding of libmdm_hip.so.
 
-The product path has NO fallback: if the shared library is missing, or a call
+include/mdm_hip.h is the only statement of the C ABI: the two descriptor structs, every prototype and the parameter
+names below are parsed from it at import.  To add an entry point, declare it in the header -- nothing else.
+
+The product path has NO fallback: if the shared library or the header is missing, or a call
 returns non-zero, a RuntimeError is raised.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import inspect
 import os
+import re
 
 import torch
 
@@ -14,128 +20,87 @@ F32, BF16 = 0, 1
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (MDM_LIB_PATH: load another BUILD of the same library -- A/B timing of two builds on one box; it selects a file, not a code path)
 LIB_PATH = os.environ.get("MDM_LIB_PATH") or os.path.join(_HERE, "libmdm_hip.so")
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "mdm_hip.h"))
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
+_SCALARS = {"int": i32, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32}
+
+_TOP = re.compile(r'\s*(?:extern\s+"C"\s*\{|\}|typedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;|([^;{}()]+)\(([^;{}()]*)\)\s*;)')
+_DECL = re.compile(r"(?:const\s+)?(\w+)\s*(\**)\s*(\w*)")
+
+
+def _declaration(text, where):
+    """`[const] T[*..] name` -> (name, type): type "T" for a known scalar, "T*" / "T**" for any pointer.  Everything else raises."""
+    m = _DECL.fullmatch(text.strip())
+    if not m:
+        raise ValueError(f"mdm_hip.h: cannot split `{text.strip()}` into type and name in `{where}`")
+    base, stars, name = m.groups()
+    if not name:
+        raise ValueError(f"mdm_hip.h: `{text.strip()}` has no name in `{where}`")
+    if not stars and base not in _SCALARS:
+        raise ValueError(f"mdm_hip.h: unknown type `{base}` of `{name}` in `{where}`")
+    return name, base + stars
+
+
+def parse_header(text):
+    """The C ABI as text -> ({struct: [(field, type)]}, {function: (return type, [(parameter, type)])}) in the header's order.
+    Closed: whatever is not a comment, a preprocessor line, the `extern "C"` bracket, a `typedef struct` or a prototype raises,
+    and so does every declaration `_declaration` refuses.  Nothing is skipped."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    structs, protos, pos = {}, {}, 0
+    while text[pos:].strip():
+        m = _TOP.match(text, pos)
+        if not m:
+            raise ValueError(f"mdm_hip.h: cannot parse `{' '.join(text[pos:].split())[:80]}`")
+        pos, where = m.end(), " ".join(m.group(0).split())
+        body, struct, head, params = m.groups()
+        if struct:
+            fields = structs[struct] = []
+            for stmt in filter(None, (s.strip() for s in body.split(";"))):
+                first, *more = stmt.split(",")
+                name, typ = _declaration(first, f"{struct}: {stmt}")
+                if more and typ not in _SCALARS:      # `float* a, b` declares ONE pointer
+                    raise ValueError(f"mdm_hip.h: one pointer per declaration in `{struct}: {stmt}`")
+                fields += [(name, typ)] + [_declaration(f"{typ} {n}", f"{struct}: {stmt}") for n in more]
+        elif head:
+            name, rtype = _declaration(head, where)
+            protos[name] = (rtype, [] if params.strip() in ("", "void") else [_declaration(p, where) for p in params.split(",")])
+    return structs, protos
+
+
+if not os.path.exists(HEADER_PATH):
+    raise RuntimeError(
+        f"{HEADER_PATH} is missing: it is the only statement of libmdm_hip.so's C ABI and this binding is built from it at import "
+        "(include/ sits next to masked-diffusion-model_amd/).  There is no fallback.")
+with open(HEADER_PATH) as _f:
+    _STRUCTS, _DECLS = parse_header(_f.read())
+
+_DESC_PTR = {}
+
+
+def _ctype(typ, ret=False):
+    """Scalars by name; a pointer to a descriptor struct is typed; a returned `const char*` is bytes; every other pointer is void*."""
+    return C.c_char_p if ret and typ == "char*" else _SCALARS.get(typ) or _DESC_PTR.get(typ, vp)
 
 
 class GemmDesc(C.Structure):
-    """Mirror of `mdm_gemm_desc` (include/mdm_hip.h)."""
-    _fields_ = [
-        ("dtype", i32), ("layout", i32), ("M", i32), ("N", i32), ("K", i32), ("batch", i32),
-        ("sA", i64), ("sB", i64), ("sD", i64), ("sR", i64),
-        ("A", vp), ("lda", i32), ("f32_split", i32),
-        ("B", vp), ("ldb", i32), ("_p1", i32),
-        ("conv", i32), ("OH", i32), ("OW", i32), ("IH", i32), ("IW", i32),
-        ("KH", i32), ("KW", i32), ("stride", i32), ("pad_t", i32), ("pad_l", i32), ("transposed", i32), ("ups", i32),
-        ("C0", i32), ("C1", i32), ("Ck", i32),
-        ("src0", vp), ("src1", vp), ("ld0", i32), ("ld1", i32), ("wtap", i64),
-        ("D0", vp), ("D1", vp), ("ldd0", i32), ("ldd1", i32), ("N0", i32), ("out_f32", i32), ("alpha", f32),
-        ("acc0", i32), ("acc1", i32), ("bias", vp), ("rowvec", vp), ("rv_ld", i32), ("rows_per_img", i32),
-        ("resid", vp), ("ldr", i32), ("splitk", i32), ("dtap", i64), ("ws", vp), ("ws_bytes", i64), ("dbias", vp),
-        ("gnb_x", vp), ("gnb_stats", vp), ("gnb_gamma", vp), ("gnb_beta", vp), ("gnb_dgamma", vp), ("gnb_dbeta", vp),
-        ("gnb_sum_img", vp), ("gnb_sum_all", vp), ("gnb_G", i32), ("gnb_silu", i32), ("gnb_sum_ld", i32), ("_p3", i32), ("gnb_add", vp),
-        ("gnf_out", vp), ("gnf_gamma", vp), ("gnf_beta", vp), ("gnf_stats", vp), ("gnf_G", i32), ("gnf_silu", i32), ("gnf_eps", f32), ("_p4", i32),
-        ("B_split", vp),
-    ]
+    """`mdm_gemm_desc` as include/mdm_hip.h declares it: the header is the only statement, a new field goes there and nowhere else."""
+    _fields_ = [(n, _ctype(t)) for n, t in _STRUCTS["mdm_gemm_desc"]]
     _defaults = dict(alpha=1.0, batch=1)
 
 
 class GnDesc(C.Structure):
-    """Mirror of `mdm_gn_desc` (include/mdm_hip.h)."""
-    _fields_ = [
-        ("src0", vp), ("src1", vp), ("gamma", vp), ("beta", vp), ("stats", vp), ("ws", vp), ("y", vp),
-        ("dy", vp), ("dst0", vp), ("add0", vp), ("add0b", vp), ("dst1", vp), ("add1", vp), ("dgamma", vp), ("dbeta", vp),
-        ("sum_img", vp), ("sum_all", vp), ("rng", vp), ("drop_base", u64), ("ctl", vp),
-        ("dtype", i32), ("N", i32), ("P", i32), ("G", i32), ("C0", i32), ("C1", i32), ("silu", i32), ("sum_ld", i32),
-        ("eps", f32), ("_pad", i32),
-    ]
+    """`mdm_gn_desc` as include/mdm_hip.h declares it: the header is the only statement, a new field goes there and nowhere else."""
+    _fields_ = [(n, _ctype(t)) for n, t in _STRUCTS["mdm_gn_desc"]]
     _defaults = {}
 
 
-_PROTOS = {
-    "mdm_version": ([], i32),
-    "mdm_device_count": ([], i32),
-    "mdm_gemm": ([C.POINTER(GemmDesc), vp], i32),
-    "mdm_gemm_pair": ([C.POINTER(GemmDesc), C.POINTER(GemmDesc), vp], i32),
-    "mdm_wgrad_group_accepts": ([C.POINTER(GemmDesc)], i32),
-    "mdm_wgrad_group_create": ([C.POINTER(GemmDesc), i32, vp, i64, C.POINTER(i64), C.POINTER(vp)], i32),
-    "mdm_wgrad_group_launch": ([vp, vp], i32),
-    "mdm_wgrad_group_destroy": ([vp], i32),
-    "mdm_gemm_plan": ([C.POINTER(GemmDesc), C.POINTER(i32), C.POINTER(i64)], i32),
-    "mdm_gemm_can_fuse_gn_bwd": ([C.POINTER(GemmDesc), i32], i32),
-    "mdm_gemm_can_fuse_gn_fwd": ([C.POINTER(GemmDesc), i32], i32),
-    "mdm_gemm_last_route": ([], C.c_char_p),
-    "mdm_gemm_route_of": ([C.POINTER(GemmDesc)], C.c_char_p),
-    "mdm_gemm_pair_route_of": ([C.POINTER(GemmDesc), C.POINTER(GemmDesc)], C.c_char_p),
-    "mdm_gemm_route_names": ([C.POINTER(C.c_char_p), i32], i32),
-    "mdm_groupnorm_fwd": ([C.POINTER(GnDesc), vp], i32),
-    "mdm_groupnorm_bwd": ([C.POINTER(GnDesc), vp], i32),
-    "mdm_groupnorm_bwd_ws_floats": ([i32, i32, i32], i64),
-    "mdm_dropout_mask": ([vp, u64, vp, i64, vp, vp], i32),
-    "mdm_attn_supported": ([i32, i32, i32], i32),
-    "mdm_attn_fwd": ([i32, vp, vp, vp, i32, i32, i32, f32, vp], i32),
-    "mdm_attn_f32_small_supported": ([i32, i32], i32),
-    "mdm_attn_f32_small_fwd": ([vp, vp, vp, i32, i32, i32, f32, vp], i32),
-    "mdm_attn_bwd": ([i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp], i32),
-    "mdm_attn_mh_fwd": ([i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp], i32),
-    "mdm_attn_mh_bwd": ([i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp], i32),
-    "mdm_softmax_fwd": ([i32, vp, i32, i32, vp], i32),
-    "mdm_softmax_bwd": ([i32, vp, vp, i32, i32, vp], i32),
-    "mdm_timestep_embedding": ([vp, i32, i32, vp, vp], i32),
-    "mdm_timestep_embedding2": ([vp, i32, i32, i32, f32, vp, vp], i32),
-    "mdm_silu_fwd": ([vp, vp, i64, vp], i32),
-    "mdm_silu_bwd": ([vp, vp, vp, i32, i64, vp], i32),
-    "mdm_skinny_supported": ([i32, i32, i32, i32], i32),
-    "mdm_skinny_linear_fwd": ([vp, i32, vp, i32, f32, vp, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp], i32),
-    "mdm_skinny_linear_bwd": ([vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp], i32),
-    "mdm_silu_bwd_sum": ([vp, vp, i32, i64, vp, vp], i32),
-    "mdm_colsum": ([i32, vp, i32, i32, i32, vp, i32, i32, vp, vp], i32),
-    "mdm_sumpool2": ([i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),
-    "mdm_avgpool2": ([i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),
-    "mdm_upsample2": ([i32, vp, vp, i32, f32, i32, i32, i32, i32, vp], i32),
-    "mdm_add": ([i32, vp, vp, i64, vp], i32),
-    "mdm_add3": ([i32, vp, vp, vp, i64, vp], i32),
-    "mdm_nchw_to_nhwc": ([i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),
-    "mdm_nhwc_to_nchw": ([i32, vp, vp, i32, i32, i32, i32, i32, vp], i32),
-    "mdm_draw_timesteps": ([vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp], i32),
-    "mdm_degrade": ([vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp], i32),
-    "mdm_index_mask": ([vp, i32, vp, i32, i32, i32, i32, vp, vp], i32),
-    "mdm_shift": ([vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp], i32),
-    "mdm_zero_pad_channels": ([i32, vp, i64, i32, i32, vp], i32),
-    "mdm_loss_fwd_bwd": ([i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp], i32),
-    "mdm_loss_fwd_bwd_mon": ([i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp], i32),
-    "mdm_monitor_commit": ([vp, vp, vp, vp, vp, i32, vp], i32),
-    "mdm_sampler_x0": ([i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp], i32),
-    "mdm_sampler_update": ([vp, vp, vp, vp, i32, i64, vp], i32),
-    "mdm_normalize01": ([vp, vp, i32, i32, vp], i32),
-    "mdm_unit_rows": ([vp, vp, i32, i32, f32, vp], i32),
-    "mdm_col_argmax": ([vp, i32, i32, vp, vp, vp], i32),
-    "mdm_rng_advance": ([vp, vp], i32),
-    "mdm_sampler_step_params": ([vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
-    "mdm_sqnorm": ([vp, i64, vp, vp], i32),
-    "mdm_adamw_ema": ([vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp], i32),
-    "mdm_optim_update": ([i32, vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, vp], i32),
-    "mdm_cast_bf16": ([vp, vp, i64, vp], i32),
-    "mdm_transpose_shadow_bf16": ([vp, vp, vp, i32, vp], i32),
-    "mdm_split_shadow": ([vp, vp, vp, i32, vp], i32),
-    "mdm_split_shadow_t": ([vp, vp, vp, i32, vp], i32),
-    "mdm_conv_wgrad_split": ([C.POINTER(GemmDesc), vp], i32),
-    "mdm_conv_wgrad_split_plan": ([C.POINTER(GemmDesc), C.POINTER(i32), C.POINTER(i64)], i32),
-    "mdm_wgrad_split_last_route": ([], C.c_char_p),
-    "mdm_fill_f32": ([vp, f32, i64, vp], i32),
-    "mdm_fill_segments_f32": ([vp, vp, i32, f32, vp], i32),
-    "mdm_graph_begin": ([vp], i32),
-    "mdm_graph_end": ([vp, C.POINTER(vp)], i32),
-    "mdm_graph_launch": ([vp, vp], i32),
-    "mdm_graph_destroy": ([vp], i32),
-    "mdm_event_create": ([C.POINTER(vp)], i32),
-    "mdm_event_record": ([vp, vp], i32),
-    "mdm_event_elapsed_ms": ([vp, vp, C.POINTER(f32)], i32),
-    "mdm_event_destroy": ([vp], i32),
-    "mdm_stream_sync": ([vp], i32),
-}
-
-EXPORTS = ["mdm_last_error"] + list(_PROTOS)
+_DESC_PTR.update({"mdm_gemm_desc*": C.POINTER(GemmDesc), "mdm_gn_desc*": C.POINTER(GnDesc)})
+# every function the header declares: {name: (argtypes, restype)} and {name: parameter names}
+_PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _DECLS.items()}
+_PARAMS = {name: [n for n, _ in params] for name, (_, params) in _DECLS.items()}
+EXPORTS = list(_PROTOS)
 
 _lib = None
 
@@ -150,8 +115,6 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C masked-diffusion-model_amd/csrc`).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    lib.mdm_last_error.restype = C.c_char_p
-    lib.mdm_last_error.argtypes = []
     for name, (args, res) in _PROTOS.items():
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -289,9 +252,21 @@ class GraphExec:
             pass
 
 
-def call(name, *args):
-    """Call a kernel entry point (last positional argument = stream) or record it."""
+@functools.lru_cache(maxsize=None)
+def _signature(name):
+    return inspect.Signature([inspect.Parameter(p, inspect.Parameter.POSITIONAL_OR_KEYWORD) for p in _PARAMS[name]])
+
+
+def call(name, *args, **kw):
+    """Call a kernel entry point (last parameter = stream) or record it.  Keywords are the header's parameter names; they are
+    bound into the positional tuple first, so a wrong, missing or doubled name is a TypeError before anything is launched or
+    recorded.  Nothing is defaulted."""
     fn = getattr(load(), name)
+    if kw:
+        try:
+            args = _signature(name).bind(*args, **kw).args
+        except TypeError as e:
+            raise TypeError(f"{name}: {e}") from None
     if _recording is not None:
         _recording.calls.append((name, fn, args[:-1]))
         _recording.keep.append(args)

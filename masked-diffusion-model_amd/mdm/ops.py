@@ -239,13 +239,14 @@ def skinny_supported(M, N, K, splits=1):
 def skinny_linear_fwd(x, W, bias, M, N, K, y, act_out=None, t=None, variant=None, emb_out=None):
     """y = x W^T + bias (fp32, M = batch rows), act_out = silu(y); x=None: the input is the timestep embedding of t."""
     flip, shift = (0, 1.0) if variant is None else (int(bool(variant[0])), float(variant[1]))
-    call("mdm_skinny_linear_fwd", ptr(x), K, ptr(t), flip, shift, ptr(emb_out), ptr(W), K, ptr(bias), M, N, K, ptr(y), N,
-         ptr(act_out), stream())
+    call("mdm_skinny_linear_fwd", x=ptr(x), ldx=K, t=ptr(t), flip_sin_to_cos=flip, freq_shift=shift, emb_out=ptr(emb_out),
+         W=ptr(W), ldw=K, bias=ptr(bias), M=M, N=N, K=K, y=ptr(y), ldy=N, act_out=ptr(act_out), stream=stream())
 
 
 def skinny_linear_bwd(dy, W, M, N, K, dx=None, pre=None, splits=1, slabs=None):
     """dx = dy W (* silu'(pre)); splits > 1: partial sums to slabs[splits][M][N] for silu_bwd_sum."""
-    call("mdm_skinny_linear_bwd", ptr(dy), K, ptr(W), N, M, N, K, splits, ptr(pre), ptr(dx), ptr(slabs), stream())
+    call("mdm_skinny_linear_bwd", dy=ptr(dy), lddy=K, W=ptr(W), ldw=N, M=M, N=N, K=K, splits=splits, pre=ptr(pre), dx=ptr(dx),
+         slabs=ptr(slabs), stream=stream())
 
 
 def silu_bwd_sum(pre, slabs, nslab, n, dx):
@@ -333,7 +334,8 @@ def attn_f32_small_fwd(qkv, o, S, N, L, C, scale):
 
 
 def attn_bwd(dt, qkv, o, do, lse, delta, dqkv, N, L, C, scale):
-    call("mdm_attn_bwd", dt, ptr(qkv), ptr(o), ptr(do), ptr(lse), ptr(delta), ptr(dqkv), N, L, C, float(scale), stream())
+    call("mdm_attn_bwd", dtype=dt, qkv=ptr(qkv), o=ptr(o), d_o=ptr(do), lse=ptr(lse), delta=ptr(delta), dqkv=ptr(dqkv),
+         N=N, L=L, C=C, scale=float(scale), stream=stream())
 
 
 def softmax_fwd(dt, S, rows, L):
@@ -352,12 +354,13 @@ def timestep_embedding(t, N, dim, y, variant=None):
 
 
 def attn_mh_fwd(dt, q, k, v, o, lse, N, L, C, heads, scale):
-    call("mdm_attn_mh_fwd", dt, ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), N, L, C, heads, float(scale), stream())
+    call("mdm_attn_mh_fwd", dtype=dt, q=ptr(q), k=ptr(k), v=ptr(v), o=ptr(o), lse=ptr(lse), N=N, L=L, C=C, heads=heads,
+         scale=float(scale), stream=stream())
 
 
 def attn_mh_bwd(dt, q, k, v, o, do, lse, delta, dq, dk, dv, N, L, C, heads, scale):
-    call("mdm_attn_mh_bwd", dt, ptr(q), ptr(k), ptr(v), ptr(o), ptr(do), ptr(lse), ptr(delta), ptr(dq), ptr(dk), ptr(dv),
-         N, L, C, heads, float(scale), stream())
+    call("mdm_attn_mh_bwd", dtype=dt, q=ptr(q), k=ptr(k), v=ptr(v), o=ptr(o), d_o=ptr(do), lse=ptr(lse), delta=ptr(delta),
+         dq=ptr(dq), dk=ptr(dk), dv=ptr(dv), N=N, L=L, C=C, heads=heads, scale=float(scale), stream=stream())
 
 
 def silu_fwd(x, y, n):

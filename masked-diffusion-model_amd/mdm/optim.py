@@ -188,8 +188,8 @@ class AdamW(_AdamBase):
 
     def _emit_kernel(self, ema_buf, max_norm, gmul):
         st = self.store
-        call("mdm_adamw_ema", ptr(st.P), ptr(st.G), ptr(self.m), ptr(self.v), ptr(ema_buf), ptr(st.Pb), st.size,
-             ptr(self.hp), ptr(self.sqnorm), max_norm, gmul, stream())
+        call("mdm_adamw_ema", p=ptr(st.P), g=ptr(st.G), m=ptr(self.m), v=ptr(self.v), ema=ptr(ema_buf), shadow_bf16=ptr(st.Pb),
+             n=st.size, hp=ptr(self.hp), sqnorm=ptr(self.sqnorm), max_norm=max_norm, gmul=gmul, stream=stream())
 
 
 class Adam(_AdamBase):
@@ -206,8 +206,8 @@ class Adam(_AdamBase):
 
     def _emit_kernel(self, ema_buf, max_norm, gmul):
         st = self.store
-        call("mdm_optim_update", 2, ptr(st.P), ptr(st.G), ptr(self.m), ptr(self.v), ptr(ema_buf), ptr(st.Pb), st.size,
-             ptr(self.hp), ptr(self.sqnorm), max_norm, gmul, stream())
+        call("mdm_optim_update", kind=2, p=ptr(st.P), g=ptr(st.G), buf0=ptr(self.m), buf1=ptr(self.v), ema=ptr(ema_buf),
+             shadow_bf16=ptr(st.Pb), n=st.size, hp=ptr(self.hp), sqnorm=ptr(self.sqnorm), max_norm=max_norm, gmul=gmul, stream=stream())
 
 
 def _check_sgd(g):
@@ -260,8 +260,9 @@ class SGD(_FlatOptimizer):
 
     def _emit_kernel(self, ema_buf, max_norm, gmul):
         st = self.store
-        call("mdm_optim_update", 0 if self.buf is None else 1, ptr(st.P), ptr(st.G), ptr(self.buf), None, ptr(ema_buf), ptr(st.Pb), st.size,
-             ptr(self.hp), ptr(self.sqnorm), max_norm, gmul, stream())
+        call("mdm_optim_update", kind=0 if self.buf is None else 1, p=ptr(st.P), g=ptr(st.G), buf0=ptr(self.buf), buf1=None,
+             ema=ptr(ema_buf), shadow_bf16=ptr(st.Pb), n=st.size, hp=ptr(self.hp), sqnorm=ptr(self.sqnorm), max_norm=max_norm, gmul=gmul,
+             stream=stream())
 
     def _group(self, g):
         return dict(momentum=g["momentum"], dampening=g["dampening"], weight_decay=g["weight_decay"], nesterov=g["nesterov"],

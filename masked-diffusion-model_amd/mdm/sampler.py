@@ -176,22 +176,26 @@ class Sampler:
         rng = S.dev_rng.dev
 
         def degrade(amount, stream_id, mask_src, out, mask_out, mi):
+            same = dict(x0=ptr(x0_hat), u=None, amount_stride=1, rng=ptr(rng), N=n, C=c, HW=HW, fill_mode=fm, fill_const=fc,
+                        x_t=ptr(out), mean_pixel=ptr(mp), stream=stream())
             if mask_src is not None:                      # degrade_with_mask (scheduler.py:572-598)
-                call("mdm_degrade", ptr(x0_hat), None, ptr(mask_src), None, 1, ptr(rng), 0, n, c, HW, c, fm, fc, ptr(out), None, ptr(mp), stream())
+                call("mdm_degrade", **same, mask_in=ptr(mask_src), amount=None, rng_stream=0, Cm=c, mask=None)
             elif sel == "indexing":
                 call("mdm_index_mask", ptr(amount), 1, ptr(rng), stream_id, n, c, HW, ptr(mi), stream())
-                call("mdm_degrade", ptr(x0_hat), None, ptr(mi), None, 1, ptr(rng), stream_id, n, c, HW, c, fm, fc, ptr(out), ptr(mask_out), ptr(mp), stream())
+                call("mdm_degrade", **same, mask_in=ptr(mi), amount=None, rng_stream=stream_id, Cm=c, mask=ptr(mask_out))
             else:
-                call("mdm_degrade", ptr(x0_hat), None, None, ptr(amount), 1, ptr(rng), stream_id, n, c, HW, Cm, fm, fc, ptr(out), ptr(mask_out), ptr(mp), stream())
+                call("mdm_degrade", **same, mask_in=None, amount=ptr(amount), rng_stream=stream_id, Cm=Cm, mask=ptr(mask_out))
 
         def emit(update):
-            call("mdm_sampler_step_params", ptr(ts_dev), T, ptr(ctr), ptr(ratio_tab), ptr(amount_tab), n, ptr(model.t_in),
-                 ptr(ratio) if kind != 0 else None, ptr(amt_t), ptr(amt_next), ptr(rng), stream())
-            call("mdm_shift", ptr(x_t), None, ptr(ratio) if kind != 0 else None, ptr(rng), 2, kind, float(getattr(a, "noise_mean", 0.0)),
-                 per_col, n, c, hw, hw, ptr(s), ptr(x_in), model.dt, ptr(model.x_in.data), model.cin_p, stream())
+            call("mdm_sampler_step_params", timesteps=ptr(ts_dev), T=T, step_ctr=ptr(ctr), ratio_tab=ptr(ratio_tab),
+                 amount_tab=ptr(amount_tab), n=n, time_out=ptr(model.t_in), ratio_out=ptr(ratio) if kind != 0 else None,
+                 amt_t=ptr(amt_t), amt_next=ptr(amt_next), rng=ptr(rng), stream=stream())
+            call("mdm_shift", x_t=ptr(x_t), z=None, ratio=ptr(ratio) if kind != 0 else None, rng=ptr(rng), rng_stream=2, kind=kind,
+                 noise_mean=float(getattr(a, "noise_mean", 0.0)), per_column=per_col, N=n, C=c, H=hw, W=hw, s=ptr(s), x_in=ptr(x_in),
+                 dtype=model.dt, x_in_nhwc=ptr(model.x_in.data), Cp=model.cin_p, stream=stream())
             _lib._recording.extend(model.forward_plan)
-            call("mdm_sampler_x0", model.dt, ptr(model.y_out.data), model.cout_p, ptr(x_in), ptr(s), n, c, hw, hw, None, None,
-                 ptr(x0_hat), stream())
+            call("mdm_sampler_x0", dtype=model.dt, pred_nhwc=ptr(model.y_out.data), Cp=model.cout_p, x_in=ptr(x_in), s=ptr(s),
+                 N=n, C=c, H=hw, W=hw, pred_nchw=None, shifted0=None, x0_hat=ptr(x0_hat), stream=stream())
             if dep == "independent":
                 degrade(amt_t, 3, None, d_t, m_t, mi_t)
                 degrade(amt_next, 4, None, d_next, m_next, mi_next)
@@ -260,8 +264,8 @@ class Sampler:
             nhwc = (model.dt, model.x_in.data, model.cin_p) if fused else None
             s, x_in = S.shift_and_perturb(time, x_t, want_nhwc=nhwc)                 # sampler.py:142-143
             pred, cp, pdt = self._predict(model, x_in, time, fused)                  # :145
-            call("mdm_sampler_x0", pdt, ptr(pred), cp, ptr(x_in), ptr(s), n, c, hw, hw, ptr(pred_nchw), ptr(shifted0),
-                 ptr(x0_hat), stream())                                              # :146-152
+            call("mdm_sampler_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(x_in), s=ptr(s), N=n, C=c, H=hw, W=hw,
+                 pred_nchw=ptr(pred_nchw), shifted0=ptr(shifted0), x0_hat=ptr(x0_hat), stream=stream())   # :146-152
             next_t = time - 1 if i > 0 else time                                     # :167-170
             n_t = S.get_black_area_num_pixels_time(time)
             n_next = S.get_black_area_num_pixels_time(next_t)

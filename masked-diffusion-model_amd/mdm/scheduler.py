@@ -228,8 +228,9 @@ class Scheduler:
                     u_out.append(u)
         else:
             mask_in = mask_in.to(self.device, torch.float32).contiguous()
-        call("mdm_degrade", ptr(img), ptr(u), ptr(mask_in), ptr(amt), 1, ptr(self.dev_rng.dev), rng_stream, N, C, HW,
-             Cm if mask_in is None else C, fm, fc, ptr(x_t), ptr(mask), ptr(mp), stream())
+        call("mdm_degrade", x0=ptr(img), u=ptr(u), mask_in=ptr(mask_in), amount=ptr(amt), amount_stride=1, rng=ptr(self.dev_rng.dev),
+             rng_stream=rng_stream, N=N, C=C, HW=HW, Cm=Cm if mask_in is None else C, fill_mode=fm, fill_const=fc,
+             x_t=ptr(x_t), mask=ptr(mask), mean_pixel=ptr(mp), stream=stream())
         return x_t, mask, mp
 
     def degrade_training(self, black_area_num, img, mean_option=None, mean_area=None):
@@ -311,8 +312,9 @@ class Scheduler:
         s = torch.empty_like(x_t)
         x_in = torch.empty_like(x_t)
         dt, nh, Cp = want_nhwc if want_nhwc is not None else (0, None, 0)
-        call("mdm_shift", ptr(x_t), ptr(z), ptr(ratio), ptr(self.dev_rng.dev), 2, kind,
-             float(getattr(self.args, "noise_mean", 0.0)), per_col, N, C, H, W, ptr(s), ptr(x_in), dt, ptr(nh), Cp, stream())
+        call("mdm_shift", x_t=ptr(x_t), z=ptr(z), ratio=ptr(ratio), rng=ptr(self.dev_rng.dev), rng_stream=2, kind=kind,
+             noise_mean=float(getattr(self.args, "noise_mean", 0.0)), per_column=per_col, N=N, C=C, H=H, W=W, s=ptr(s), x_in=ptr(x_in),
+             dtype=dt, x_in_nhwc=ptr(nh), Cp=Cp, stream=stream())
         return s, x_in
 
     def get_schedule_shift_time(self, timesteps, binarymasks):

@@ -168,19 +168,21 @@ class TrainStep:
         N, C, H, W = m.N, m.cin, m.H, m.W
         fm, fc = _fill_mode(a.mean_option, a.mean_area)
         kind = self._kind()
-        call("mdm_degrade", ptr(self.x0), ptr(u), ptr(mask_in), ptr(self.amount), 1, ptr(S.dev_rng.dev), 1, N, C, H * W,
-             C if mask_in is not None else Cm, fm, fc, ptr(self.x_t), ptr(self.mask), ptr(self.mean_pixel), stream())
+        call("mdm_degrade", x0=ptr(self.x0), u=ptr(u), mask_in=ptr(mask_in), amount=ptr(self.amount), amount_stride=1,
+             rng=ptr(S.dev_rng.dev), rng_stream=1, N=N, C=C, HW=H * W, Cm=C if mask_in is not None else Cm, fill_mode=fm, fill_const=fc,
+             x_t=ptr(self.x_t), mask=ptr(self.mask), mean_pixel=ptr(self.mean_pixel), stream=stream())
         per_col = int(S.reference_quirks and kind in (3, 4) and N == W and N > 1)
-        call("mdm_shift", ptr(self.x_t), ptr(z), ptr(self.ratio), ptr(S.dev_rng.dev), 2, kind,
-             float(getattr(a, "noise_mean", 0.0)), per_col, N, C, H, W, ptr(self.s), ptr(self.x_in), m.dt,
-             ptr(m.x_in.data), m.cin_p, stream())
+        call("mdm_shift", x_t=ptr(self.x_t), z=ptr(z), ratio=ptr(self.ratio), rng=ptr(S.dev_rng.dev), rng_stream=2, kind=kind,
+             noise_mean=float(getattr(a, "noise_mean", 0.0)), per_column=per_col, N=N, C=C, H=H, W=W, s=ptr(self.s), x_in=ptr(self.x_in),
+             dtype=m.dt, x_in_nhwc=ptr(m.x_in.data), Cp=m.cin_p, stream=stream())
         m.forward_plan.run() if _lib._recording is None else _lib._recording.extend(m.forward_plan)
-        head = (m.dt, ptr(m.y_out.data), ptr(self.x_in), ptr(self.s) if kind != 0 else None, ptr(self.x0),
-                ptr(self.w) if weights_on else None, N, C, H, W, m.cout_p, 1.0 / self.grad_accum, ptr(m.y_out.grad), ptr(self.loss.raw))
+        head = dict(dtype=m.dt, pred=ptr(m.y_out.data), x_in=ptr(self.x_in), s=ptr(self.s) if kind != 0 else None, x0=ptr(self.x0),
+                    w=ptr(self.w) if weights_on else None, N=N, C=C, H=H, W=W, Cp=m.cout_p, gscale=1.0 / self.grad_accum,
+                    dpred=ptr(m.y_out.grad), loss_q40=ptr(self.loss.raw), stream=stream())
         if self.mon is None:
-            call("mdm_loss_fwd_bwd", *head, stream())
+            call("mdm_loss_fwd_bwd", **head)
         else:
-            call("mdm_loss_fwd_bwd_mon", *head, ptr(self.x_t), ptr(self.mon.mon_q40), stream())
+            call("mdm_loss_fwd_bwd_mon", **head, x_t=ptr(self.x_t), mon_q40=ptr(self.mon.mon_q40))
 
     def _emit_commit(self, with_norm):
         """The monitored step's last launch: one ring row.  `with_norm`: the optimizer update ran (its squared norm is current)."""
@@ -302,8 +304,9 @@ class TrainStep:
         rng = ptr(S.dev_rng.dev)
         n_used = self.used_dev.numel()
         S.dev_rng.advance()                 # first launch of the step (part of the captured graph): a fresh Philox offset
-        call("mdm_draw_timesteps", rng, ptr(self.used_dev), n_used, ptr(self.table_dev), ptr(self.wtab_dev), N,
-             ptr(m.t_in), ptr(self.amount), ptr(self.w), ptr(self.tidx), ptr(S.ratio_dev), ptr(self.ratio), ptr(self.loss.raw), stream())
+        call("mdm_draw_timesteps", rng=rng, used=ptr(self.used_dev), n_used=n_used, table=ptr(self.table_dev), wtab=ptr(self.wtab_dev),
+             N=N, t_out=ptr(m.t_in), amount_out=ptr(self.amount), weight_out=ptr(self.w), idx_out=ptr(self.tidx),
+             table2=ptr(S.ratio_dev), out2=ptr(self.ratio), zero_out=ptr(self.loss.raw), stream=stream())
         mask_in, Cm = None, 1
         if a.select_degrade_pixel == "indexing":
             call("mdm_index_mask", ptr(self.amount), 1, rng, 1, N, C, H * W, ptr(self.mask), stream())

@@ -31,29 +31,116 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_descriptor_layout_matches_the_header(tmp_path):
-    """mdm_gemm_desc at a sample of offsets; mdm_gn_desc completely: sizeof, then offset and size of EVERY field of GnDesc against
-    the header as a C compiler lays it out, and the field sizes add up to sizeof: no implicit padding, and no member that only one
-    side has."""
+    """Both descriptors completely: sizeof, then offset and size of EVERY field of GemmDesc and GnDesc against the header as a C
+    compiler lays it out.  The field list comes from the class and must equal the struct's declarators as a regex of this test
+    counts them (every identifier in front of a `,` or `;`), so a parser that drops or invents a member fails.  mdm_gn_desc has
+    no implicit padding: its field sizes add up to sizeof.  (mdm_gemm_desc has 8 bytes of it by design.)"""
     from mdm._lib import GemmDesc, GnDesc
-    gn = [name for name, _ in GnDesc._fields_]
+    hdr = os.path.join(ROOT, "include", "mdm_hip.h")
+    text = re.sub(r"/\*.*?\*/", " ", open(hdr).read(), flags=re.S)
+    structs = {"mdm_gemm_desc": GemmDesc, "mdm_gn_desc": GnDesc}
+    prints = []
+    for cname, cls in structs.items():
+        fields = [name for name, _ in cls._fields_]
+        body = re.search(r"typedef\s+struct\s+%s\s*\{(.*?)\}\s*%s\s*;" % (cname, cname), text, flags=re.S).group(1)
+        assert fields == re.findall(r"(\w+)\s*[,;]", body), cname
+        prints.append('printf("%%zu\\n",sizeof(%s));\n' % cname)
+        prints += ['printf("%s %%zu %%zu\\n",offsetof(%s,%s),sizeof(((%s*)0)->%s));\n' % (f, cname, f, cname, f) for f in fields]
+    assert (len(GemmDesc._fields_), len(GnDesc._fields_)) == (78, 30)
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu\\n",'
-                   'sizeof(mdm_gemm_desc),offsetof(mdm_gemm_desc,A),offsetof(mdm_gemm_desc,conv),offsetof(mdm_gemm_desc,src0),'
-                   'offsetof(mdm_gemm_desc,D0),offsetof(mdm_gemm_desc,bias),offsetof(mdm_gemm_desc,dtap));\n'
-                   'printf("%%zu\\n",sizeof(mdm_gn_desc));\n%sreturn 0;}\n'
-                   % (os.path.join(ROOT, "include", "mdm_hip.h"),
-                      "".join('printf("%s %%zu %%zu\\n",offsetof(mdm_gn_desc,%s),sizeof(((mdm_gn_desc*)0)->%s));\n' % (f, f, f) for f in gn)))
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){%sreturn 0;}\n' % (hdr, "".join(prints)))
     exe = tmp_path / "sz"
     subprocess.run(["gcc", str(src), "-o", str(exe)], check=True)
-    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
-    got = [int(v) for v in lines[0].split()]
-    want = [ctypes.sizeof(GemmDesc), GemmDesc.A.offset, GemmDesc.conv.offset, GemmDesc.src0.offset, GemmDesc.D0.offset,
-            GemmDesc.bias.offset, GemmDesc.dtap.offset]
-    assert got == want
-    assert int(lines[1]) == ctypes.sizeof(GnDesc)
-    c_fields = [(ln.split()[0], int(ln.split()[1]), int(ln.split()[2])) for ln in lines[2:]]
-    assert c_fields == [(f, getattr(GnDesc, f).offset, getattr(GnDesc, f).size) for f in gn]
-    assert sum(size for _, _, size in c_fields) == int(lines[1]) == sum(getattr(GnDesc, f).size for f in gn)
+    lines = iter(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
+    for cname, cls in structs.items():
+        size = int(next(lines))
+        assert size == ctypes.sizeof(cls), cname
+        c_fields = [(ln.split()[0], int(ln.split()[1]), int(ln.split()[2])) for ln in (next(lines) for _ in cls._fields_)]
+        assert c_fields == [(f, getattr(cls, f).offset, getattr(cls, f).size) for f, _ in cls._fields_], cname
+        if cls is GnDesc:
+            assert sum(sz for _, _, sz in c_fields) == size == sum(getattr(cls, f).size for f, _ in cls._fields_)
+    assert ctypes.sizeof(GemmDesc) == 448 and next(lines, None) is None
+
+
+PARSER_REFUSALS = [      # header text, what the message must name
+    ("int mdm_x(int n, unsigned flags, void* stream);", ("unknown type", "unsigned", "mdm_x")),
+    ("typedef struct mdm_s { int32_t a; double b; } mdm_s;", ("unknown type", "double", "mdm_s")),
+    ("int mdm_x(int n, const float*, void* stream);", ("no name", "const float*", "mdm_x")),
+    ("int mdm_x(int, void* stream);", ("no name", "mdm_x")),
+    ("int mdm_x(unsigned int n, void* stream);", ("cannot split", "unsigned int n", "mdm_x")),
+    ("typedef struct mdm_s { float* a, b; } mdm_s;", ("one pointer per declaration", "mdm_s")),
+    ("int mdm_x(int n, void* stream);\nstruct mdm_t;\n", ("cannot parse", "struct mdm_t")),
+]
+
+
+@pytest.mark.parametrize("text,named", PARSER_REFUSALS, ids=[" ".join(n[:2]) for _, n in PARSER_REFUSALS])
+def test_header_parser_refuses_what_it_does_not_know(text, named):
+    """The parser is closed: an unknown type, a declaration without a name or one it cannot split, and a construct that is neither
+    a struct nor a prototype raise and name the declaration; nothing is skipped."""
+    from mdm import _lib
+    with pytest.raises(ValueError) as e:
+        _lib.parse_header(text)
+    for word in named:
+        assert word in str(e.value), (word, str(e.value))
+
+
+def test_header_parser_reads_a_prototype_over_three_lines():
+    from mdm import _lib
+    structs, protos = _lib.parse_header(
+        "#define X 1\ntypedef struct mdm_s { const void* p; int32_t a, b; /* two */ float c; } mdm_s;\n"
+        "int64_t mdm_x(const mdm_s* d_host, int n,   /* rows; cols, (both) */\n"
+        "              const uint64_t* rng,\n"
+        "              float scale, void* stream);\nconst char* mdm_y(void);\n")
+    assert structs == {"mdm_s": [("p", "void*"), ("a", "int32_t"), ("b", "int32_t"), ("c", "float")]}
+    assert protos == {"mdm_x": ("int64_t", [("d_host", "mdm_s*"), ("n", "int"), ("rng", "uint64_t*"), ("scale", "float"), ("stream", "void*")]),
+                      "mdm_y": ("char*", [])}
+
+
+def test_a_missing_header_is_a_loud_error(tmp_path):
+    """The binding is built from the header at import: without it there is a RuntimeError that says so, not a partial module."""
+    pkg = tmp_path / "masked-diffusion-model_amd" / "mdm"
+    pkg.mkdir(parents=True)
+    import mdm._lib as real
+    (pkg / "_lib.py").write_text(open(real.__file__).read())
+    (pkg / "__init__.py").write_text("")
+    r = subprocess.run([sys.executable, "-c", "import mdm._lib"], cwd=str(pkg.parent), capture_output=True, text=True)
+    assert r.returncode != 0 and "RuntimeError" in r.stderr and "mdm_hip.h is missing" in r.stderr, r.stderr
+
+
+def test_the_parsed_tables_are_the_types_the_wrappers_rely_on():
+    """Spot values written down here, not derived: scalar widths, descriptor pointers typed, every other pointer void*."""
+    from mdm import _lib
+    C = ctypes
+    assert _lib._PROTOS["mdm_add"] == ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p], C.c_int32)
+    assert _lib._PROTOS["mdm_gemm_pair"] == ([C.POINTER(_lib.GemmDesc)] * 2 + [C.c_void_p], C.c_int32)
+    assert _lib._PROTOS["mdm_groupnorm_bwd"] == ([C.POINTER(_lib.GnDesc), C.c_void_p], C.c_int32)
+    assert _lib._PROTOS["mdm_groupnorm_bwd_ws_floats"] == ([C.c_int32] * 3, C.c_int64)
+    assert _lib._PROTOS["mdm_dropout_mask"][0][1] is C.c_uint64 and _lib._PROTOS["mdm_fill_f32"][0][1] is C.c_float
+    assert _lib._PROTOS["mdm_last_error"] == ([], C.c_char_p) == _lib._PROTOS["mdm_gemm_last_route"]
+    assert dict(_lib.GnDesc._fields_)["drop_base"] is C.c_uint64 and dict(_lib.GemmDesc._fields_)["wtap"] is C.c_int64
+    assert _lib._PARAMS["mdm_add"] == ["dtype", "dst", "src", "n", "stream"]
+    assert len(_lib._PROTOS) == 81 and len(_lib.EXPORTS) == 81
+
+
+def test_call_binds_keywords_against_the_header_names():
+    """Under a Recording (nothing launches): keyword, mixed and positional calls record the same tuple; a misspelt, missing or
+    doubled parameter is a TypeError naming the entry point and records nothing."""
+    from mdm import _lib
+    lib = _lib.load()
+    with _lib.Recording() as rec:
+        _lib.call("mdm_add", 0, 16, 32, 8, None)
+        _lib.call("mdm_add", dtype=0, dst=16, src=32, n=8, stream=None)
+        _lib.call("mdm_add", 0, 16, n=8, stream=None, src=32)
+        assert rec.calls == [("mdm_add", lib.mdm_add, (0, 16, 32, 8))] * 3
+        for bad in (dict(dtype=0, dest=16, src=32, n=8, stream=None),          # misspelt
+                    dict(dtype=0, dst=16, src=32, stream=None)):               # missing
+            with pytest.raises(TypeError, match="mdm_add"):
+                _lib.call("mdm_add", **bad)
+        with pytest.raises(TypeError, match="mdm_add"):                        # doubled
+            _lib.call("mdm_add", 0, 16, 32, dst=16, n=8, stream=None)
+        with pytest.raises(TypeError, match="mdm_add"):                        # one too many
+            _lib.call("mdm_add", 0, 16, 32, 8, None, stream=None)
+        assert len(rec.calls) == 3 and len(rec.keep) == 3
 
 
 def _gn_desc(**kw):
