@@ -276,6 +276,16 @@ int mdm_dropout_mask(const uint64_t* rng, uint64_t base, const uint32_t* ctl, in
  * Replaces both einsums, the softmax and `.contiguous()` of unet6.py:319-324 and their autograd backward.
  * ------------------------------------------------------------------------- */
 int mdm_attn_supported(int dtype, int L, int C);
+/* Which of the fused kernels runs (tests): the kernel choice is one pure host function of (direction, dtype, L, C), and these
+ * three ask it without any device work.
+ *   mdm_attn_route_of     which = 0 forward, 1 backward -> "fwd<128>", "fwd_dma<256>", "bwd<32>", "bwd_dma<64>", ...;
+ *                         NULL for a request mdm_attn_fwd / mdm_attn_bwd would refuse (the backward needs L <= 4096)
+ *   mdm_attn_last_route   what the last mdm_attn_fwd / mdm_attn_bwd call of this thread launched; "none" before the first call
+ *                         and after a refused one
+ *   mdm_attn_route_names  every name the two can return: fills up to `cap` of them into out (may be NULL), returns how many */
+const char* mdm_attn_route_of(int which, int dtype, int L, int C);
+const char* mdm_attn_last_route(void);
+int mdm_attn_route_names(const char** out, int cap);
 /* Exact-fp32 forward of the same attention for short sequences (L in {16, 32, 48, 64}, C in {64, 128, 256}: the 8x8 / 4x4 attention
  * blocks on the fp32 path): one launch on v_mfma_f32_16x16x4_f32 instead of two batched contractions and a softmax launch.  It also
  * writes the probabilities S[N][L][L] (fp32) -- what the unfused fp32 backward (softmax_bwd + three contractions) reads. */

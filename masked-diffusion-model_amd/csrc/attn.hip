@@ -729,62 +729,92 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t* __restrict_
     else attn_bwd_dkv_body<D>(lds, qkv, o, d_o, lse, dqkv, L, scale);
 }
 
+// ---- the routes (mdm_attn_route_of / mdm_attn_last_route): which of the fused kernels a forward or backward request runs.
+// attn_route is the only statement of the rule -- pure host code; mdm_attn_supported, the launcher and the route queries all ask it.
+enum AttnKernel { AK_FWD = 0, AK_FWD_DMA, AK_BWD, AK_BWD_DMA, AK_COUNT };
+constexpr int ATTN_BWD_MAX_L = 4096;          // the dK/dV workgroup keeps delta (DMA: and lse) of the image's L queries in LDS
+constexpr int ATTN_UNSUPPORTED = -1, ATTN_BWD_TOO_LONG = -2;
+static const char* const kAttnRouteNames[AK_COUNT][4] = {       // [kernel][head width 32, 64, 128, 256]; no LDS-DMA kernel at width 32
+    {"fwd<32>", "fwd<64>", "fwd<128>", "fwd<256>"},
+    {nullptr, "fwd_dma<64>", "fwd_dma<128>", "fwd_dma<256>"},
+    {"bwd<32>", "bwd<64>", "bwd<128>", "bwd<256>"},
+    {nullptr, "bwd_dma<64>", "bwd_dma<128>", "bwd_dma<256>"},
+};
+// which: 0 forward, 1 backward -> kernel * 4 + width index, or one of the two negative codes
+static int attn_route(int which, int dtype, int L, int C) {
+    if ((which != 0 && which != 1) || dtype != MDM_BF16 || L <= 0 || L % 16 != 0) return ATTN_UNSUPPORTED;
+    const int wi = C == 32 ? 0 : C == 64 ? 1 : C == 128 ? 2 : C == 256 ? 3 : -1;
+    if (wi < 0) return ATTN_UNSUPPORTED;
+    if (which == 1 && L > ATTN_BWD_MAX_L) return ATTN_BWD_TOO_LONG;
+    const bool dma = C >= 64 && L % 64 == 0 && L >= 256;       // several full key tiles: K / V (Q / dO) prefetched by LDS-DMA
+    return ((which ? AK_BWD : AK_FWD) + (dma ? 1 : 0)) * 4 + wi;
+}
+static inline const char* attn_route_name(int r) { return r >= 0 ? kAttnRouteNames[r >> 2][r & 3] : nullptr; }
+static thread_local int g_attn_route = -1;
+
 template <int D>
-static int attn_launch(int which, const bf16_t* qkv, bf16_t* o, const bf16_t* d_o, float* lse, float* delta, bf16_t* dqkv,
+static int attn_launch(int kernel, const bf16_t* qkv, bf16_t* o, const bf16_t* d_o, float* lse, float* delta, bf16_t* dqkv,
                        int N, int L, float scale, hipStream_t s) {
     constexpr int bytes = 2 * 64 * 2 * D;
     static bool configured = false;
     if (!configured) {
         MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes + 4 * 4096));
+        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          bytes + 4 * ATTN_BWD_MAX_L));
         configured = true;
     }
     dim3 grid((unsigned)cdiv(L, 64), (unsigned)N);
-    if (which == 0) {
-        if constexpr (D >= 64) {
-            if (L % 64 == 0 && L >= 256) {         // several key tiles: K / V prefetched by LDS-DMA
-                constexpr int dma_bytes = (D <= 128 ? 3 : 2) * 2 * 64 * 2 * D;
-                static bool dma_configured = false;
-                if (!dma_configured) {
-                    MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_dma_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_bytes));
-                    dma_configured = true;
-                }
-                hipLaunchKernelGGL((attn_fwd_dma_kernel<D>), grid, dim3(256), dma_bytes, s, qkv, o, lse, L, scale);
-                return launch_status("attention");
+    if constexpr (D >= 64) {
+        constexpr int dma_bytes = (D <= 128 ? 3 : 2) * 2 * 64 * 2 * D;
+        if (kernel == AK_FWD_DMA) {
+            static bool dma_configured = false;
+            if (!dma_configured) {
+                MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_dma_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, dma_bytes));
+                dma_configured = true;
             }
+            hipLaunchKernelGGL((attn_fwd_dma_kernel<D>), grid, dim3(256), dma_bytes, s, qkv, o, lse, L, scale);
+            return launch_status("attention");
         }
+        if (kernel == AK_BWD_DMA) {
+            static bool dma_configured = false;
+            if (!dma_configured) {
+                MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dma_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  dma_bytes + 8 * ATTN_BWD_MAX_L));
+                dma_configured = true;
+            }
+            hipLaunchKernelGGL((attn_bwd_dma_kernel<D>), dim3(grid.x, grid.y, 2), dim3(256), dma_bytes + 8 * L, s, qkv, (const bf16_t*)o, d_o,
+                               (const float*)lse, delta, dqkv, L, scale);
+            return launch_status("attention");
+        }
+    }
+    if (kernel == AK_FWD) {
         hipLaunchKernelGGL((attn_fwd_kernel<D>), grid, dim3(256), bytes, s, qkv, o, lse, L, scale);
-    } else {
-        MDM_REQUIRE(L <= 4096, "attention backward: L=%d > 4096", L);
-        if constexpr (D >= 64) {
-            if (L % 64 == 0 && L >= 256) {
-                constexpr int dma_bytes = (D <= 128 ? 3 : 2) * 2 * 64 * 2 * D;
-                static bool dma_configured = false;
-                if (!dma_configured) {
-                    MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dma_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                      dma_bytes + 8 * 4096));
-                    dma_configured = true;
-                }
-                hipLaunchKernelGGL((attn_bwd_dma_kernel<D>), dim3(grid.x, grid.y, 2), dim3(256), dma_bytes + 8 * L, s, qkv, (const bf16_t*)o, d_o,
-                                   (const float*)lse, delta, dqkv, L, scale);
-                return launch_status("attention");
-            }
-        }
+    } else if (kernel == AK_BWD) {
         hipLaunchKernelGGL((attn_bwd_kernel<D>), dim3(grid.x, grid.y, 2), dim3(256), bytes + 4 * L, s, qkv, (const bf16_t*)o, d_o,
                            (const float*)lse, delta, dqkv, L, scale);
+    } else {
+        set_error("attention: no kernel %d at head width %d", kernel, D);
+        return -1;
     }
     return launch_status("attention");
 }
+// launches what attn_route names; a refused request launches nothing and leaves no route
 static int attn_dispatch(int which, int C, const bf16_t* qkv, bf16_t* o, const bf16_t* d_o, float* lse, float* delta, bf16_t* dqkv,
                          int N, int L, float scale, hipStream_t s) {
+    g_attn_route = -1;
+    const int r = attn_route(which, MDM_BF16, L, C);
+    MDM_REQUIRE(r != ATTN_BWD_TOO_LONG, "attention backward: L=%d > %d", L, ATTN_BWD_MAX_L);
+    MDM_REQUIRE(r >= 0, "attention: unsupported L %d / C %d (L %% 16 == 0, head width C one of 32, 64, 128, 256)", L, C);
+    const int kernel = r >> 2;
+    int rc = -1;
     switch (C) {
-        case 32: return attn_launch<32>(which, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s);
-        case 64: return attn_launch<64>(which, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s);
-        case 128: return attn_launch<128>(which, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s);
-        case 256: return attn_launch<256>(which, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s);
+        case 32: rc = attn_launch<32>(kernel, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s); break;
+        case 64: rc = attn_launch<64>(kernel, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s); break;
+        case 128: rc = attn_launch<128>(kernel, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s); break;
+        case 256: rc = attn_launch<256>(kernel, qkv, o, d_o, lse, delta, dqkv, N, L, scale, s); break;
     }
-    set_error("attention: head width C=%d is not one of 32, 64, 128, 256", C);
-    return -1;
+    if (rc == 0) g_attn_route = r;
+    return rc;
 }
 
 
@@ -1040,16 +1070,27 @@ extern "C" int mdm_attn_f32_small_fwd(const float* qkv, float* o, float* S, int 
     return launch_status("attn_f32_small_fwd");
 }
 
-extern "C" int mdm_attn_supported(int dtype, int L, int C) {
-    return dtype == MDM_BF16 && L > 0 && L % 16 == 0 && (C == 32 || C == 64 || C == 128 || C == 256) ? 1 : 0;
+extern "C" int mdm_attn_supported(int dtype, int L, int C) { return attn_route(0, dtype, L, C) >= 0 ? 1 : 0; }
+extern "C" const char* mdm_attn_route_of(int which, int dtype, int L, int C) { return attn_route_name(attn_route(which, dtype, L, C)); }
+extern "C" const char* mdm_attn_last_route(void) { return g_attn_route >= 0 ? attn_route_name(g_attn_route) : "none"; }
+extern "C" int mdm_attn_route_names(const char** out, int cap) {
+    int n = 0;
+    for (int r = 0; r < AK_COUNT * 4; ++r) {
+        if (!attn_route_name(r)) continue;
+        if (out && n < cap) out[n] = attn_route_name(r);
+        ++n;
+    }
+    return n;
 }
 extern "C" int mdm_attn_fwd(int dtype, const void* qkv, void* o, float* lse, int N, int L, int C, float scale, void* stream) {
+    g_attn_route = -1;
     MDM_REQUIRE(mdm_attn_supported(dtype, L, C), "attn_fwd: unsupported dtype %d / L %d / C %d (use the contraction path)", dtype, L, C);
     MDM_REQUIRE(qkv && o && lse && N > 0, "attn_fwd: bad arguments");
     return attn_dispatch(0, C, (const bf16_t*)qkv, (bf16_t*)o, nullptr, lse, nullptr, nullptr, N, L, scale, pick_stream(stream));
 }
 extern "C" int mdm_attn_bwd(int dtype, const void* qkv, const void* o, const void* d_o, const float* lse, float* delta, void* dqkv,
                             int N, int L, int C, float scale, void* stream) {
+    g_attn_route = -1;
     MDM_REQUIRE(mdm_attn_supported(dtype, L, C), "attn_bwd: unsupported dtype %d / L %d / C %d (use the contraction path)", dtype, L, C);
     MDM_REQUIRE(qkv && o && d_o && lse && delta && dqkv && N > 0, "attn_bwd: bad arguments");
     return attn_dispatch(1, C, (const bf16_t*)qkv, (bf16_t*)const_cast<void*>(o), (const bf16_t*)d_o, const_cast<float*>(lse), delta,

@@ -409,6 +409,27 @@ def route_names():
     return [v.decode() for v in arr]
 
 
+def attn_route_of(which, dt, L, C):
+    """The fused attention kernel mdm_attn_fwd (which = 0) / mdm_attn_bwd (1) would launch, e.g. "fwd_dma<256>", without
+    launching (mdm_attn_route_of); None for a request they refuse."""
+    r = load().mdm_attn_route_of(which, dt, L, C)
+    return None if r is None else r.decode()
+
+
+def attn_last_route():
+    """Kernel of the last mdm_attn_fwd / mdm_attn_bwd call on this thread (mdm_attn_last_route); "none" after a refused one."""
+    return load().mdm_attn_last_route().decode()
+
+
+def attn_route_names():
+    """Every name attn_route_of() / attn_last_route() can return."""
+    lib = load()
+    n = lib.mdm_attn_route_names(None, 0)
+    arr = (C.c_char_p * n)()
+    lib.mdm_attn_route_names(arr, n)
+    return [v.decode() for v in arr]
+
+
 def wgrad_group_accepts(**kw):
     kw.pop("_flops", None)
     return bool(load().mdm_wgrad_group_accepts(C.byref(_desc(kw))))
