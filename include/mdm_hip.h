@@ -257,6 +257,18 @@ typedef struct mdm_gn_desc {
 int mdm_groupnorm_fwd(const mdm_gn_desc* desc_host, void* stream);
 /* reads src0, src1, gamma, beta, stats, dy and the add tensors; writes dst0, dst1, sum_img and adds to dgamma, dbeta, sum_all */
 int mdm_groupnorm_bwd(const mdm_gn_desc* desc_host, void* stream);
+/* Which kernel runs (tests): the choice is one pure host function of (direction, dtype, N, P, G, C0 + C1), and these three ask it
+ * without any device work.  Storage type and dropout are not part of a name.
+ *   mdm_gn_route_of     which = 0 forward, 1 backward -> "fwd_reg<4,512>" (register-cached, <vectors per lane, threads>), "fwd",
+ *                       "bwd_reg<2,256>", "bwd", "bwd+reduce" (the fp32 backward: two launches), ...; NULL, with the message in
+ *                       mdm_last_error, for a shape or dtype the entry points refuse.  What they require of the pointers (ws, ctl,
+ *                       one source under rng or the column sums) is not asked here.
+ *   mdm_gn_last_route   what the last mdm_groupnorm_fwd / mdm_groupnorm_bwd call of this thread launched; "none" before the first
+ *                       call and after a refused one
+ *   mdm_gn_route_names  every name the two can return: fills up to `cap` of them into out (may be NULL), returns how many */
+const char* mdm_gn_route_of(int which, const mdm_gn_desc* desc_host);
+const char* mdm_gn_last_route(void);
+int mdm_gn_route_names(const char** out, int cap);
 
 /* floats mdm_groupnorm_bwd writes into `ws` for an [N][P][C] problem of this dtype (0: `ws` may be NULL): the entry point cannot check
  * a size it is not given. */

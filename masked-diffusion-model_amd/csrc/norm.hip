@@ -9,6 +9,8 @@
 // broadcast backward sums (unet6.py:233, 359).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace mdm {
@@ -188,10 +190,12 @@ __device__ __forceinline__ unsigned long long nstamp_now() {
 #define MDM_T(...)
 #endif
 
-// MODE 0: the whole GroupNorm in one workgroup per (image, channel block).  Large maps leave too few such
-// workgroups to pull HBM bandwidth (128 for a 32x32x128 map: 14/24 us fwd/bwd against ~6/9 us of traffic),
-// so there the pixels are cut into gridDim.z chunks: MODE 1 = statistics of one chunk -> partials in ws
-// [image][chunk][group][2] (plain stores, nothing to zero, fixed summation order), MODE 2 = apply.
+// MODE 0, the only one instantiated: the whole GroupNorm in one workgroup per (image, channel block).  Large maps leave few such
+// workgroups to pull HBM bandwidth (128 for a 32x32x128 map: 14/24 us fwd/bwd against ~6/9 us of traffic).  MODE 1 / 2 cut the
+// pixels into gridDim.z chunks (statistics of one chunk -> partials in ws, then an apply launch); the pair was measured no faster
+// than the single launch at cfg2 (13.4 vs 13.7 us forward, 25.3 vs 24.1 us backward on 32x32x128) and nothing launches it.  Its
+// text stays in the kernels: without it the same arithmetic compiles to a schedule that measured slower on the step
+// (profiles/r13_gn_routes.md: gn_fwd_reg_kernel<1,256> 5.2 -> 5.7 us, gn_bwd_reg_kernel<8,512> 40.8 -> 42.9 us).
 // NT = threads per workgroup: 512 on the larger slices (the kernels are VALU- and latency-bound at one wave per SIMD:
 // twice the waves per workgroup halve each thread's serial share of exp / rcp work)
 // (T = float, round 3: the fp32 forward -- the reverse sampler -- ran on the streaming kernel, two reads and a write per element;
@@ -533,7 +537,7 @@ static int gn_check(int C0, int C1, int G, int N, int P) {
 }
 
 // channels per workgroup: whole groups, whole 16-byte vectors, at least 32 channels
-static int gn_cblk(int C, int G, int N, int P) {
+static int gn_cblk(int C, int G, int P) {
     int cpg = C / G, l = cpg;
     while (l % 8) l += cpg;            // lcm(cpg, 8)
     // 32 channels per workgroup; 16 on large maps (more workgroups pulling HBM: 12.3 -> 10.1 us forward,
@@ -544,79 +548,141 @@ static int gn_cblk(int C, int G, int N, int P) {
     while (cb < want) cb += l;
     return cb > C ? C : cb;
 }
-// (A pixel-chunked statistics + apply pair of launches -- MODE 1 / 2 of the register kernels -- was measured no faster
-// than the single launch at cfg2: 13.4 vs 13.7 us forward, 25.3 vs 24.1 us backward on 32x32x128; it is not dispatched.)
-// DROP: the dropout variants of the same kernels (desc.rng != NULL); one route choice for both, so a dropout site runs
-// on the kernel its plain GroupNorm runs on
-template <bool DROP>
-static int gn_fwd_dispatch(const mdm_gn_desc& d, void* stream) {
-    const int dtype = d.dtype, C0 = d.C0, C1 = d.C1, N = d.N, P = d.P, G = d.G, silu = d.silu;
-    const void *src0 = d.src0, *src1 = d.src1;
-    const float eps = d.eps, *gamma = d.gamma, *beta = d.beta;
-    void* y = d.y;
-    float *stats = d.stats, *ws = d.ws;
-    if (int rc = gn_check(C0, C1, G, N, P)) return rc;
-    const int C = C0 + C1;
-    int cblk = gn_cblk(C, G, N, P);
+
+// ---- the routes (mdm_gn_route_of / mdm_gn_last_route): which GroupNorm kernel a descriptor runs on.  gn_route is the only
+// statement of the rule -- pure host code, no HIP call; mdm_groupnorm_fwd, mdm_groupnorm_bwd and the route queries all ask it.
+// Storage type and dropout are not part of a route (the launchers below resolve them), so a dropout site runs on the kernel its
+// plain GroupNorm runs on and the fp32 forward on the register kernels of the bf16 one.
+enum { GN_FWD_REG = 0, GN_FWD = 5, GN_BWD_REG = 6, GN_BWD = 11, GN_BWD_REDUCE = 12, GN_ROUTES = 13 };      // *_REG: + rung of the ladder
+struct GnPlan { int route, cblk, grid_x, grid_y; };
+// which: 0 forward, 1 backward -> 0 and *out, or -1 and the message
+static int gn_route(int which, const mdm_gn_desc& d, GnPlan* out) {
+    MDM_REQUIRE(which == 0 || which == 1, "groupnorm: bad direction %d", which);
+    if (int rc = gn_check(d.C0, d.C1, d.G, d.N, d.P)) return rc;
+    const int C = d.C0 + d.C1, P = d.P;
+    int cblk = gn_cblk(C, d.G, P);
     // fp32 forward on large maps: 32 channels per workgroup = whole 128-byte lines per pixel (16 fp32 channels are 64-byte pieces:
     // 3.0 TB/s on the sampler's 32x32x128 maps), as long as the slice still fits the register-cached kernels
-    if (dtype == MDM_F32 && P > 256) {
-        const int wide = gn_cblk(C, G, N, 256);
+    if (which == 0 && d.dtype == MDM_F32 && P > 256) {
+        const int wide = gn_cblk(C, d.G, 256);
         if (cdiv(P, 256 / (wide / 8)) <= 16) cblk = wide;
     }
-    MDM_REQUIRE(cblk <= 64 && cblk / (C / G) <= 64, "groupnorm: unsupported channel/group combination C=%d G=%d", C, G);
-    dim3 grid(N, cdiv(C, cblk));
+    MDM_REQUIRE(cblk <= 64 && cblk / (C / d.G) <= 64, "groupnorm: unsupported channel/group combination C=%d G=%d", C, d.G);
+    MDM_REQUIRE(d.dtype == MDM_F32 || d.dtype == MDM_BF16, "bad dtype %d", d.dtype);
     const int np = cdiv(P, 256 / (cblk / 8));          // 16-byte vectors per lane of a 256-thread workgroup
-    if (dtype == MDM_BF16 && np <= 16) {
-#define GN_FWD_REG(NPV, NT)                                                                                                                          \
-    do {                                                                                                                                             \
-        if constexpr (DROP)                                                                                                                          \
-            hipLaunchKernelGGL((gn_fwd_reg_kernel_drop<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0,                \
-                               (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws, d.rng, d.drop_base, d.ctl);       \
-        else                                                                                                                                         \
-            hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, (const bf16_t*)src0, C0,                     \
-                               (const bf16_t*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (bf16_t*)y, stats, ws);                                  \
-    } while (0)
-        if (np <= 1) GN_FWD_REG(1, 256); else if (np <= 2) GN_FWD_REG(2, 256); else if (np <= 4) GN_FWD_REG(2, 512);
-        else if (np <= 8) GN_FWD_REG(4, 512); else GN_FWD_REG(8, 512);
-#undef GN_FWD_REG
-        return launch_status("groupnorm_fwd");
-    }
-    if (dtype == MDM_F32 && np <= 16) {            // the same kernels on fp32 storage: one read of the slice instead of two
-#define GN_FWD_REG(NPV, NT)                                                                                                                          \
-    do {                                                                                                                                             \
-        if constexpr (DROP)                                                                                                                          \
-            hipLaunchKernelGGL((gn_fwd_reg_kernel_drop<NPV, 0, NT, float>), grid, dim3(NT), 0, (hipStream_t)stream, (const float*)src0, C0,          \
-                               (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws, d.rng, d.drop_base, d.ctl);         \
-        else                                                                                                                                         \
-            hipLaunchKernelGGL((gn_fwd_reg_kernel<NPV, 0, NT, float>), grid, dim3(NT), 0, (hipStream_t)stream, (const float*)src0, C0,               \
-                               (const float*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (float*)y, stats, ws);                                    \
-    } while (0)
-        if (np <= 1) GN_FWD_REG(1, 256); else if (np <= 2) GN_FWD_REG(2, 256); else if (np <= 4) GN_FWD_REG(2, 512);
-        else if (np <= 8) GN_FWD_REG(4, 512); else GN_FWD_REG(8, 512);
-#undef GN_FWD_REG
-        return launch_status("groupnorm_fwd");
-    }
-    if constexpr (DROP)
-        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_fwd_kernel_drop<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
-                                             (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats, d.rng, d.drop_base, d.ctl));
-    else
-        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_fwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
-                                             (const T*)src1, C1, P, G, cblk, eps, gamma, beta, silu, (T*)y, stats));
-    return launch_status("groupnorm_fwd");
-}
-static int drop_check(const char* what, const mdm_gn_desc& d) {
-    MDM_REQUIRE(d.C1 == 0, "%s: a dropout site has one source (C1=%d)", what, d.C1);
-    MDM_REQUIRE(d.rng && d.ctl, "%s: null rng / ctl", what);
-    MDM_REQUIRE(d.drop_base % 8 == 0, "%s: base must be a multiple of 8", what);
+    // the register-cached kernels hold up to 16 of them (8 per lane of a 512-thread workgroup): <NP, NT> = <1,256>, <2,256>,
+    // <2,512>, <4,512>, <8,512> for np <= 1, 2, 4, 8, 16; the backward has them for bf16 only
+    int rung = 0;
+    while (np > (1 << rung)) ++rung;
+    if (rung <= 4 && (which == 0 || d.dtype == MDM_BF16)) out->route = (which ? GN_BWD_REG : GN_FWD_REG) + rung;
+    // fp32 backward: fixed summation order across the images too (per-image partials in ws + a second stage); bf16 large maps: atomics
+    else out->route = which == 0 ? GN_FWD : d.dtype == MDM_F32 ? GN_BWD_REDUCE : GN_BWD;
+    out->cblk = cblk; out->grid_x = d.N; out->grid_y = cdiv(C, cblk);
     return 0;
 }
-extern "C" int mdm_groupnorm_fwd(const mdm_gn_desc* desc_host, void* stream) {
-    MDM_REQUIRE(desc_host != nullptr, "groupnorm_fwd: null descriptor");
-    if (!desc_host->rng) return gn_fwd_dispatch<false>(*desc_host, stream);
-    if (int rc = drop_check("groupnorm_fwd_dropout", *desc_host)) return rc;
-    return gn_fwd_dispatch<true>(*desc_host, stream);
+
+// ---- the launchers: one per kernel shape, each kernel's argument list written once
+// f(T(), bool_constant<DROP>()) for the descriptor's storage type and dropout (desc.rng != NULL: the gn_*_kernel_drop variants)
+template <typename F>
+static void gn_resolve(const mdm_gn_desc& d, F f) {
+    if (d.dtype == MDM_F32) d.rng ? f(float(), std::true_type()) : f(float(), std::false_type());
+    else d.rng ? f(bf16_t(), std::true_type()) : f(bf16_t(), std::false_type());
 }
+// the kernel on the route's grid with the arguments a...; its dropout variant takes the descriptor's rng, drop_base, ctl behind them
+template <bool DROP, typename KP, typename KD, typename... A>
+static void gn_launch(KP* plain, KD* drop, int nt, const mdm_gn_desc& d, const GnPlan& r, hipStream_t s, A... a) {
+    const dim3 grid(r.grid_x, r.grid_y);
+    if constexpr (DROP) hipLaunchKernelGGL(drop, grid, dim3(nt), 0, s, a..., d.rng, d.drop_base, d.ctl);
+    else hipLaunchKernelGGL(plain, grid, dim3(nt), 0, s, a...);
+}
+template <typename T, bool DROP, typename KP, typename KD, typename... Ws>
+static void gn_fwd_args(KP* plain, KD* drop, int nt, const mdm_gn_desc& d, const GnPlan& r, hipStream_t s, Ws... ws) {      // register kernels: + ws
+    gn_launch<DROP>(plain, drop, nt, d, r, s, (const T*)d.src0, d.C0, (const T*)d.src1, d.C1, d.P, d.G, r.cblk, d.eps, d.gamma, d.beta, d.silu,
+                    (T*)d.y, d.stats, ws...);
+}
+template <typename T, bool DROP, typename KP, typename KD>
+static void gn_bwd_args(KP* plain, KD* drop, int nt, const mdm_gn_desc& d, const GnPlan& r, hipStream_t s, float* part) {      // register kernels: ws
+    gn_launch<DROP>(plain, drop, nt, d, r, s, (const T*)d.src0, d.C0, (const T*)d.src1, d.C1, d.P, d.G, r.cblk, d.gamma, d.beta, d.silu,
+                    (const T*)d.dy, d.stats, (T*)d.dst0, (const T*)d.add0, (T*)d.dst1, (const T*)d.add1, (const T*)d.add0b, d.dgamma, d.dbeta,
+                    d.sum_img, d.sum_ld, d.sum_all, part);
+}
+template <int NP, int NT>
+static void gn_fwd_reg_launch(const mdm_gn_desc& d, const GnPlan& r, hipStream_t s) {
+    gn_resolve(d, [&](auto t, auto drop) {
+        typedef decltype(t) T;
+        gn_fwd_args<T, decltype(drop)::value>(gn_fwd_reg_kernel<NP, 0, NT, T>, gn_fwd_reg_kernel_drop<NP, 0, NT, T>, NT, d, r, s, d.ws);
+    });
+}
+static void gn_fwd_launch(const mdm_gn_desc& d, const GnPlan& r, hipStream_t s) {
+    gn_resolve(d, [&](auto t, auto drop) {
+        typedef decltype(t) T;
+        gn_fwd_args<T, decltype(drop)::value>(gn_fwd_kernel<T>, gn_fwd_kernel_drop<T>, 256, d, r, s);
+    });
+}
+template <int NP, int NT>
+static void gn_bwd_reg_launch(const mdm_gn_desc& d, const GnPlan& r, hipStream_t s) {      // bf16 only
+    auto go = [&](auto drop) {
+        gn_bwd_args<bf16_t, decltype(drop)::value>(gn_bwd_reg_kernel<NP, 0, NT>, gn_bwd_reg_kernel_drop<NP, 0, NT>, NT, d, r, s, d.ws);
+    };
+    d.rng ? go(std::true_type()) : go(std::false_type());
+}
+static void gn_bwd_launch(const mdm_gn_desc& d, const GnPlan& r, hipStream_t s) {
+    float* part = r.route == GN_BWD_REDUCE ? d.ws : nullptr;
+    gn_resolve(d, [&](auto t, auto drop) {
+        typedef decltype(t) T;
+        gn_bwd_args<T, decltype(drop)::value>(gn_bwd_kernel<T>, gn_bwd_kernel_drop<T>, 256, d, r, s, part);
+    });
+    if (part) {
+        const int C = d.C0 + d.C1;
+        hipLaunchKernelGGL(gn_param_reduce_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, part, d.N, C, d.dgamma, d.dbeta, d.sum_all);
+    }
+}
+static const struct GnRouteRow {
+    const char* name;
+    void (*launch)(const mdm_gn_desc&, const GnPlan&, hipStream_t);
+} kGnRoutes[GN_ROUTES] = {
+    {"fwd_reg<1,256>", gn_fwd_reg_launch<1, 256>}, {"fwd_reg<2,256>", gn_fwd_reg_launch<2, 256>}, {"fwd_reg<2,512>", gn_fwd_reg_launch<2, 512>},
+    {"fwd_reg<4,512>", gn_fwd_reg_launch<4, 512>}, {"fwd_reg<8,512>", gn_fwd_reg_launch<8, 512>}, {"fwd", gn_fwd_launch},
+    {"bwd_reg<1,256>", gn_bwd_reg_launch<1, 256>}, {"bwd_reg<2,256>", gn_bwd_reg_launch<2, 256>}, {"bwd_reg<2,512>", gn_bwd_reg_launch<2, 512>},
+    {"bwd_reg<4,512>", gn_bwd_reg_launch<4, 512>}, {"bwd_reg<8,512>", gn_bwd_reg_launch<8, 512>}, {"bwd", gn_bwd_launch},
+    {"bwd+reduce", gn_bwd_launch},          // the fp32 backward: the generic kernel, then gn_param_reduce_kernel
+};
+static thread_local int g_gn_route = -1;
+
+// launches what gn_route names; a refused descriptor launches nothing and leaves no route
+static int gn_run(int which, const char* what, const mdm_gn_desc* desc_host, void* stream) {
+    g_gn_route = -1;
+    MDM_REQUIRE(desc_host != nullptr, "%s: null descriptor", what);
+    const mdm_gn_desc& d = *desc_host;
+    if (d.rng) {
+        MDM_REQUIRE(d.C1 == 0, "%s_dropout: a dropout site has one source (C1=%d)", what, d.C1);
+        MDM_REQUIRE(d.ctl, "%s_dropout: null rng / ctl", what);
+        MDM_REQUIRE(d.drop_base % 8 == 0, "%s_dropout: base must be a multiple of 8", what);
+    }
+    GnPlan r;
+    if (int rc = gn_route(which, d, &r)) return rc;
+    if (which == 1) {
+        MDM_REQUIRE(!(d.sum_img || d.sum_all) || d.C1 == 0, "groupnorm_bwd: column sums need a single-source dx");
+        MDM_REQUIRE(r.route != GN_BWD_REDUCE || d.ws, "groupnorm_bwd: the fp32 path needs ws (>= 3 * N * C floats) for its fixed-order sums");
+    }
+    kGnRoutes[r.route].launch(d, r, (hipStream_t)stream);
+    const int rc = launch_status(what);
+    if (rc == 0) g_gn_route = r.route;
+    return rc;
+}
+extern "C" int mdm_groupnorm_fwd(const mdm_gn_desc* desc_host, void* stream) { return gn_run(0, "groupnorm_fwd", desc_host, stream); }
+extern "C" int mdm_groupnorm_bwd(const mdm_gn_desc* desc_host, void* stream) { return gn_run(1, "groupnorm_bwd", desc_host, stream); }
+extern "C" const char* mdm_gn_route_of(int which, const mdm_gn_desc* desc_host) {
+    GnPlan r;
+    return desc_host && gn_route(which, *desc_host, &r) == 0 ? kGnRoutes[r.route].name : nullptr;
+}
+extern "C" const char* mdm_gn_last_route(void) { return g_gn_route >= 0 ? kGnRoutes[g_gn_route].name : "none"; }
+extern "C" int mdm_gn_route_names(const char** out, int cap) {
+    for (int i = 0; i < GN_ROUTES && i < cap; ++i)
+        if (out) out[i] = kGnRoutes[i].name;
+    return GN_ROUTES;
+}
+
 extern "C" int mdm_dropout_mask(const uint64_t* rng, uint64_t base, const uint32_t* ctl, int64_t n, uint8_t* keep, void* stream) {
     MDM_REQUIRE(rng && ctl && keep && n > 0 && n < (1ll << 36), "dropout_mask: bad arguments");
     const int64_t vecs = (int64_t)(((base + (uint64_t)n + 7) >> 3) - (base >> 3));
@@ -628,58 +694,6 @@ extern "C" int mdm_dropout_mask(const uint64_t* rng, uint64_t base, const uint32
 // sizes its workspace with this query instead of with a constant from the header's prose.
 extern "C" int64_t mdm_groupnorm_bwd_ws_floats(int dtype, int N, int C) {
     return dtype == MDM_F32 ? (int64_t)3 * N * C : 0;
-}
-
-template <bool DROP>
-static int gn_bwd_dispatch(const mdm_gn_desc& d, void* stream) {
-    const int dtype = d.dtype, C0 = d.C0, C1 = d.C1, N = d.N, P = d.P, G = d.G, silu = d.silu, sum_ld = d.sum_ld;
-    const void *src0 = d.src0, *src1 = d.src1, *dy = d.dy, *add0 = d.add0, *add0b = d.add0b, *add1 = d.add1;
-    void *dst0 = d.dst0, *dst1 = d.dst1;
-    const float *gamma = d.gamma, *beta = d.beta, *stats = d.stats;
-    float *dgamma = d.dgamma, *dbeta = d.dbeta, *sum_img = d.sum_img, *sum_all = d.sum_all, *ws = d.ws;
-    if (int rc = gn_check(C0, C1, G, N, P)) return rc;
-    const int C = C0 + C1, cblk = gn_cblk(C, G, N, P);
-    MDM_REQUIRE(cblk <= 64 && cblk / (C / G) <= 64, "groupnorm: unsupported channel/group combination C=%d G=%d", C, G);
-    MDM_REQUIRE(!(sum_img || sum_all) || C1 == 0, "groupnorm_bwd: column sums need a single-source dx");
-    dim3 grid(N, cdiv(C, cblk));
-    const int np = cdiv(P, 256 / (cblk / 8));
-    if (dtype == MDM_BF16 && np <= 16) {
-#define GN_BWD_ARGS (const bf16_t*)src0, C0, (const bf16_t*)src1, C1, P, G, cblk, gamma, beta, silu, (const bf16_t*)dy, stats, (bf16_t*)dst0,      \
-                    (const bf16_t*)add0, (bf16_t*)dst1, (const bf16_t*)add1, (const bf16_t*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, ws
-#define GN_BWD_REG(NPV, NT)                                                                                                                          \
-    do {                                                                                                                                             \
-        if constexpr (DROP)                                                                                                                          \
-            hipLaunchKernelGGL((gn_bwd_reg_kernel_drop<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, GN_BWD_ARGS, d.rng, d.drop_base, d.ctl); \
-        else                                                                                                                                         \
-            hipLaunchKernelGGL((gn_bwd_reg_kernel<NPV, 0, NT>), grid, dim3(NT), 0, (hipStream_t)stream, GN_BWD_ARGS);                                \
-    } while (0)
-        if (np <= 1) GN_BWD_REG(1, 256); else if (np <= 2) GN_BWD_REG(2, 256); else if (np <= 4) GN_BWD_REG(2, 512);
-        else if (np <= 8) GN_BWD_REG(4, 512); else GN_BWD_REG(8, 512);
-#undef GN_BWD_REG
-#undef GN_BWD_ARGS
-        return launch_status("groupnorm_bwd");
-    }
-    // fp32 path: fixed summation order across the images too (per-image partials in ws + a second stage); bf16 large maps: atomics
-    float* part = dtype == MDM_F32 ? ws : nullptr;
-    MDM_REQUIRE(dtype != MDM_F32 || ws, "groupnorm_bwd: the fp32 path needs ws (>= 3 * N * C floats) for its fixed-order sums");
-    if constexpr (DROP)
-        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_bwd_kernel_drop<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
-                                             (const T*)src1, C1, P, G, cblk, gamma, beta, silu, (const T*)dy, stats, (T*)dst0,
-                                             (const T*)add0, (T*)dst1, (const T*)add1, (const T*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, part,
-                                             d.rng, d.drop_base, d.ctl));
-    else
-        DISPATCH_T(dtype, hipLaunchKernelGGL((gn_bwd_kernel<T>), grid, dim3(256), 0, (hipStream_t)stream, (const T*)src0, C0,
-                                             (const T*)src1, C1, P, G, cblk, gamma, beta, silu, (const T*)dy, stats, (T*)dst0,
-                                             (const T*)add0, (T*)dst1, (const T*)add1, (const T*)add0b, dgamma, dbeta, sum_img, sum_ld, sum_all, part));
-    if (part)
-        hipLaunchKernelGGL(gn_param_reduce_kernel, dim3(cdiv(C, 256)), dim3(256), 0, (hipStream_t)stream, part, N, C, dgamma, dbeta, sum_all);
-    return launch_status("groupnorm_bwd");
-}
-extern "C" int mdm_groupnorm_bwd(const mdm_gn_desc* desc_host, void* stream) {
-    MDM_REQUIRE(desc_host != nullptr, "groupnorm_bwd: null descriptor");
-    if (!desc_host->rng) return gn_bwd_dispatch<false>(*desc_host, stream);
-    if (int rc = drop_check("groupnorm_bwd_dropout", *desc_host)) return rc;
-    return gn_bwd_dispatch<true>(*desc_host, stream);
 }
 
 #ifdef MDM_STAMP

@@ -430,6 +430,27 @@ def attn_route_names():
     return [v.decode() for v in arr]
 
 
+def gn_route_of(which, **fields):
+    """The GroupNorm kernel mdm_groupnorm_fwd (which = 0) / mdm_groupnorm_bwd (1) would launch for a descriptor with these
+    fields, e.g. "fwd_reg<4,512>", without launching (mdm_gn_route_of); None for a shape or dtype they refuse."""
+    r = load().mdm_gn_route_of(which, C.byref(_desc(fields, GnDesc)))
+    return None if r is None else r.decode()
+
+
+def gn_last_route():
+    """Kernel of the last mdm_groupnorm_fwd / mdm_groupnorm_bwd call on this thread (mdm_gn_last_route); "none" after a refused one."""
+    return load().mdm_gn_last_route().decode()
+
+
+def gn_route_names():
+    """Every name gn_route_of() / gn_last_route() can return."""
+    lib = load()
+    n = lib.mdm_gn_route_names(None, 0)
+    arr = (C.c_char_p * n)()
+    lib.mdm_gn_route_names(arr, n)
+    return [v.decode() for v in arr]
+
+
 def wgrad_group_accepts(**kw):
     kw.pop("_flops", None)
     return bool(load().mdm_wgrad_group_accepts(C.byref(_desc(kw))))

@@ -1133,7 +1133,9 @@ class UNet:
         self.dT_all = self.alloc((self.N, ft), torch.float32)
         self.t_in = self.alloc((self.N,), torch.float32)
         cmax = max(a.C for a in self.acts)
-        self.gn_ws = self.alloc((self.N * (64 * 32 + 4 * cmax),), torch.float32)     # slab partials + per-(image, channel) coefficients
+        self.gn_ws = self.alloc((self.N * (64 * 32 + 4 * cmax),), torch.float32)     # fp32 GroupNorm backward: per-image partial sums, 3 N C floats
+        # (mdm_groupnorm_bwd_ws_floats; no other kernel reads it.  The size dates from the pixel-chunked launches, which nothing dispatches, and
+        # stays: it is part of every plan's buffer layout)
         # split-K partial slabs of the weight-gradient contractions: room for 16 splits of the largest filter
         wmax = max(s.g.taps * s.g.Cout * s.g.Cin for s in self.specs if isinstance(s, _Conv))
         self.splitk_ws = self.alloc((16 * wmax,), torch.float32)

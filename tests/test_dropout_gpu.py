@@ -71,14 +71,26 @@ def test_mask_matches_the_numpy_restatement(base, offset, rate):
 
 
 # ----------------------------------------------------------------------------- 2: GroupNorm parity
+GN_DROPOUT_ROUTES = {      # (C, HW): {storage type: (forward, backward)}
+    (128, 64): {"bf16": ("fwd_reg<1,256>", "bwd_reg<1,256>"), "f32": ("fwd_reg<1,256>", "bwd+reduce")},
+    (256, 16): {"bf16": ("fwd_reg<1,256>", "bwd_reg<1,256>"), "f32": ("fwd_reg<1,256>", "bwd+reduce")},
+    (128, 1024): {"bf16": ("fwd_reg<4,512>", "bwd_reg<4,512>"), "f32": ("fwd_reg<8,512>", "bwd+reduce")},
+    (32, 4096): {"bf16": ("fwd", "bwd"), "f32": ("fwd", "bwd+reduce")},
+}
+
+
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("C,HW", [(128, 64), (256, 16), (128, 1024), (32, 4096)])
 def test_groupnorm_dropout_fwd_bwd(dt, C, HW):
-    """(128, 64) / (256, 16): gn_fwd_reg_kernel at small NP (both dtypes) and gn_bwd_reg_kernel; (128, 1024): both at large NP;
-    (32, 4096): more than 16 vectors per lane, the generic gn_fwd_kernel / gn_bwd_kernel; every fp32 backward is the generic kernel."""
-    from mdm import ops
+    """The register kernels at one vector per lane and at 8 - 16, and the generic kernels; every fp32 backward is the generic
+    kernel.  A dropout site runs on the kernel its plain GroupNorm runs on."""
+    from mdm import _lib, ops
     N, G, rate, silu = 3, 32, 0.3, True
     key, offset, base = 77 | (1 << 32), 5, 8 * 1000
+    fwd, bwd = GN_DROPOUT_ROUTES[C, HW][dt]
+    for fields in (dict(), dict(rng=16, ctl=16, drop_base=base)):
+        shape = dict(dtype=DT[dt], N=N, P=HW, G=G, C0=C, C1=0, **fields)
+        assert (_lib.gn_route_of(0, **shape), _lib.gn_route_of(1, **shape)) == (fwd, bwd)
     g = torch.Generator().manual_seed(C + HW)
     x = _q(torch.randn(N, C, HW, generator=g) * 1.5 + 0.3, dt).requires_grad_(True)
     gamma = (1 + 0.2 * torch.randn(C, generator=g)).requires_grad_(True)
