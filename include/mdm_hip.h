@@ -167,7 +167,7 @@ int mdm_gemm_route_names(const char** out, int cap);
  *                             (hipMemcpy): call it outside stream capture.
  *   mdm_wgrad_group_launch    the launches of the group, stream-ordered and capturable.  D0 = (acc0 ? D0 : 0) + dW.
  *   mdm_wgrad_group_destroy   frees the host-side handle (not dev_buf).
- * Nine-tap form (round 3).  3x3 stride-1 members (maps 8 / 16 / 32 wide, overwrite form) whose group gives every CU a share
+ * Nine-tap form.  3x3 stride-1 members (maps 8 / 16 / 32 / 64 wide, overwrite form) whose group gives every CU a share
  * of >= MDM_TAPS_MIN_SHARE (default 48) 64-pixel slabs run all nine taps in one pass over dY and the input (wgrad_taps_body):
  * the group is then ONE persistent launch of one workgroup per CU walking its column of the item table -- equal contiguous
  * shares of the (tile, slab) space, the remaining per-tap items in the same queues -- plus the split-K sum of per-tap layers
@@ -176,10 +176,43 @@ int mdm_gemm_route_names(const char** out, int cap);
  * are ignored.  Same results as the per-tap form up to fp32 summation order.  Environment: MDM_WGRAD_TAPS=0 keeps every layer
  * on the per-tap kernels; MDM_TAPS_DEBUG=1 prints the schedule of each group; MDM_WGRAD_RESERVE_CUS=r builds the persistent nine-tap
  * launch for CUs - r workgroups (data-parallel runs: room for the collective's kernels beside it).
+ *
+ * dev_buf, in this order, every section but the last padded to a multiple of 256 bytes:
+ *   1. descriptors   n x mdm_gemm_desc, resolved (splitk = 1 on nine-tap members)
+ *   2. flat items    per-tap form only: [entry][8 queues] item words, workgroup b of the flat grid takes word b
+ *   3. taps table    merged form only: [round][queue] item words, queue = one workgroup per CU (less the reserve)
+ *   4. part tiles    one 48-byte record per nine-tap tile that was cut: {float* dst; int64 dtap; int32 N, m0, n0, first_slot,
+ *                    parts, rows, cols, pad}
+ *   5. slots         nslots x [9][128][64] fp32 partial sums of the parts of the cut tiles
+ * A group has either section 2 (form 0, "wgrad_group") or sections 3-5 (form 1, "wgrad_taps_group"), never both.
+ * The item word is four int32 {x, y, z, w}:
+ *   x  descriptor index, -1 = padding
+ *   w  kind: 0 = 64x64, 1 = 128x128, 2 = 256x128 per-tap tile, 3 = nine-tap tile
+ *   per-tap (w < 3):  y = item index inside the descriptor, below tiles x taps x splitk;  z = tiles (of that kind) per tap and k-split
+ *   nine-tap (w = 3): y = tile | (slot + 1) << 12 (tile < 4096; slot + 1 = 0: uncut, the tile is stored straight into D0; slot + 1 < 2^19,
+ *                     a plan that needs more is refused);  z = k0 | k1 << 16: the 64-pixel slabs [k0, k1) of the reduction
+ *
+ *   mdm_wgrad_group_schedule  the table mdm_wgrad_group_create would upload for these descriptors on a device of n_cu CUs
+ *                             (n_cu is the queue count of the merged form as it stands: MDM_WGRAD_RESERVE_CUS is not applied
+ *                             to it, the other environment variables are read as in create).  Host arithmetic only: no
+ *                             device is asked, pointers are never dereferenced, mdm_gemm_last_route stays as it is.
+ *                             One row of eight int32 per table entry, padding included, in table order:
+ *                               [0] queue   entry index % 8 (form 0) or % n_cu (form 1)
+ *                               [1] round   entry index / 8 (form 0) or / n_cu (form 1)
+ *                               [2] desc    descriptor index; -1 = padding, and [3..7] are then 0
+ *                               [3] kind    w of the item word
+ *                               [4] tile_or_item   per-tap: the item index (y);  nine-tap: the tile
+ *                               [5] k0      per-tap: tiles per tap and k-split (z);  nine-tap: first slab
+ *                               [6] k1      per-tap: 0;  nine-tap: one past the last slab
+ *                               [7] slot    per-tap: 0;  nine-tap: slot + 1 of the item word (0 = uncut)
+ *                             rows_out == NULL (the size query) only fills *n_rows_out, *need_bytes_out (create's) and
+ *                             *form_out (0 per-tap, 1 merged); otherwise cap_rows >= *n_rows_out rows of space are required.
  * ------------------------------------------------------------------------- */
 int mdm_wgrad_group_accepts(const mdm_gemm_desc* desc_host);
 int mdm_wgrad_group_create(const mdm_gemm_desc* descs_host, int n, void* dev_buf, int64_t dev_bytes,
                            int64_t* need_bytes_out, void** handle_out);
+int mdm_wgrad_group_schedule(const mdm_gemm_desc* descs_host, int n, int n_cu, int32_t* rows_out, int64_t cap_rows,
+                             int64_t* n_rows_out, int64_t* need_bytes_out, int32_t* form_out);
 int mdm_wgrad_group_launch(void* handle, void* stream);
 int mdm_wgrad_group_destroy(void* handle);
 

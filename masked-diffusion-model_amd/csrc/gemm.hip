@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include <algorithm>
+#include <memory>
 #include <type_traits>
 #include <vector>
 
@@ -2312,7 +2313,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad_lin_kernel(mdm_gemm_desc d, int
 //   * a folded nearest x2 upsample (unet6.py:472) only changes the address the input DMA reads a (virtual) pixel from.
 // 24 KB of operands per slab for 9.4 MFLOP (per-tap tiles: 48 KB for 4.2), 36 fp32 accumulator tiles (144 registers) per wave.
 // Work item = (tile, range of slabs [k0, k1)): the host cuts the (tile, slab) space of a whole group into one contiguous
-// share per CU (mdm_wgrad_group_create), so a tile that is cut writes its partial sums to a `slot` ([9][128][64] fp32) and
+// share per CU (plan_wgrad_group), so a tile that is cut writes its partial sums to a `slot` ([9][128][64] fp32) and
 // tile_parts_reduce_kernel adds the slots; an uncut tile goes straight to the gradient.
 // Requires: 3x3, stride 1, pad 1, OW in {8, 16, 32}, OH a power of two, OH OW >= 64, bf16; M a multiple of 128 or one partly filled
 // tile (M < 128, 8 | M), N a multiple of 64 or one partly filled tile: the two 8-channel ends of the U-Net ride along on zero operands.
@@ -2599,7 +2600,7 @@ __device__ __forceinline__ void wgrad_taps_body(const mdm_gemm_desc& d, const in
 #endif
 }
 
-// sums the partial slots of the tiles that mdm_wgrad_group_create cut (fixed order: slot index = position in the tile's slab range)
+// sums the partial slots of the tiles that plan_wgrad_group cut (fixed order: slot index = position in the tile's slab range)
 struct PartTile { float* dst; long long dtap; int N, m0, n0, first_slot, parts, rows, cols, pad; };
 __global__ __launch_bounds__(256) void tile_parts_reduce_kernel(const PartTile* __restrict__ tab, const float* __restrict__ slots) {
     constexpr int PER_TILE4 = TAPS_SLOT_FLOATS / 4, PIECES = PER_TILE4 / 1024;
@@ -2626,23 +2627,37 @@ __global__ __launch_bounds__(256) void tile_parts_reduce_kernel(const PartTile* 
 // them as ONE flat grid: the chip is filled by the group, not by each layer on its own, so a layer needs only as
 // many k-splits as balance asks for (fewer fp32 partial slabs: the per-layer launches wrote and re-read ~0.9 GB
 // of them per step at cfg2), and ~70 launch gaps / prologues / drain tails per step disappear.
-// items[i] = {descriptor index, item index inside it, tiles per (tap, k-range), tile: 2 = 256x128, 1 = 128x128, 0 = 64x64}.
+// THE ITEM WORD, one int4 per table entry, written by the host (per_tap_word / taps_word) and read by both kernels below:
+//   x  descriptor index, -1 = padding (no work)
+//   w  GroupKind: the tile of a per-tap item, or GK_TAPS
+//   per-tap item (w != GK_TAPS):  y = item index inside the descriptor (tile + tiles_x * (tap + taps * k-split)), z = tiles_x
+//   nine-tap item (w == GK_TAPS): y = tile | (slot + 1) << ITEM_SLOT_SHIFT, slot + 1 == 0: the tile is not cut and goes straight to
+//                                 the gradient;  z = k0 | k1 << ITEM_K_BITS, the 64-pixel slabs [k0, k1) of the reduction
 // (256 output channels x 128 input channels per workgroup feed 48 KB of operands per 64-pixel slab for twice the MFMA
 // work of the 128x128 tile's 32 KB: the loop is bound by the bytes a CU takes in, so the wider tile runs ~1.3x faster.)
+enum GroupKind : int { GK_64 = 0, GK_128 = 1, GK_256x128 = 2, GK_TAPS = 3 };
+constexpr int ITEM_TILE_BITS = 12, ITEM_SLOT_SHIFT = ITEM_TILE_BITS, ITEM_K_BITS = 16;
+constexpr int ITEM_TILE_MASK = (1 << ITEM_TILE_BITS) - 1, ITEM_K_MASK = (1 << ITEM_K_BITS) - 1;
+constexpr int ITEM_MAX_TILES = ITEM_TILE_MASK, ITEM_MAX_SLABS = ITEM_K_MASK;      // wgrad_taps_eligible: tiles <= , slabs <
+constexpr int ITEM_MAX_SLOTS = (1 << (31 - ITEM_SLOT_SHIFT)) - 1;                 // slot + 1 stays positive in a signed y
+
+__device__ __forceinline__ void wgrad_per_tap_item(const mdm_gemm_desc& d, const int kind, const int item, const int tiles_x) {
+    if (kind == GK_256x128) wgrad_lin_body<256, 128, 3, 8>(d, item, tiles_x);
+    else if (kind == GK_128) wgrad_lin_body<128, 128, 3, 8>(d, item, tiles_x);
+    else wgrad_lin_body<64, 64, 4, 8>(d, item, tiles_x);
+}
 __global__ __launch_bounds__(512) void wgrad_group_kernel(const mdm_gemm_desc* descs, const int4* items, int n_items) {
     // grid == n_items: one item per workgroup; a smaller grid walks the (longest-first) list with stride gridDim.x
     for (int i = blockIdx.x; i < n_items; i += gridDim.x) {
         const int4 it = items[i];
         if (it.x < 0) continue;             // padding of the per-XCD queues (uniform for the workgroup)
         const mdm_gemm_desc d = descs[it.x];
-        if (it.w == 2) wgrad_lin_body<256, 128, 3, 8>(d, it.y, it.z);
-        else if (it.w == 1) wgrad_lin_body<128, 128, 3, 8>(d, it.y, it.z);
-        else wgrad_lin_body<64, 64, 4, 8>(d, it.y, it.z);
+        wgrad_per_tap_item(d, it.w, it.y, it.z);
         __syncthreads();            // the next item refills the LDS ring
     }
 }
 // The nine-tap layers of a group: grid = CUs, workgroup q walks column q of table[round][queue] (one share per CU, equal by
-// construction: mdm_wgrad_group_create).  item = {descriptor, tile | (slot + 1) << 12, k0 | k1 << 16, 3}.
+// construction: plan_wgrad_group).
 __global__ __launch_bounds__(512) void wgrad_taps_group_kernel(const mdm_gemm_desc* descs, const int4* items, int n_items, float* slots) {
     for (int i = blockIdx.x; i < n_items; i += gridDim.x) {
         int4 it = items[i];
@@ -2650,13 +2665,11 @@ __global__ __launch_bounds__(512) void wgrad_taps_group_kernel(const mdm_gemm_de
         it.w = __builtin_amdgcn_readfirstlane(it.w);
         if (it.x < 0) continue;
         const mdm_gemm_desc& d = descs[it.x];       // (fields are read where they are used: a copy would sit in registers next to 144 accumulators)
-        float* slot = (it.y >> 12) ? slots + (int64_t)((it.y >> 12) - 1) * TAPS_SLOT_FLOATS : nullptr;
-        const int tile = it.y & 4095, k0 = it.z & 0xFFFF, k1 = (int)((unsigned)it.z >> 16);
-        if (it.w != 3) {                    // a per-tap item that rides in this CU's queue (1x1 projections, 8-channel / stride-2 / 4x4 layers)
+        float* slot = (it.y >> ITEM_SLOT_SHIFT) ? slots + (int64_t)((it.y >> ITEM_SLOT_SHIFT) - 1) * TAPS_SLOT_FLOATS : nullptr;
+        const int tile = it.y & ITEM_TILE_MASK, k0 = it.z & ITEM_K_MASK, k1 = (int)((unsigned)it.z >> ITEM_K_BITS);
+        if (it.w != GK_TAPS) {              // a per-tap item that rides in this CU's queue (1x1 projections, 8-channel / stride-2 / 4x4 layers)
             const mdm_gemm_desc dc = d;
-            if (it.w == 2) wgrad_lin_body<256, 128, 3, 8>(dc, it.y, it.z);
-            else if (it.w == 1) wgrad_lin_body<128, 128, 3, 8>(dc, it.y, it.z);
-            else wgrad_lin_body<64, 64, 4, 8>(dc, it.y, it.z);
+            wgrad_per_tap_item(dc, it.w, it.y, it.z);
         } else if (d.dbias != nullptr && tile % ((d.N + TAPS_BN - 1) / TAPS_BN) == 0) wgrad_taps_body<true>(d, tile, k0, k1, slot);
         else wgrad_taps_body<false>(d, tile, k0, k1, slot);
         __syncthreads();
@@ -3574,15 +3587,14 @@ static bool wgrad_lin_eligible(const mdm_gemm_desc& d) {
     return d.stride == 1 && d.ups == 1 && ((64 / d.OW) & 1) == 0;                   // folded nearest x2 upsample
 }
 
-// all nine taps in one pass (wgrad_taps_body); MDM_WGRAD_TAPS=0 keeps every layer on the per-tap kernel (A/B runs)
+// all nine taps in one pass (wgrad_taps_body): the geometry, and a tile index / slab count that fit the item word.  (The A/B switch
+// MDM_WGRAD_TAPS is GroupKnobs::taps_enabled.)
 static bool wgrad_taps_eligible(const mdm_gemm_desc& d) {
-    static const bool off = [] { const char* e = getenv("MDM_WGRAD_TAPS"); return e && atoi(e) == 0; }();
-    if (off) return false;
     return d.dtype == MDM_BF16 && d.layout == 2 && d.conv && d.KH == 3 && d.KW == 3 && d.stride == 1 && d.pad_t == 1 && d.pad_l == 1 &&
            (d.OW == 8 || d.OW == 16 || d.OW == 32 || d.OW == 64) && d.OH >= 2 && (d.OH & (d.OH - 1)) == 0 && d.OH * d.OW >= 64 && d.IH == d.OH && d.IW == d.OW &&
            (d.ups == 0 || d.ups == 1) && (d.M % TAPS_BM == 0 || (d.M < TAPS_BM && d.M % 8 == 0)) && (d.N % TAPS_BN == 0 || (d.N < TAPS_BN && d.N % 8 == 0)) &&
-           cdiv(d.N, TAPS_BN) * cdiv(d.M, TAPS_BM) <= 4095 && d.K % 64 == 0 &&
-           d.K / 64 < 65535 && d.C0 % 8 == 0 && d.C1 % 8 == 0 && d.N == d.C0 + d.C1 && d.out_f32 && !d.acc0 && d.ldd0 == d.N && d.N0 == d.N &&
+           cdiv(d.N, TAPS_BN) * cdiv(d.M, TAPS_BM) <= ITEM_MAX_TILES && d.K % 64 == 0 &&
+           d.K / 64 < ITEM_MAX_SLABS && d.C0 % 8 == 0 && d.C1 % 8 == 0 && d.N == d.C0 + d.C1 && d.out_f32 && !d.acc0 && d.ldd0 == d.N && d.N0 == d.N &&
            d.alpha == 1.0f && d.dtap == (int64_t)d.M * d.N;
 }
 
@@ -4158,20 +4170,43 @@ static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
 }
 
 // ---- grouped weight gradients ---------------------------------------------------------------------------------
+// Host side: group_knobs reads the environment and the device (the only getenv / HIP calls in front of the upload), plan_wgrad_group
+// is host arithmetic on the descriptors, mdm_wgrad_group_schedule shows a plan, mdm_wgrad_group_create uploads one.
 struct WgradGroup {
     const mdm_gemm_desc* descs_dev = nullptr;
-    const int4* items_dev = nullptr;
-    int n_items = 0, max_blocks = 0;
+    const int4* items_dev = nullptr;        // per-tap form: the flat grid's table [entry][8 queues]
+    int n_items = 0;
     std::vector<ReduceTable> reduces;       // the split-K sums of the group's split layers: passed by value at launch
     std::vector<int> reduce_blocks;
-    const int4* taps_items_dev = nullptr;   // the nine-tap layers: table[round][CU] of the persistent launch
+    const int4* taps_items_dev = nullptr;   // merged form: table[round][CU] of the persistent launch
     int n_taps_items = 0, taps_blocks = 0;
     float* slots_dev = nullptr;             // nine-tap tiles that were cut: partial sums [slot][9][128][64]
     const PartTile* parts_dev = nullptr;
     int n_part_tiles = 0;
 };
-struct GroupItem { int desc, item, tiles_x, big, cost; };
+struct GroupKnobs { int n_cu; int min_share; double slab_cost, item_cost; bool taps_enabled; bool debug; };
+struct GroupItem { int desc, item, tiles_x, kind, slabs; };     // a per-tap work item and the 64-pixel slabs of its k-range
 struct TapsTile { int desc, tile, slabs; };
+// Everything mdm_wgrad_group_create decides.  dev_buf = descriptors | flat items | taps table | part tiles | slots, every section
+// but the last padded to 256 bytes.
+struct GroupPlan {
+    std::vector<mdm_gemm_desc> descs;       // resolved; splitk = 1 on nine-tap members
+    bool merged = false;                    // false: per-tap flat grid (`items`); true: ONE persistent launch (`taps_table`)
+    int n_cu = 0;                           // workgroups (= queues) of the persistent launch
+    std::vector<int4> items;                // [entry][8 XCD queues], workgroup b takes entry (b / 8, b % 8)
+    std::vector<int4> taps_table;           // [round][n_cu queues]
+    std::vector<PartTile> parts;            // the nine-tap tiles that were cut, and the slots of their parts
+    int nslots = 0;
+    std::vector<ReduceTable> reduces;
+    std::vector<int> reduce_blocks;
+    int64_t desc_bytes = 0, item_bytes = 0, taps_bytes = 0, part_bytes = 0, need = 0;
+    int64_t items_at() const { return desc_bytes; }
+    int64_t taps_at() const { return items_at() + item_bytes; }
+    int64_t parts_at() const { return taps_at() + taps_bytes; }
+    int64_t slots_at() const { return parts_at() + part_bytes; }
+    size_t taps_tiles = 0, per_tap_items = 0;                   // what MDM_TAPS_DEBUG prints of the merged form
+    double slabs_total = 0, level = 0, load_lo = 0, load_hi = 0;
+};
 
 }  // namespace mdm
 using namespace mdm;
@@ -4282,37 +4317,98 @@ extern "C" int mdm_wgrad_group_accepts(const mdm_gemm_desc* desc_host) {
     const mdm_gemm_desc d = with_n0(*desc_host);
     return wgrad_lin_eligible(d) && d.out_f32 && d.N0 == d.N && d.ldd0 == d.N && d.dtap == (int64_t)d.M * d.N ? 1 : 0;
 }
+// MDM_TAPS_MIN_SHARE and MDM_WGRAD_RESERVE_CUS are read per call (the kernel test forces the nine-tap path on a small group;
+// bench.py --reserve-cus), the cost constants and the A/B switch once per process.  n_cu > 0 is the caller's queue count as it
+// stands and no device is asked; otherwise the device's CU count (256 if it cannot be had) less the reserve, at least 8.
+//   MDM_WGRAD_RESERVE_CUS=r (data-parallel runs): the persistent nine-tap launch is built for CUs - r workgroups, leaving r CUs
+//   to whatever else wants to run beside it -- RCCL's all-reduce kernels of the previous bucket.
+static GroupKnobs group_knobs(int n_cu) {
+    static const double slab_cost = [] { const char* e = getenv("MDM_TAPS_SLAB_COST"); return e ? atof(e) : 4350.0; }();
+    static const double item_cost = [] { const char* e = getenv("MDM_TAPS_ITEM_COST"); return e ? atof(e) : 25000.0; }();
+    static const bool taps_off = [] { const char* e = getenv("MDM_WGRAD_TAPS"); return e && atoi(e) == 0; }();
+    GroupKnobs k{n_cu, 48, slab_cost, item_cost, !taps_off, getenv("MDM_TAPS_DEBUG") != nullptr};
+    if (const char* e = getenv("MDM_TAPS_MIN_SHARE")) k.min_share = atoi(e);
+    if (n_cu <= 0) {
+        static const int n_cu_dev = [] {
+            int dev = 0; hipDeviceProp_t pr;
+            if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess || pr.multiProcessorCount <= 0) return 256;
+            return pr.multiProcessorCount;
+        }();
+        const char* rs = getenv("MDM_WGRAD_RESERVE_CUS");
+        k.n_cu = std::max(8, n_cu_dev - (rs ? std::max(0, atoi(rs)) : 0));
+    }
+    return k;
+}
+
+static int4 per_tap_word(const GroupItem& gi) { return make_int4(gi.desc, gi.item, gi.tiles_x, gi.kind); }
+static int4 taps_word(int desc, int tile, int slot1, int k0, int k1) {
+    return make_int4(desc, tile | (slot1 << ITEM_SLOT_SHIFT), k0 | (k1 << ITEM_K_BITS), GK_TAPS);
+}
+// the 64-pixel slabs of k-split `ks` of a per-tap member (the k-ranges of wgrad_lin_body)
+static int split_slabs(const mdm_gemm_desc& d, int ks) {
+    const int sk = d.splitk < 1 ? 1 : d.splitk;
+    const int chunk = ((d.K + sk - 1) / sk + 63) / 64 * 64;
+    const int len = d.K - ks * chunk;
+    return (len > chunk ? chunk : len) / 64;
+}
+// Two cost models of a per-tap item, both deliberate and both measured with in-kernel stamps (scripts/stamp_group.py).  The per-tap
+// form only ORDERS bundles and balances 8 queues, so it uses small integer units per slab and tile kind.  The merged form pours
+// nine-tap slabs (GroupKnobs::slab_cost / item_cost, shader cycles) into the same queues, so there the per-tap items count in cycles.
+static int cost_units(const GroupItem& gi) { return gi.slabs * (gi.kind == GK_256x128 ? 6 : gi.kind == GK_128 ? 4 : 1) + 2; }
+static double cost_cycles(const GroupItem& gi) {
+    return gi.kind == GK_256x128 ? gi.slabs * 2500.0 + 11000 : gi.kind == GK_128 ? gi.slabs * 1510.0 + 5700 : gi.slabs * 1050.0 + 3000;
+}
+
+// Per-tap form, order.  The items of one (layer, k-range) -- every filter tap x output tile -- read the same dY and input slabs,
+// so they should meet in ONE XCD's L2 (each of the 8 XCDs otherwise fetches the slabs for itself: this kernel was
+// 2.8 GB of the step's 6.3 GB of L2-side traffic).  Workgroup b runs on XCD b % 8 (observed dispatch rule, used for
+// speed only): the table is laid out [maxlen][8 queues], workgroup b takes entry (b / 8, b % 8).  Bundles go longest
+// first to the queue with the least work so far (short ones fill the tail); unused entries are no-ops (desc -1).
+static void build_per_tap_table(const std::vector<mdm_gemm_desc>& ds, const std::vector<GroupItem>& items, std::vector<int4>& table) {
+    std::vector<std::pair<long long, std::pair<int, int>>> bundles;            // (cost of one item, [first, last) in `items`)
+    for (size_t a = 0; a < items.size();) {
+        size_t b = a;
+        const int per = items[a].tiles_x * (int)(ds[(size_t)items[a].desc].KH * ds[(size_t)items[a].desc].KW);
+        while (b < items.size() && items[b].desc == items[a].desc && items[b].item / per == items[a].item / per) ++b;
+        // (at most 12 items per bundle -- a few neighbouring taps x the output tiles: whole 18..72-item bundles balance
+        // the 32 CUs of an XCD too coarsely, measured +1 % on the step)
+        for (size_t c = a; c < b; c += 12) bundles.push_back({cost_units(items[a]), {(int)c, (int)(c + 12 < b ? c + 12 : b)}});
+        a = b;
+    }
+    std::stable_sort(bundles.begin(), bundles.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
+    std::vector<std::vector<int>> queue(8);
+    long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (const auto& bd : bundles) {
+        int q = 0;
+        for (int x = 1; x < 8; ++x) if (load[x] < load[q]) q = x;
+        for (int i = bd.second.first; i < bd.second.second; ++i) { queue[(size_t)q].push_back(i); load[q] += cost_units(items[(size_t)i]); }
+    }
+    size_t maxlen = 0;
+    for (const auto& qv : queue) maxlen = qv.size() > maxlen ? qv.size() : maxlen;
+    table.assign(8 * maxlen, make_int4(-1, 0, 0, 0));
+    for (size_t x = 0; x < 8; ++x)
+        for (size_t w = 0; w < queue[x].size(); ++w) table[w * 8 + x] = per_tap_word(items[(size_t)queue[x][w]]);
+}
+
 // Schedule of a group's nine-tap layers: ONE queue per CU, walked by one persistent workgroup (grid = CUs, table[round][queue]).
 // The (tile, slab) space is poured over the queues in order, every queue up to the common level -- a tile is cut where a queue
 // is full, so the shares are equal by construction and a tile has only as many partial slots as CUs that worked on it.
-// Costs in shader cycles per slab / per item, from in-kernel stamps (scripts/stamp_group.py).
-static void build_taps_schedule(const std::vector<mdm_gemm_desc>& ds, const std::vector<TapsTile>& tt, const std::vector<GroupItem>& legacy, int NQ,
-                                std::vector<int4>& table, std::vector<PartTile>& parts, int& nslots) {
-    static const double CF = [] { const char* e = getenv("MDM_TAPS_SLAB_COST"); return e ? atof(e) : 4350.0; }();
-    static const double FF = [] { const char* e = getenv("MDM_TAPS_ITEM_COST"); return e ? atof(e) : 25000.0; }();
-    const int MINPART = 8;
+static void build_taps_schedule(const std::vector<mdm_gemm_desc>& ds, const std::vector<TapsTile>& tt, const std::vector<GroupItem>& per_tap,
+                                const GroupKnobs& kn, GroupPlan& p) {
+    const int NQ = kn.n_cu, MINPART = 8;
+    const double CF = kn.slab_cost, FF = kn.item_cost;
     std::vector<std::vector<int4>> fq((size_t)NQ), lq((size_t)NQ);
     std::vector<double> load((size_t)NQ, 0.0);
     double total = 0.0;
     {   // the per-tap items of the group (1x1 projections, 8-channel / stride-2 / 4x4 layers) ride in the same queues: longest first
         // onto the least loaded one; the nine-tap shares then fill every queue up to the common level
-        auto cost = [&](const GroupItem& gi) -> double {
-            const mdm_gemm_desc& d = ds[(size_t)gi.desc];
-            const int sk = d.splitk < 1 ? 1 : d.splitk;
-            const int chunk = ((d.K + sk - 1) / sk + 63) / 64 * 64;
-            const int ks = gi.item / (gi.tiles_x * d.KH * d.KW);
-            int len = d.K - ks * chunk; if (len > chunk) len = chunk;
-            const double slabs = len / 64.0;
-            return gi.big == 2 ? slabs * 2500 + 11000 : gi.big == 1 ? slabs * 1510 + 5700 : slabs * 1050 + 3000;
-        };
         std::vector<std::pair<double, int>> order;
-        for (size_t a = 0; a < legacy.size(); ++a) order.push_back({cost(legacy[a]), (int)a});
+        for (size_t a = 0; a < per_tap.size(); ++a) order.push_back({cost_cycles(per_tap[a]), (int)a});
         std::stable_sort(order.begin(), order.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
         for (const auto& o : order) {
             int qq = 0;
             for (int x = 1; x < NQ; ++x) if (load[(size_t)x] < load[(size_t)qq]) qq = x;
-            const GroupItem& gi = legacy[(size_t)o.second];
-            lq[(size_t)qq].push_back(make_int4(gi.desc, gi.item, gi.tiles_x, gi.big));
+            lq[(size_t)qq].push_back(per_tap_word(per_tap[(size_t)o.second]));
             load[(size_t)qq] += o.first; total += o.first;
         }
     }
@@ -4323,7 +4419,7 @@ static void build_taps_schedule(const std::vector<mdm_gemm_desc>& ds, const std:
     // pour the nine-tap tiles; a part is never shorter than MINPART slabs.  What does not fit (every queue keeps up to MINPART slabs
     // of room) would all land in the last queue: raise the level until the last queue is no higher than the others.
     for (int attempt = 0; attempt < 40; ++attempt) {
-        load = base_load; parts.clear(); nslots = 0;
+        load = base_load; p.parts.clear(); p.nslots = 0;
         for (auto& v : fq) v.clear();
         int q = 0;
         for (const auto& t : tt) {
@@ -4343,18 +4439,17 @@ static void build_taps_schedule(const std::vector<mdm_gemm_desc>& ds, const std:
                 k += take;
             }
             const int tiles_n = cdiv(d.N, TAPS_BN), tm = t.tile / tiles_n, tn = t.tile - tm * tiles_n;
-            if (ps.size() > 1) {
+            const bool cut = ps.size() > 1;
+            if (cut) {
                 PartTile pt;
                 pt.dst = reinterpret_cast<float*>(d.D0); pt.dtap = d.dtap; pt.N = d.N; pt.m0 = tm * TAPS_BM; pt.n0 = tn * TAPS_BN;
-                pt.first_slot = nslots; pt.parts = (int)ps.size();
+                pt.first_slot = p.nslots; pt.parts = (int)ps.size();
                 pt.rows = d.M - pt.m0 < TAPS_BM ? d.M - pt.m0 : TAPS_BM; pt.cols = d.N - pt.n0 < TAPS_BN ? d.N - pt.n0 : TAPS_BN;
-                parts.push_back(pt);
+                p.parts.push_back(pt);
             }
-            for (size_t a2 = 0; a2 < ps.size(); ++a2) {
-                const int slot1 = ps.size() > 1 ? nslots + (int)a2 + 1 : 0;
-                fq[(size_t)ps[a2].q].push_back(make_int4(t.desc, t.tile | (slot1 << 12), ps[a2].k0 | (ps[a2].k1 << 16), 3));
-            }
-            if (ps.size() > 1) nslots += (int)ps.size();
+            for (size_t a2 = 0; a2 < ps.size(); ++a2)
+                fq[(size_t)ps[a2].q].push_back(taps_word(t.desc, t.tile, cut ? p.nslots + (int)a2 + 1 : 0, ps[a2].k0, ps[a2].k1));
+            if (cut) p.nslots += (int)ps.size();
         }
         if (load[(size_t)NQ - 1] <= level * 1.01) break;
         level *= 1.015;
@@ -4364,82 +4459,64 @@ static void build_taps_schedule(const std::vector<mdm_gemm_desc>& ds, const std:
         fq[(size_t)x].insert(fq[(size_t)x].end(), lq[(size_t)x].begin(), lq[(size_t)x].end());
         rounds = fq[(size_t)x].size() > rounds ? fq[(size_t)x].size() : rounds;
     }
-    table.assign(rounds * (size_t)NQ, make_int4(-1, 0, 0, 0));
+    p.taps_table.assign(rounds * (size_t)NQ, make_int4(-1, 0, 0, 0));
     for (int x = 0; x < NQ; ++x)
-        for (size_t w = 0; w < fq[(size_t)x].size(); ++w) table[w * (size_t)NQ + (size_t)x] = fq[(size_t)x][w];
-    if (getenv("MDM_TAPS_DEBUG")) {
-        double lo = 1e30, hi = 0;
-        for (int x = 0; x < NQ; ++x) { lo = load[(size_t)x] < lo ? load[(size_t)x] : lo; hi = load[(size_t)x] > hi ? load[(size_t)x] : hi; }
-        fprintf(stderr, "[mdm] wgrad group: %zu nine-tap tiles (%.0f slabs) + %zu per-tap items, %d queues x %zu rounds, level %.0f, load %.0f..%.0f, %zu cut tiles, %d slots\n",
-                tt.size(), slabs_total, legacy.size(), NQ, rounds, level, lo, hi, parts.size(), nslots);
-    }
+        for (size_t w = 0; w < fq[(size_t)x].size(); ++w) p.taps_table[w * (size_t)NQ + (size_t)x] = fq[(size_t)x][w];
+    p.taps_tiles = tt.size(); p.per_tap_items = per_tap.size(); p.slabs_total = slabs_total; p.level = level;
+    p.load_lo = *std::min_element(load.begin(), load.end()); p.load_hi = *std::max_element(load.begin(), load.end());
 }
 
-extern "C" int mdm_wgrad_group_create(const mdm_gemm_desc* descs_host, int n, void* dev_buf, int64_t dev_bytes,
-                                      int64_t* need_bytes_out, void** handle_out) {
-    MDM_REQUIRE(descs_host && n > 0 && need_bytes_out && handle_out, "wgrad_group_create: bad arguments");
-    *handle_out = nullptr;
-    std::vector<mdm_gemm_desc> ds((size_t)n);
-    std::vector<GroupItem> items;
-    std::vector<TapsTile> taps_tiles;
-    WgradGroup* g = new WgradGroup();
-    ReduceTable tab;
-    tab.n = 0;
-    int blocks = 0;
-    auto close_table = [&]() {
-        if (tab.n > 0) { tab.first_block[tab.n] = blocks; g->reduces.push_back(tab); g->reduce_blocks.push_back(blocks); }
-        tab.n = 0; blocks = 0;
-    };
-    static const int n_cu_dev = [] {
-        int dev = 0; hipDeviceProp_t pr;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&pr, dev) != hipSuccess || pr.multiProcessorCount <= 0) return 256;
-        return pr.multiProcessorCount;
-    }();
+// Where every weight-gradient work item of the group runs.  Host arithmetic only: no HIP call, no static state, the pointers of the
+// descriptors are copied and never dereferenced.
+static int plan_wgrad_group(const mdm_gemm_desc* descs_host, int n, const GroupKnobs& kn, GroupPlan& p) {
+    MDM_REQUIRE(descs_host && n > 0 && kn.n_cu > 0, "wgrad_group_create: bad arguments");
+    p = GroupPlan();
+    p.n_cu = kn.n_cu;
+    std::vector<Resolved> rs((size_t)n);
+    auto nine_tap = [&](const mdm_gemm_desc& d) { return kn.taps_enabled && wgrad_taps_eligible(d); };
+    long long taps_slabs = 0;
+    for (int i = 0; i < n; ++i) {
+        Resolved& r = rs[(size_t)i];
+        if (int rc = resolve(descs_host + i, false, r)) return rc;
+        MDM_REQUIRE(mdm_wgrad_group_accepts(&r.d), "wgrad_group_create: descriptor %d is not a groupable weight gradient", i);
+        // (asked of the caller's descriptor: resolve has already folded a split without a workspace into an unsplit reduction)
+        MDM_REQUIRE(!(descs_host[i].splitk > 1 && !descs_host[i].ws), "wgrad_group_create: descriptor %d is split %d ways but has no workspace of its own",
+                    i, descs_host[i].splitk);
+        if (nine_tap(r.d)) taps_slabs += (long long)cdiv(r.d.M, TAPS_BM) * cdiv(r.d.N, TAPS_BN) * (r.d.K / 64);
+    }
     // The nine-tap kernel pays ~30 000 cycles per work item around its loop (two DMA round trips + transposes in front, nine fp32 tiles
     // behind) and a launch that sums the cut tiles' slots; its loop is ~1.3x faster per flop than the per-tap tiles'.  Per group
     // (profiles/r03_wgrad_taps_stamps.txt): the decoder's 32x32 / 16x16 layers (94 slabs per CU) 392 -> 330 us, the encoder's (34 slabs per
     // CU) and the 8x8 maps' (10 per CU) came out 10-40 % slower.  So: only where a CU's share is long.
-    const char* ms_env = getenv("MDM_TAPS_MIN_SHARE");          // (read per group: the kernel test forces the path on a small group)
-    const int min_share = ms_env ? atoi(ms_env) : 48;
-    // MDM_WGRAD_RESERVE_CUS=r (data-parallel runs): the persistent nine-tap launch is built for CUs - r workgroups, leaving r CUs
-    // to whatever else wants to run beside it -- RCCL's all-reduce kernels of the previous bucket (bench.py --reserve-cus)
-    const char* rs_env = getenv("MDM_WGRAD_RESERVE_CUS");
-    const int n_cu = std::max(8, n_cu_dev - (rs_env ? std::max(0, atoi(rs_env)) : 0));
-    long long taps_slabs = 0;
+    const bool use_taps = taps_slabs >= (long long)kn.min_share * kn.n_cu;
+    std::vector<GroupItem> items;
+    std::vector<TapsTile> taps_tiles;
+    ReduceTable tab;
+    tab.n = 0;
+    int blocks = 0;
+    auto close_table = [&]() {
+        if (tab.n > 0) { tab.first_block[tab.n] = blocks; p.reduces.push_back(tab); p.reduce_blocks.push_back(blocks); }
+        tab.n = 0; blocks = 0;
+    };
+    p.descs.resize((size_t)n);
     for (int i = 0; i < n; ++i) {
-        Resolved r;
-        if (resolve(descs_host + i, false, r) == 0 && wgrad_taps_eligible(r.d)) taps_slabs += (long long)cdiv(r.d.M, TAPS_BM) * cdiv(r.d.N, TAPS_BN) * (r.d.K / 64);
-    }
-    const bool use_taps = taps_slabs >= (long long)min_share * n_cu;
-    for (int i = 0; i < n; ++i) {
-        Resolved r;
-        if (int rc = resolve(descs_host + i, false, r)) { delete g; return rc; }
-        if (!mdm_wgrad_group_accepts(&r.d)) { delete g; set_error("wgrad_group_create: descriptor %d is not a groupable weight gradient", i); return -1; }
-        if (r.d.splitk > 1 && !r.d.ws) { delete g; set_error("wgrad_group_create: descriptor %d is split %d ways but has no workspace of its own", i, r.d.splitk); return -1; }
-        if (use_taps && wgrad_taps_eligible(r.d)) {             // all nine taps per work item: cut into per-CU shares below, no split-K slabs
-            r.d.splitk = 1;
-            ds[(size_t)i] = r.d;
-            const int tiles = cdiv(r.d.M, TAPS_BM) * cdiv(r.d.N, TAPS_BN);
-            for (int tl = 0; tl < tiles; ++tl) taps_tiles.push_back(TapsTile{i, tl, r.d.K / 64});
+        const Resolved& r = rs[(size_t)i];
+        mdm_gemm_desc& d = p.descs[(size_t)i] = r.d;
+        if (use_taps && nine_tap(d)) {                          // all nine taps per work item: cut into per-CU shares below, no split-K slabs
+            d.splitk = 1;
+            const int tiles = cdiv(d.M, TAPS_BM) * cdiv(d.N, TAPS_BN);
+            for (int tl = 0; tl < tiles; ++tl) taps_tiles.push_back(TapsTile{i, tl, d.K / 64});
             continue;
         }
-        ds[(size_t)i] = r.d;
-        const mdm_gemm_desc& d = r.d;
-        const int BK = 64, sk = d.splitk < 1 ? 1 : d.splitk;
-        const int chunk = ((d.K + sk - 1) / sk + BK - 1) / BK * BK;
+        const int sk = d.splitk < 1 ? 1 : d.splitk;
         // tile: 256 x 128 where the filter has >= 256 output channels (a multiple of 256) and the reduction is long
         // (short reductions -- the 4x4 maps: 8 slabs -- take 64x64 tiles when a layer has to fill the chip on its own; in the static
         //  queues of a nine-tap group the big tiles' 2.7x fewer cycles per flop count instead)
         const bool big = r.big || (use_taps && d.M >= 128 && d.N >= 128 && sk == 1);
-        const int tile_kind = !big ? 0 : (d.M % 256 == 0 && d.N >= 128 ? 2 : 1);
-        const int tiles_i = tile_kind == 2 ? (d.M / 256) * cdiv(d.N, 128) : tile_kind == 1 ? cdiv(d.M, 128) * cdiv(d.N, 128) : (int)r.tiles;
+        const GroupKind kind = !big ? GK_64 : (d.M % 256 == 0 && d.N >= 128 ? GK_256x128 : GK_128);
+        const int tiles_i = kind == GK_256x128 ? (d.M / 256) * cdiv(d.N, 128) : kind == GK_128 ? cdiv(d.M, 128) * cdiv(d.N, 128) : (int)r.tiles;
         const int n_local = tiles_i * r.zouter * sk;
-        for (int it = 0; it < n_local; ++it) {
-            const int ks = it / (tiles_i * r.zouter);
-            int len = d.K - ks * chunk;
-            if (len > chunk) len = chunk;
-            items.push_back(GroupItem{i, it, tiles_i, tile_kind, (len / BK) * (tile_kind == 2 ? 6 : tile_kind == 1 ? 4 : 1) + 2});
-        }
+        for (int it = 0; it < n_local; ++it) items.push_back(GroupItem{i, it, tiles_i, kind, split_slabs(d, it / (tiles_i * r.zouter))});
         if (sk > 1) {
             const long long total4 = (long long)((int64_t)r.zouter * d.M * d.N / 4);
             const long long nb = (total4 + REDUCE_VEC_PER_BLOCK - 1) / REDUCE_VEC_PER_BLOCK;
@@ -4450,68 +4527,73 @@ extern "C" int mdm_wgrad_group_create(const mdm_gemm_desc* descs_host, int n, vo
         }
     }
     close_table();
-    // Order.  The items of one (layer, k-range) -- every filter tap x output tile -- read the same dY and input slabs,
-    // so they should meet in ONE XCD's L2 (each of the 8 XCDs otherwise fetches the slabs for itself: this kernel was
-    // 2.8 GB of the step's 6.3 GB of L2-side traffic).  Workgroup b runs on XCD b % 8 (observed dispatch rule, used for
-    // speed only): the table is laid out [8 queues][maxlen], workgroup b takes entry (b % 8, b / 8).  Bundles go longest
-    // first to the queue with the least work so far (short ones fill the tail); unused entries are no-ops (desc -1).
-    std::vector<std::pair<long long, std::pair<int, int>>> bundles;            // (cost of one item, [first, last) in `items`)
-    for (size_t a = 0; a < items.size();) {
-        size_t b = a;
-        const int per = items[a].tiles_x * (int)(ds[(size_t)items[a].desc].KH * ds[(size_t)items[a].desc].KW);
-        while (b < items.size() && items[b].desc == items[a].desc && items[b].item / per == items[a].item / per) ++b;
-        // (at most 12 items per bundle -- a few neighbouring taps x the output tiles: whole 18..72-item bundles balance
-        // the 32 CUs of an XCD too coarsely, measured +1 % on the step)
-        for (size_t c = a; c < b; c += 12) bundles.push_back({items[a].cost, {(int)c, (int)(c + 12 < b ? c + 12 : b)}});
-        a = b;
-    }
-    std::stable_sort(bundles.begin(), bundles.end(), [](const auto& x, const auto& y) { return x.first > y.first; });
-    std::vector<std::vector<int>> queue(8);
-    long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (const auto& bd : bundles) {
-        int q = 0;
-        for (int x = 1; x < 8; ++x) if (load[x] < load[q]) q = x;
-        for (int i = bd.second.first; i < bd.second.second; ++i) { queue[(size_t)q].push_back(i); load[q] += items[(size_t)i].cost; }
-    }
-    size_t maxlen = 0;
-    for (const auto& qv : queue) maxlen = qv.size() > maxlen ? qv.size() : maxlen;
-    const size_t n_slots_lin = 8 * maxlen;
-    // the nine-tap layers: their own table, launch and partial slots
-    std::vector<int4> taps_table;
-    std::vector<PartTile> parts;
-    int nslots = 0;
-    const bool merged = !taps_tiles.empty();        // a group with nine-tap layers runs as ONE persistent launch, its per-tap items in the same queues
-    if (merged) build_taps_schedule(ds, taps_tiles, items, n_cu, taps_table, parts, nslots);
-    const size_t n_slots = merged ? 0 : n_slots_lin;
+    p.merged = !taps_tiles.empty();         // a group with nine-tap layers runs as ONE persistent launch, its per-tap items in the same queues
+    if (p.merged) build_taps_schedule(p.descs, taps_tiles, items, kn, p);
+    else build_per_tap_table(p.descs, items, p.items);
+    MDM_REQUIRE(p.nslots <= ITEM_MAX_SLOTS, "wgrad_group_create: %d partial slots do not fit the item word (at most %d)", p.nslots, ITEM_MAX_SLOTS);
     auto pad256 = [](int64_t v) { return (v + 255) / 256 * 256; };
-    const int64_t desc_bytes = pad256((int64_t)n * (int64_t)sizeof(mdm_gemm_desc));
-    const int64_t item_bytes = pad256((int64_t)n_slots * 16), titem_bytes = pad256((int64_t)taps_table.size() * 16);
-    const int64_t part_bytes = pad256((int64_t)parts.size() * (int64_t)sizeof(PartTile));
-    const int64_t need = desc_bytes + item_bytes + titem_bytes + part_bytes + (int64_t)nslots * TAPS_SLOT_FLOATS * 4;
-    *need_bytes_out = need;
-    if (!dev_buf || dev_bytes < need) { delete g; return 0; }      // size query
-    std::vector<int4> it4(n_slots, make_int4(-1, 0, 0, 0));
-    for (int x = 0; x < 8 && !merged; ++x)
-        for (size_t w = 0; w < queue[(size_t)x].size(); ++w) {
-            const GroupItem& gi = items[(size_t)queue[(size_t)x][w]];
-            it4[w * 8 + (size_t)x] = make_int4(gi.desc, gi.item, gi.tiles_x, gi.big);      // slot of workgroup b = w * 8 + x
-        }
+    p.desc_bytes = pad256((int64_t)n * (int64_t)sizeof(mdm_gemm_desc));
+    p.item_bytes = pad256((int64_t)p.items.size() * 16);
+    p.taps_bytes = pad256((int64_t)p.taps_table.size() * 16);
+    p.part_bytes = pad256((int64_t)p.parts.size() * (int64_t)sizeof(PartTile));
+    p.need = p.slots_at() + (int64_t)p.nslots * TAPS_SLOT_FLOATS * 4;
+    return 0;
+}
+
+extern "C" int mdm_wgrad_group_schedule(const mdm_gemm_desc* descs_host, int n, int n_cu, int32_t* rows_out, int64_t cap_rows,
+                                        int64_t* n_rows_out, int64_t* need_bytes_out, int32_t* form_out) {
+    MDM_REQUIRE(n_cu > 0 && n_rows_out && need_bytes_out && form_out, "wgrad_group_schedule: bad arguments");
+    GroupPlan p;
+    if (int rc = plan_wgrad_group(descs_host, n, group_knobs(n_cu), p)) return rc;
+    const std::vector<int4>& table = p.merged ? p.taps_table : p.items;
+    const int queues = p.merged ? p.n_cu : 8;
+    *n_rows_out = (int64_t)table.size(); *need_bytes_out = p.need; *form_out = p.merged ? 1 : 0;
+    if (!rows_out) return 0;                // size query
+    MDM_REQUIRE(cap_rows >= (int64_t)table.size(), "wgrad_group_schedule: %lld rows do not fit %lld", (long long)table.size(), (long long)cap_rows);
+    for (size_t i = 0; i < table.size(); ++i) {
+        const int4 it = table[i];
+        int32_t* row = rows_out + 8 * i;
+        row[0] = (int32_t)(i % (size_t)queues); row[1] = (int32_t)(i / (size_t)queues); row[2] = it.x < 0 ? -1 : it.x; row[3] = it.x < 0 ? 0 : it.w;
+        const bool taps = it.x >= 0 && it.w == GK_TAPS;
+        row[4] = it.x < 0 ? 0 : taps ? (it.y & ITEM_TILE_MASK) : it.y;
+        row[5] = it.x < 0 ? 0 : taps ? (it.z & ITEM_K_MASK) : it.z;
+        row[6] = taps ? (int32_t)((unsigned)it.z >> ITEM_K_BITS) : 0;
+        row[7] = taps ? (it.y >> ITEM_SLOT_SHIFT) : 0;
+    }
+    return 0;
+}
+
+extern "C" int mdm_wgrad_group_create(const mdm_gemm_desc* descs_host, int n, void* dev_buf, int64_t dev_bytes,
+                                      int64_t* need_bytes_out, void** handle_out) {
+    MDM_REQUIRE(descs_host && n > 0 && need_bytes_out && handle_out, "wgrad_group_create: bad arguments");
+    *handle_out = nullptr;
+    const GroupKnobs kn = group_knobs(0);
+    GroupPlan p;
+    if (int rc = plan_wgrad_group(descs_host, n, kn, p)) return rc;
+    if (kn.debug && p.merged)
+        fprintf(stderr, "[mdm] wgrad group: %zu nine-tap tiles (%.0f slabs) + %zu per-tap items, %d queues x %zu rounds, level %.0f, load %.0f..%.0f, %zu cut tiles, %d slots\n",
+                p.taps_tiles, p.slabs_total, p.per_tap_items, p.n_cu, p.taps_table.size() / (size_t)p.n_cu, p.level, p.load_lo, p.load_hi, p.parts.size(), p.nslots);
+    *need_bytes_out = p.need;
+    if (!dev_buf || dev_bytes < p.need) return 0;       // size query
     char* base = reinterpret_cast<char*>(dev_buf);
-    hipError_t e = hipMemcpy(base, ds.data(), (size_t)n * sizeof(mdm_gemm_desc), hipMemcpyHostToDevice);
-    if (e == hipSuccess && !it4.empty()) e = hipMemcpy(base + desc_bytes, it4.data(), it4.size() * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !taps_table.empty()) e = hipMemcpy(base + desc_bytes + item_bytes, taps_table.data(), taps_table.size() * 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !parts.empty()) e = hipMemcpy(base + desc_bytes + item_bytes + titem_bytes, parts.data(), parts.size() * sizeof(PartTile), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { delete g; return hip_fail(e, "wgrad_group_create: hipMemcpy"); }
+    hipError_t e = hipMemcpy(base, p.descs.data(), (size_t)n * sizeof(mdm_gemm_desc), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !p.items.empty()) e = hipMemcpy(base + p.items_at(), p.items.data(), p.items.size() * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !p.taps_table.empty()) e = hipMemcpy(base + p.taps_at(), p.taps_table.data(), p.taps_table.size() * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !p.parts.empty()) e = hipMemcpy(base + p.parts_at(), p.parts.data(), p.parts.size() * sizeof(PartTile), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "wgrad_group_create: hipMemcpy");
+    std::unique_ptr<WgradGroup> g(new WgradGroup());
     g->descs_dev = reinterpret_cast<const mdm_gemm_desc*>(base);
-    g->items_dev = reinterpret_cast<const int4*>(base + desc_bytes);
-    g->n_items = (int)n_slots;
-    g->taps_items_dev = reinterpret_cast<const int4*>(base + desc_bytes + item_bytes);
-    g->n_taps_items = (int)taps_table.size();
-    g->taps_blocks = n_cu;
-    g->parts_dev = reinterpret_cast<const PartTile*>(base + desc_bytes + item_bytes + titem_bytes);
-    g->slots_dev = reinterpret_cast<float*>(base + desc_bytes + item_bytes + titem_bytes + part_bytes);
-    g->n_part_tiles = (int)parts.size();
-    *handle_out = g;
+    g->items_dev = reinterpret_cast<const int4*>(base + p.items_at());
+    g->n_items = (int)p.items.size();
+    g->taps_items_dev = reinterpret_cast<const int4*>(base + p.taps_at());
+    g->n_taps_items = (int)p.taps_table.size();
+    g->taps_blocks = p.n_cu;
+    g->parts_dev = reinterpret_cast<const PartTile*>(base + p.parts_at());
+    g->slots_dev = reinterpret_cast<float*>(base + p.slots_at());
+    g->n_part_tiles = (int)p.parts.size();
+    g->reduces = std::move(p.reduces);
+    g->reduce_blocks = std::move(p.reduce_blocks);
+    *handle_out = g.release();
     return 0;
 }
 extern "C" int mdm_wgrad_group_launch(void* handle, void* stream) {
@@ -4527,10 +4609,8 @@ extern "C" int mdm_wgrad_group_launch(void* handle, void* stream) {
         const int tb = g->taps_blocks < g->n_taps_items ? g->taps_blocks : g->n_taps_items;
         hipLaunchKernelGGL(wgrad_taps_group_kernel, dim3((unsigned)tb), dim3(512), bytes, s, g->descs_dev, g->taps_items_dev, g->n_taps_items, g->slots_dev);
     }
-    if (g->n_items > 0) {
-        const int nb = (g->max_blocks > 0 && g->max_blocks < g->n_items) ? g->max_blocks : g->n_items;
-        hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)nb), dim3(512), bytes, s, g->descs_dev, g->items_dev, g->n_items);
-    }
+    if (g->n_items > 0)
+        hipLaunchKernelGGL(wgrad_group_kernel, dim3((unsigned)g->n_items), dim3(512), bytes, s, g->descs_dev, g->items_dev, g->n_items);
     for (size_t i = 0; i < g->reduces.size(); ++i)
         hipLaunchKernelGGL(splitk_reduce_batched_kernel, dim3((unsigned)g->reduce_blocks[i]), dim3(256), 0, s, g->reduces[i]);
     if (g->n_part_tiles > 0)

@@ -313,6 +313,28 @@ def gemm_plan(**kw):
     return sk.value, nb.value
 
 
+def _desc_array(fields_list):
+    arr = (GemmDesc * len(fields_list))()
+    for i, f in enumerate(fields_list):
+        d = _desc({k: v for k, v in f.items() if k != "_flops"})
+        C.memmove(C.byref(arr, i * C.sizeof(GemmDesc)), C.byref(d), C.sizeof(GemmDesc))
+    return arr
+
+
+def wgrad_group_schedule(fields_list, n_cu):
+    """The table WgradGroup(fields_list) would upload on a device of `n_cu` CUs, decoded (mdm_wgrad_group_schedule, no device):
+    -> (rows, need_bytes, form): one tuple (queue, round, desc, kind, tile_or_item, k0, k1, slot) per table entry, padding
+    included; the bytes of the device table; 0 = per-tap flat grid, 1 = merged persistent launch."""
+    lib, arr, n = load(), _desc_array(fields_list), len(fields_list)
+    n_rows, need, form = i64(), i64(), i32()
+    check(lib.mdm_wgrad_group_schedule(arr, n, n_cu, None, 0, C.byref(n_rows), C.byref(need), C.byref(form)), "mdm_wgrad_group_schedule")
+    rows = (i32 * (8 * n_rows.value))()
+    check(lib.mdm_wgrad_group_schedule(arr, n, n_cu, rows, n_rows.value, C.byref(n_rows), C.byref(need), C.byref(form)),
+          "mdm_wgrad_group_schedule")
+    flat = list(rows)
+    return [tuple(flat[i:i + 8]) for i in range(0, len(flat), 8)], need.value, form.value
+
+
 class WgradGroup:
     """Handle of mdm_wgrad_group_*: a set of weight-gradient descriptors that run as ONE launch (+ one launch summing
     their split-K partials).  `fields_list`: keyword dicts like `gemm()` takes.  The device table lives in a tensor
@@ -322,10 +344,7 @@ class WgradGroup:
         lib = load()
         n = len(fields_list)
         self.flops = sum(f.pop("_flops", 0.0) for f in fields_list)
-        arr = (GemmDesc * n)()
-        for i, f in enumerate(fields_list):
-            d = _desc(f)
-            C.memmove(C.byref(arr, i * C.sizeof(GemmDesc)), C.byref(d), C.sizeof(GemmDesc))
+        arr = _desc_array(fields_list)
         need, h = i64(), vp()
         check(lib.mdm_wgrad_group_create(arr, n, None, 0, C.byref(need), C.byref(h)), "mdm_wgrad_group_create")
         self.table = torch.empty(need.value, dtype=torch.uint8, device=device)

@@ -41,6 +41,24 @@ def test_only_the_grouped_rows_are_left_out():
     assert all(kinds[cid] == "group" for cid in OUTSIDE)
 
 
+@pytest.mark.parametrize("case", [c for c in R.CASES if c.values[0].id in OUTSIDE])
+def test_grouped_rows_take_the_form_their_route_names(case, monkeypatch):
+    """The rows mdm_gemm is not asked about: mdm_wgrad_group_schedule says which form the group takes on a 256-CU device --
+    `wgrad_group*` is the per-tap flat grid (form 0), `wgrad_taps_group*` the merged persistent launch (form 1)."""
+    from mdm import _lib
+    dev, g = torch.device("cpu"), torch.Generator().manual_seed(0)
+    fields = [R.BUILD["wgrad"](R.Prob(dev), m, g) for m in case.p["members"]]
+    if case.p.get("min_share") is None:
+        monkeypatch.delenv("MDM_TAPS_MIN_SHARE", raising=False)
+    else:
+        monkeypatch.setenv("MDM_TAPS_MIN_SHARE", str(case.p["min_share"]))
+    before = _lib.last_route()
+    _, _, form = _lib.wgrad_group_schedule(fields, 256)
+    assert case.route.split("+")[0] in ("wgrad_group", "wgrad_taps_group")
+    assert form == int(case.route.startswith("wgrad_taps_group")), case.id
+    assert _lib.last_route() == before
+
+
 def test_refused_descriptor_has_no_route():
     from mdm import _lib
     f = dict(dtype=R.BF, layout=0, M=64, N=64, K=64, A=16, lda=64, B=16, ldb=64, D0=16, ldd0=64, N0=64)
