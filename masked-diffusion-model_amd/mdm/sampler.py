@@ -15,6 +15,9 @@ What is different from the reference loop (same arithmetic, same RNG order in re
 """
 from __future__ import annotations
 
+import functools
+import types
+
 import numpy as np
 import torch
 
@@ -144,87 +147,83 @@ class Sampler:
         ops.nchw_to_nhwc(_lib.F32, pred, nh, n, c, h, w, cp)
         return nh, cp, _lib.F32
 
-    def _sample_graph(self, model, timesteps, x_t, dep, mode):
-        """The same loop as `_sample_mean_shift_momentum` (history off, device RNG) with ONE hipGraph per reverse step:
-        the per-step scalars (t, t-1, shift ratio, degrade amounts, Philox offset) are produced on the device by
-        `mdm_sampler_step_params` from a step counter, so T replays need no host work in between."""
-        from .scheduler import SHIFT_KINDS, _fill_mode
+    def _emit_step(self, b, update, params, forward):
+        """One reverse step (sampler.py:137-216) over the fixed buffers `b`, launched or recorded: shift + perturb, the forward,
+        x0 reconstruction, the two degrades, and with `update` the write of x_t.  What the two loops do differently comes in:
+        `params()` fills b.time / ratio / amt_t / amt_next and bumps the Philox offset, `forward()` runs the net on b.x_in ->
+        (pred NHWC, Cp, dtype); `b.draw_z` / `b.mask_src` (`_draws`) make a launch's random input in the scheduler's RNG mode."""
         a, S = self.args, self.Scheduler
-        dev = S.device
-        T = len(timesteps)
-        n, c, hw = a.sample_num, a.out_channel, a.data_size
-        HW = hw * hw
-        st = a.shift_type
-        if st not in SHIFT_KINDS:
-            raise UnboundLocalError(f"shift_time undefined for shift_type={st!r}")
-        kind = SHIFT_KINDS[st]
-        per_col = int(S.reference_quirks and kind in (3, 4) and n == hw and n > 1)
-        sel = a.select_degrade_pixel
-        fm, fc = _fill_mode(a.mean_option, a.mean_area)
-        Cm = S._check_degrade_args(x_t)
-        amount_tab = (S.pixels_dev if sel == "indexing" else S.ratio_dev).to(dev, torch.float64).contiguous()
+        n, c, h, w = b.x_t.shape
+        dep, mask_src = a.sampling_mask_dependency, b.mask_src
+        params()
+        S.emit_shift(b.x_t, b.s, b.x_in, kind=b.kind, ratio=b.ratio if b.kind != 0 else None, z=b.draw_z(), nhwc=b.nhwc)  # :142-143
+        pred, cp, pdt = forward()                                                                                      # :145
+        call("mdm_sampler_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), N=n, C=c, H=h, W=w,
+             pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0), x0_hat=ptr(b.x0_hat), stream=stream())              # :146-152
+        degrade = functools.partial(S.emit_degrade, b.x0_hat, mean_pixel=b.mp, mean_option=a.mean_option, mean_area=a.mean_area)
+        if dep == "independent":                                                                                       # :175-181
+            degrade(b.d_t, rng_stream=3, mask_out=b.m_t, **mask_src(b.amt_t, b.mi_t))
+            degrade(b.d_next, rng_stream=4, mask_out=b.m_next, **mask_src(b.amt_next, b.mi_next))
+        elif dep == "dependent_t":      # :191-196, nested masks: ONE draw (the same Philox stream) thresholded at both ratios
+            src = mask_src(b.amt_t, b.mi_t)
+            degrade(b.d_t, rng_stream=3, mask_out=b.m_t, **src)
+            degrade(b.d_next, rng_stream=3, mask_out=b.m_next, **dict(src, amount=b.amt_next))
+        else:                           # :184-188: the mask of the step before, read before this step's takes its place
+            degrade(b.d_t, rng_stream=0, mask_in=b.m_next)
+            degrade(b.d_next, rng_stream=4, mask_out=b.m_next, **mask_src(b.amt_next, b.mi_next))
+        if update:                                                                                                     # :206-216
+            call("mdm_sampler_update", ptr(b.d_t), ptr(b.d_next), ptr(b.x_t), ptr(b.diff), int(a.momentum_adaptive == "base_momentum"),
+                 b.x_t.numel(), stream())
+
+    def _sample_graph(self, model, timesteps, b):
+        """The same loop as the host-driven one of `_sample_mean_shift_momentum` (history off, device RNG) with ONE hipGraph per
+        reverse step: the per-step scalars (t, t-1, shift ratio, degrade amounts, Philox offset) are produced on the device by
+        `mdm_sampler_step_params` from a step counter, so T replays need no host work in between."""
+        S = self.Scheduler
+        dev, T, n = S.device, len(timesteps), b.x_t.shape[0]
+        amount_tab = (S.pixels_dev if b.indexing else S.ratio_dev).to(dev, torch.float64).contiguous()
         ratio_tab = S.ratio_dev.to(dev, torch.float64).contiguous()
         ts_dev = torch.as_tensor([int(t) for t in timesteps], dtype=torch.int32, device=dev)
         ctr = torch.zeros(1, dtype=torch.int32, device=dev)
-        f64 = lambda: torch.empty(n, dtype=torch.float64, device=dev)
-        ratio, amt_t, amt_next = f64(), f64(), f64()
-        img = lambda: torch.empty_like(x_t)
-        s, x_in, x0_hat, d_t, d_next, m_t, diff = img(), img(), img(), img(), img(), img(), torch.zeros_like(x_t)
-        m_next = torch.zeros(n, c, hw, hw, device=dev)
-        mi_t, mi_next = (img(), img()) if sel == "indexing" else (None, None)
-        mp = torch.empty(n, c, device=dev)
-        rng = S.dev_rng.dev
 
-        def degrade(amount, stream_id, mask_src, out, mask_out, mi):
-            same = dict(x0=ptr(x0_hat), u=None, amount_stride=1, rng=ptr(rng), N=n, C=c, HW=HW, fill_mode=fm, fill_const=fc,
-                        x_t=ptr(out), mean_pixel=ptr(mp), stream=stream())
-            if mask_src is not None:                      # degrade_with_mask (scheduler.py:572-598)
-                call("mdm_degrade", **same, mask_in=ptr(mask_src), amount=None, rng_stream=0, Cm=c, mask=None)
-            elif sel == "indexing":
-                call("mdm_index_mask", ptr(amount), 1, ptr(rng), stream_id, n, c, HW, ptr(mi), stream())
-                call("mdm_degrade", **same, mask_in=ptr(mi), amount=None, rng_stream=stream_id, Cm=c, mask=ptr(mask_out))
-            else:
-                call("mdm_degrade", **same, mask_in=None, amount=ptr(amount), rng_stream=stream_id, Cm=Cm, mask=ptr(mask_out))
-
-        def emit(update):
+        def params():
             call("mdm_sampler_step_params", timesteps=ptr(ts_dev), T=T, step_ctr=ptr(ctr), ratio_tab=ptr(ratio_tab),
-                 amount_tab=ptr(amount_tab), n=n, time_out=ptr(model.t_in), ratio_out=ptr(ratio) if kind != 0 else None,
-                 amt_t=ptr(amt_t), amt_next=ptr(amt_next), rng=ptr(rng), stream=stream())
-            call("mdm_shift", x_t=ptr(x_t), z=None, ratio=ptr(ratio) if kind != 0 else None, rng=ptr(rng), rng_stream=2, kind=kind,
-                 noise_mean=float(getattr(a, "noise_mean", 0.0)), per_column=per_col, N=n, C=c, H=hw, W=hw, s=ptr(s), x_in=ptr(x_in),
-                 dtype=model.dt, x_in_nhwc=ptr(model.x_in.data), Cp=model.cin_p, stream=stream())
+                 amount_tab=ptr(amount_tab), n=n, time_out=ptr(b.time), ratio_out=ptr(b.ratio) if b.kind != 0 else None,
+                 amt_t=ptr(b.amt_t), amt_next=ptr(b.amt_next), rng=ptr(S.dev_rng.dev), stream=stream())
+
+        def forward():
             _lib._recording.extend(model.forward_plan)
-            call("mdm_sampler_x0", dtype=model.dt, pred_nhwc=ptr(model.y_out.data), Cp=model.cout_p, x_in=ptr(x_in), s=ptr(s),
-                 N=n, C=c, H=hw, W=hw, pred_nchw=None, shifted0=None, x0_hat=ptr(x0_hat), stream=stream())
-            if dep == "independent":
-                degrade(amt_t, 3, None, d_t, m_t, mi_t)
-                degrade(amt_next, 4, None, d_next, m_next, mi_next)
-            elif dep == "dependent_t":                    # nested masks: the SAME Philox stream thresholded at both ratios
-                degrade(amt_t, 3, None, d_t, m_t, mi_t)
-                degrade(amt_next, 3, None, d_next, m_next, mi_next)
-            else:
-                degrade(None, 0, m_next, d_t, None, None)
-                degrade(amt_next, 4, None, d_next, m_next, mi_next)
-            if update:
-                call("mdm_sampler_update", ptr(d_t), ptr(d_next), ptr(x_t), ptr(diff), int(mode == "base_momentum"), x_t.numel(), stream())
+            return model.y_out.data, model.cout_p, model.dt
 
         with _lib.Recording() as body:
-            emit(True)
-        with _lib.Recording() as last:
-            emit(False)                                      # i == 0: base_sampling breaks before the write, momentum skips it
-        keep = (ts_dev, ctr, ratio, amt_t, amt_next, s, x_in, d_t, d_next, m_t, m_next, mi_t, mi_next, mp, diff, amount_tab, ratio_tab)
+            self._emit_step(b, True, params, forward)
+        with _lib.Recording() as last:                       # i == 0: base_sampling breaks before the write, momentum skips it
+            self._emit_step(b, False, params, forward)
         gb, gl = _lib.GraphExec(body), _lib.GraphExec(last)
         for _ in range(T - 1):
             gb.launch()
         gl.launch()
-        self._graph_keep = (keep, gb, gl)
-        return x0_hat
+        self._graph_keep = ((b, ts_dev, ctr, amount_tab, ratio_tab), gb, gl)
+        return b.x0_hat
+
+    def _draws(self, b):
+        """-> (z(), mask_src(amount, index_buffer)): the random input of a shift / a degrade launch as keywords of the Scheduler's
+        emitters.  Device RNG: the kernels draw (Philox), 'indexing' pairs the degrade with the index-mask launch.  Replay RNG: the
+        host's draws, made when asked for -- where the reference makes them (shift, degrade t, degrade t-1)."""
+        S = self.Scheduler
+        n, c, h, w = b.x_t.shape
+        if S.rng_mode == "device":
+            return (lambda: None), (lambda amount, mi: dict(index_mask=(amount, mi)) if b.indexing else dict(amount=amount))
+        def mask_src(amount, mi):
+            if b.indexing:
+                return dict(mask_in=S.host_index_mask(S._host_full(amount.cpu().long(), n), n, c, h, w))
+            return dict(amount=amount, u=S.host_uniforms(b.x_t))
+        return (lambda: S.host_shift_z(S._host_full(b.ratio.cpu(), n), n, c, h, w) if b.kind != 0 else None), mask_src
 
     def _sample_mean_shift_momentum(self, model, timesteps, latent=None):
         from .unet import UNet
         a, S = self.args, self.Scheduler
-        dev = S.device
-        T = len(timesteps)
+        dev, T = S.device, len(timesteps)
         n, c, hw = a.sample_num, a.out_channel, a.data_size
         dep, mode = a.sampling_mask_dependency, a.momentum_adaptive
         if dep not in ("independent", "dependent_prev", "dependent_t"):
@@ -241,57 +240,50 @@ class Sampler:
         if fused:
             assert (model.N, model.H, model.W) == (n, hw, hw), "UNet plan was built for another batch/extent"
         x_t = (latent if latent is not None else self._get_latent_initial(model)).to(dev, torch.float32).contiguous()
-        m_next = torch.zeros(n, c, hw, hw, device=dev)
-        hist = None
-        if hist_mode:
-            hist = {k: torch.zeros(T + 1, n, c, hw, hw, device=dev) for k in HISTORY_NAMES}
-        if (fused and not hist_mode and S.rng_mode == "device" and model.use_graph and getattr(a, "sampler_graph", True)
-                and self.step_hook is None):
-            return self._sample_graph(model, timesteps, x_t, dep, mode), []
-        x0_hat = torch.empty_like(x_t)
-        pred_nchw = torch.empty_like(x_t) if hist_mode else None
-        shifted0 = torch.empty_like(x_t) if hist_mode else None
-        diff = torch.zeros_like(x_t)
-        numel = x_t.numel()
+        graph = (fused and not hist_mode and S.rng_mode == "device" and model.use_graph and getattr(a, "sampler_graph", True)
+                 and self.step_hook is None)
+        # the step's buffers, allocated once: both loops run `_emit_step` over them
+        img = lambda on=True: torch.empty_like(x_t) if on else None
+        f64 = lambda: torch.empty(n, dtype=torch.float64, device=dev)
+        indexing = a.select_degrade_pixel == "indexing"
+        b = types.SimpleNamespace(
+            x_t=x_t, kind=S.shift_kind(), indexing=indexing, nhwc=(model.dt, model.x_in.data, model.cin_p) if fused else None,
+            time=model.t_in if graph else torch.empty(n, device=dev), ratio=f64(), amt_t=f64(), amt_next=f64(),
+            s=img(), x_in=img(), pred_nchw=img(hist_mode), shifted0=img(hist_mode), x0_hat=img(), d_t=img(), d_next=img(), m_t=img(),
+            m_next=torch.zeros_like(x_t), mi_t=img(indexing and S.rng_mode == "device"), mi_next=img(indexing and S.rng_mode == "device"),
+            mp=torch.empty(n, c, device=dev), diff=torch.zeros_like(x_t))
+        b.draw_z, b.mask_src = self._draws(b)
+        if graph:
+            return self._sample_graph(model, timesteps, b), []
+        hist = {k: torch.zeros(T + 1, n, c, hw, hw, device=dev) for k in HISTORY_NAMES} if hist_mode else None
+
+        def params(i):                          # what mdm_sampler_step_params does for the graph loop
+            S.dev_rng.advance()
+            b.time.fill_(float(timesteps[i]))
+            n_t = S.get_black_area_num_pixels_time(b.time)
+            n_next = S.get_black_area_num_pixels_time(b.time - 1 if i > 0 else b.time)       # :167-170
+            S._check_counts(n_t)
+            b.amt_t.copy_(n_t); b.amt_next.copy_(n_next)
+            if b.kind != 0:
+                torch.index_select(S.ratio_dev, 0, b.time.int() - 1, out=b.ratio)
         for i in range(T - 1, -1, -1):
             slot = T - i
-            S.dev_rng.advance()
-            time = torch.full((n,), float(timesteps[i]), device=dev)
             if self.step_hook is not None:
                 self.step_hook(i, slot, x_t)
             if hist_mode:
                 hist["sample_t"][slot].copy_(x_t)
-            nhwc = (model.dt, model.x_in.data, model.cin_p) if fused else None
-            s, x_in = S.shift_and_perturb(time, x_t, want_nhwc=nhwc)                 # sampler.py:142-143
-            pred, cp, pdt = self._predict(model, x_in, time, fused)                  # :145
-            call("mdm_sampler_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(x_in), s=ptr(s), N=n, C=c, H=hw, W=hw,
-                 pred_nchw=ptr(pred_nchw), shifted0=ptr(shifted0), x0_hat=ptr(x0_hat), stream=stream())   # :146-152
-            next_t = time - 1 if i > 0 else time                                     # :167-170
-            n_t = S.get_black_area_num_pixels_time(time)
-            n_next = S.get_black_area_num_pixels_time(next_t)
-            if dep == "independent":                                                 # :175-181
-                d_t, m_t, _ = S.degrade_independent_base_sampling(n_t, x0_hat, mean_option=a.mean_option, mean_area=a.mean_area, _stream=3)
-                d_next, m_next, _ = S.degrade_independent_base_sampling(n_next, x0_hat, mean_option=a.mean_option, mean_area=a.mean_area, _stream=4)
-            elif dep == "dependent_t":                                               # :191-196
-                d_t, m_t, _, d_next, m_next, _ = S.degrade_dependent_base_sampling(n_t, n_next, x0_hat, mean_option=a.mean_option, mean_area=a.mean_area)
-            else:                                                                    # :184-188
-                m_t = None
-                d_t = S.degrade_with_mask(x0_hat, m_next, mean_option=a.mean_option, mean_area=a.mean_area)
-                d_next, m_next, _ = S.degrade_independent_base_sampling(n_next, x0_hat, mean_option=a.mean_option, mean_area=a.mean_area, _stream=4)
-            if hist_mode:
-                hist["shift"][slot].copy_(s); hist["shifted"][slot].copy_(x_in); hist["mask"][slot].copy_(pred_nchw)
-                hist["shifted_result"][slot].copy_(shifted0); hist["sample_0"][slot].copy_(x0_hat)
+            last = mode == "base_sampling" and i == 0                                  # :204-205 (break before the writes)
+            self._emit_step(b, not last and (i > 0 or mode == "base_sampling"), functools.partial(params, i),      # :206-216
+                            lambda: self._predict(model, b.x_in, b.time, fused))
+            if hist_mode:                       # (the update writes x_t and diff only: these read what the step left)
+                hist["shift"][slot].copy_(b.s); hist["shifted"][slot].copy_(b.x_in); hist["mask"][slot].copy_(b.pred_nchw)
+                hist["shifted_result"][slot].copy_(b.shifted0); hist["sample_0"][slot].copy_(b.x0_hat)
                 if dep in ("independent", "dependent_t"):
-                    hist["degraded_mask"][slot].copy_(m_t); hist["degraded_mask_next"][slot].copy_(m_next)
+                    hist["degraded_mask"][slot].copy_(b.m_t); hist["degraded_mask_next"][slot].copy_(b.m_next)
                 else:
-                    hist["degraded_mask"][slot].copy_(m_next)
-            if mode == "base_sampling" and i == 0:                                   # :204-205 (break before the writes)
+                    hist["degraded_mask"][slot].copy_(b.m_next)
+            if last:
                 break
-            if i > 0 or mode == "base_sampling":                                     # :206-216
-                call("mdm_sampler_update", ptr(d_t), ptr(d_next), ptr(x_t), ptr(diff), int(mode == "base_momentum"), numel, stream())
             if hist_mode:
-                hist["degraded_next_t"][slot].copy_(d_next); hist["degraded_t"][slot].copy_(d_t); hist["difference"][slot].copy_(diff)
-        out_hist = []
-        if hist_mode:
-            out_hist = [hist[k] if hist_mode == "device" else hist[k].cpu() for k in HISTORY_NAMES]
-        return x0_hat, out_hist
+                hist["degraded_next_t"][slot].copy_(b.d_next); hist["degraded_t"][slot].copy_(b.d_t); hist["difference"][slot].copy_(b.diff)
+        return b.x0_hat, [hist[k] if hist_mode == "device" else hist[k].cpu() for k in HISTORY_NAMES] if hist_mode else []

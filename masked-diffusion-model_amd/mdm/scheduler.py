@@ -188,65 +188,107 @@ class Scheduler:
             return 1
         raise UnboundLocalError("select_degrade_pixel")
 
-    def _degrade(self, amount, img, mean_option, mean_area, rng_stream, mask_in=None, want_mask=True, u=None, u_out=None):
-        """Core of the degrade_* methods -> (x_t, mask, mean_pixel[N,C]).  `u`: uniforms already on the device to threshold
-        (replay mode, thresholding) instead of drawing; `u_out`: a list that receives the uniforms this call drew."""
+    def _check_counts(self, amount):
+        if self.args.select_degrade_pixel == "indexing" and amount.dtype.is_floating_point:
+            raise TypeError("indexing needs integer pixel counts (linear/exponential schedules give ratios, D7)")
+
+    def emit_degrade(self, x0, x_t, mean_pixel, *, rng_stream, mean_option, mean_area, amount=None, u=None, mask_in=None,
+                     index_mask=None, mask_out=None):
+        """The one place that launches (or records) mdm_degrade, over the caller's contiguous fp32 device tensors; nothing is
+        allocated, converted or read back.  The keep-mask comes from `mask_in` (degrade_with_mask; a replayed host mask), from
+        `index_mask = (counts, buffer)` -- 'indexing' on the device: mdm_index_mask over `counts` [N] fp64 is issued in front into
+        the caller's `buffer`, which then is the mask source -- or is drawn by the kernel: `amount` [N] fp64 ratios thresholding
+        the uniforms `u` (replay) or Philox stream `rng_stream`.  Outputs: x_t, mean_pixel [N, C], optionally the mask."""
+        N, C, HW = x0.shape[0], x0.shape[1], x0[0, 0].numel()
+        fm, fc = _fill_mode(mean_option, mean_area)
+        rng = ptr(self.dev_rng.dev)
+        if index_mask is not None:
+            counts, mask_in = index_mask
+            call("mdm_index_mask", ptr(counts), 1, rng, rng_stream, N, C, HW, ptr(mask_in), stream())
+        call("mdm_degrade", x0=ptr(x0), u=ptr(u), mask_in=ptr(mask_in), amount=ptr(amount), amount_stride=1, rng=rng,
+             rng_stream=rng_stream, N=N, C=C, HW=HW, Cm=self._check_degrade_args(x0) if mask_in is None else C, fill_mode=fm,
+             fill_const=fc, x_t=ptr(x_t), mask=ptr(mask_out), mean_pixel=ptr(mean_pixel), stream=stream())
+
+    # replay mode: the host draws, in the reference's order and shape.  Each draws for the WHOLE batch and keeps this rank's rows
+    # (`_host_rows`); `*_all` arguments are host values of the whole batch.
+    def _host_full(self, v, n_local):
+        """`v` [n_local] of a SAMPLER step for the whole batch: every sample of a step has the same, a shard repeats its first."""
+        nh, _ = self._host_rows(n_local)
+        return v if nh == n_local else v[:1].expand(nh)
+
+    def host_index_mask(self, counts_all, N, C, H, W):
+        """Serial CPU randperms like scheduler.py:281-282 -> keep-mask [N, C, H, W] on the device."""
+        nh, rows = self._host_rows(N)
+        m = torch.ones(nh, H * W)
+        for i, num in enumerate(counts_all):
+            m[i, torch.randperm(H * W)[:num]] = 0.0
+        return m[rows].reshape(N, 1, H, W).expand(N, C, H, W).contiguous().to(self.device)
+
+    def host_uniforms(self, img):
+        """The uniforms 'thresholding' compares with the ratio (scheduler.py:288/294) -> [N, Cm * HW] on the device."""
+        N, HW = img.shape[0], img[0, 0].numel()
+        nh, rows = self._host_rows(N)
+        return torch.empty(nh, self._check_degrade_args(img) * HW, dtype=torch.float32).uniform_(0.0, 1.0)[rows].contiguous().to(self.device)
+
+    def host_shift_z(self, ratio_all, N, C, H, W):
+        """-> z of mdm_shift on the device (None for 'non_shift'), scheduler.py:620,658,675,694,703-707."""
+        nh, rows = self._host_rows(N)
+        st, mean = self.args.shift_type, float(getattr(self.args, "noise_mean", 0.0))
+        if st == "1-d_constant":
+            z = torch.empty(nh).uniform_(-1.0, 1.0)
+        elif st == "3-d_constant":
+            z = torch.empty(nh, 3, 1, 1).uniform_(-1.0, 1.0)
+        elif st == "noise_reduction":
+            z = torch.empty(nh, 1, H, W).normal_(mean=mean, std=1)
+        elif st == "noise_std_reduction":
+            z = torch.zeros(nh, 3, H, W)
+            for i in range(nh):
+                z[i] = torch.empty(1, 3, H, W).normal_(mean=mean, std=float(ratio_all[i]))
+        elif st == "noise_with_perturbation":
+            torch.empty((nh,) if nh == 1 else (nh, 1, 1, 1)).uniform_(-1.0, 1.0)      # consumed then discarded (D11)
+            z = torch.empty(nh, 3, H, W).normal_(mean=mean, std=1)
+        else:
+            return None
+        return z[rows].to(self.device).contiguous()
+
+    def _degrade(self, amount, img, mean_option, mean_area, rng_stream, mask_in=None, want_mask=True, u=None):
+        """Allocate-then-emit core of the degrade_* methods -> (x_t, mask, mean_pixel[N,C], u).  `u`: uniforms already on the
+        device to threshold (replay mode) instead of drawing; the ones this call used are returned."""
         img = img.to(self.device, torch.float32).contiguous()
         N, C, H, W = img.shape
-        HW = H * W
-        fm, fc = _fill_mode(mean_option, mean_area)
         x_t = torch.empty_like(img)
         mask = torch.empty_like(img) if want_mask else None
         mp = torch.empty(N, C, device=self.device)
-        amt = None
-        Cm = 1
-        if mask_in is None:
-            Cm = self._check_degrade_args(img)
-            sel = self.args.select_degrade_pixel
-            if sel == "indexing":
-                if amount.dtype.is_floating_point:
-                    raise TypeError("indexing needs integer pixel counts (linear/exponential schedules give ratios, D7)")
-                if self.rng_mode == "replay":       # N serial CPU randperms, like scheduler.py:281-282
-                    nh, rows = self._host_rows(N)
-                    counts = amount.cpu()
-                    if nh != N:                     # sharded sampler: every sample of a step has the same count
-                        counts = counts[:1].expand(nh)
-                    m = torch.ones(nh, HW)
-                    for i, num in enumerate(counts):
-                        m[i, torch.randperm(HW)[:num]] = 0.0
-                    mask_in = m[rows].reshape(N, 1, H, W).expand(N, C, H, W).contiguous().to(self.device)
-                else:
-                    mask_in = torch.empty_like(img)
-                    cnt = amount.to(self.device, torch.float64).contiguous()
-                    call("mdm_index_mask", ptr(cnt), 1, ptr(self.dev_rng.dev), rng_stream, N, C, HW, ptr(mask_in), stream())
-            else:
-                amt = amount.to(self.device, torch.float64).contiguous()
-                if self.rng_mode == "replay" and u is None:
-                    nh, rows = self._host_rows(N)
-                    u = torch.empty(nh, Cm * HW, dtype=torch.float32).uniform_(0.0, 1.0)[rows].contiguous().to(self.device)
-                if u_out is not None:
-                    u_out.append(u)
+        _fill_mode(mean_option, mean_area)          # a mean_option that does not run raises before the mask options do
+        if mask_in is not None:
+            src = dict(mask_in=mask_in.to(self.device, torch.float32).contiguous())
         else:
-            mask_in = mask_in.to(self.device, torch.float32).contiguous()
-        call("mdm_degrade", x0=ptr(img), u=ptr(u), mask_in=ptr(mask_in), amount=ptr(amt), amount_stride=1, rng=ptr(self.dev_rng.dev),
-             rng_stream=rng_stream, N=N, C=C, HW=HW, Cm=Cm if mask_in is None else C, fill_mode=fm, fill_const=fc,
-             x_t=ptr(x_t), mask=ptr(mask), mean_pixel=ptr(mp), stream=stream())
-        return x_t, mask, mp
+            self._check_degrade_args(img)
+            self._check_counts(amount)
+            if self.args.select_degrade_pixel != "indexing":
+                if self.rng_mode == "replay" and u is None:
+                    u = self.host_uniforms(img)
+                src = dict(amount=amount.to(self.device, torch.float64).contiguous(), u=u)
+            elif self.rng_mode == "replay":
+                src = dict(mask_in=self.host_index_mask(self._host_full(amount.cpu(), N), N, C, H, W))
+            else:
+                src = dict(index_mask=(amount.to(self.device, torch.float64).contiguous(), torch.empty_like(img)))
+        self.emit_degrade(img, x_t, mp, rng_stream=rng_stream, mean_option=mean_option, mean_area=mean_area, mask_out=mask, **src)
+        return x_t, mask, mp, u
 
     def degrade_training(self, black_area_num, img, mean_option=None, mean_area=None):
-        x_t, masks, mp = self._degrade(black_area_num, img, mean_option, mean_area, rng_stream=1)
+        x_t, masks, mp, _ = self._degrade(black_area_num, img, mean_option, mean_area, rng_stream=1)
         mp4 = mp[:, :, None, None]
         degrade_mask = (1 - masks) * mp4 + masks                         # scheduler.py:320 (visualisation)
         mean_mask = torch.ones_like(x_t) * mp4                            # scheduler.py:321
         return x_t, masks, degrade_mask, mean_mask
 
     def degrade_independent_base_sampling(self, black_area_num_t, img, mean_option=None, mean_area=None, _stream=3):
-        x_t, masks, mp = self._degrade(black_area_num_t, img, mean_option, mean_area, rng_stream=_stream)
+        x_t, masks, mp, _ = self._degrade(black_area_num_t, img, mean_option, mean_area, rng_stream=_stream)
         return x_t, masks, mp[:, :, None, None] * torch.ones_like(x_t)
 
     def degrade_with_mask(self, img, masks, mean_option, mean_area):
-        x_t, _, _ = self._degrade(None, img, mean_option, mean_area, rng_stream=0, mask_in=masks, want_mask=False)
-        return x_t
+        return self._degrade(None, img, mean_option, mean_area, rng_stream=0, mask_in=masks, want_mask=False)[0]
 
     @staticmethod
     def _check_dependent_args(args, mean_option, mean_area):
@@ -264,39 +306,35 @@ class Scheduler:
         ratios -> (degraded_t, mask_t, mean_mask_t, degraded_next, mask_next, mean_mask_next).  Two launches of the degrade
         kernel over the SAME uniforms: the host draw shipped once (replay), or the same Philox stream id (device)."""
         self._check_dependent_args(self.args, mean_option, mean_area)
-        drawn = []
-        x_t, m_t, mp_t = self._degrade(black_area_num_t, img, mean_option, mean_area, rng_stream=_stream, u_out=drawn)
-        x_n, m_n, mp_n = self._degrade(black_area_num_next_t, img, mean_option, mean_area, rng_stream=_stream, u=drawn[0] if drawn else None)
+        x_t, m_t, mp_t, u = self._degrade(black_area_num_t, img, mean_option, mean_area, rng_stream=_stream)
+        x_n, m_n, mp_n, _ = self._degrade(black_area_num_next_t, img, mean_option, mean_area, rng_stream=_stream, u=u)
         ones = torch.ones_like(x_t)
         return x_t, m_t, mp_t[:, :, None, None] * ones, x_n, m_n, mp_n[:, :, None, None] * ones
 
     # ---- shift -------------------------------------------------------------------------
-    def _shift_draws(self, n, C, H, W, ratio_cpu):
-        """Replay-mode host draws in the reference's order/shape -> z tensor for mdm_shift (or None)."""
-        st, mean = self.args.shift_type, float(getattr(self.args, "noise_mean", 0.0))
-        if st == "1-d_constant":
-            return torch.empty(n).uniform_(-1.0, 1.0)
-        if st == "3-d_constant":
-            return torch.empty(n, 3, 1, 1).uniform_(-1.0, 1.0)
-        if st == "noise_reduction":
-            return torch.empty(n, 1, H, W).normal_(mean=mean, std=1)
-        if st == "noise_std_reduction":
-            z = torch.zeros(n, 3, H, W)
-            for i in range(n):
-                z[i] = torch.empty(1, 3, H, W).normal_(mean=mean, std=float(ratio_cpu[i]))
-            return z
-        if st == "noise_with_perturbation":
-            torch.empty((n,) if n == 1 else (n, 1, 1, 1)).uniform_(-1.0, 1.0)      # consumed then discarded (D11)
-            return torch.empty(n, 3, H, W).normal_(mean=mean, std=1)
-        return None
+    def shift_kind(self, mean_shift=True):
+        """`kind` of mdm_shift; the base trainer is the mean-shift one with 'non_shift' (SURVEY 3.2)."""
+        st = self.args.shift_type if mean_shift else "non_shift"
+        if st not in SHIFT_KINDS:
+            raise UnboundLocalError(f"shift_time undefined for shift_type={st!r}")
+        return SHIFT_KINDS[st]
+
+    def emit_shift(self, x_t, s, x_in, *, kind, ratio=None, z=None, nhwc=None):
+        """The one place that launches (or records) mdm_shift: s = z * ratio, x_in = x_t + s over the caller's contiguous fp32
+        device tensors (`ratio` [N] fp64; `z`: replayed host draws, else Philox stream 2), optionally x_in once more as NHWC
+        into `nhwc = (dtype, tensor, Cp)` for the U-Net.  Nothing is allocated, converted or read back."""
+        N, C, H, W = x_t.shape
+        # reference broadcast quirk: [N,*,H,W] * [N] lines up with the LAST axis when W == N (D10)
+        per_col = int(self.reference_quirks and kind in (3, 4) and N == W and N > 1)
+        dt, nh, Cp = nhwc if nhwc is not None else (0, None, 0)
+        call("mdm_shift", x_t=ptr(x_t), z=ptr(z), ratio=ptr(ratio), rng=ptr(self.dev_rng.dev), rng_stream=2, kind=kind,
+             noise_mean=float(getattr(self.args, "noise_mean", 0.0)), per_column=per_col, N=N, C=C, H=H, W=W, s=ptr(s), x_in=ptr(x_in),
+             dtype=dt, x_in_nhwc=ptr(nh), Cp=Cp, stream=stream())
 
     def shift_and_perturb(self, timesteps, x_t, want_nhwc=None):
         """Fused get_schedule_shift_time + perturb_shift: -> (s, x_in); optionally also writes x_in as
         NHWC into `want_nhwc = (dtype, tensor, Cp)` for the U-Net."""
-        st = self.args.shift_type
-        if st not in SHIFT_KINDS:
-            raise UnboundLocalError(f"shift_time undefined for shift_type={st!r}")
-        kind = SHIFT_KINDS[st]
+        kind = self.shift_kind()
         x_t = x_t.to(self.device, torch.float32).contiguous()
         N, C, H, W = x_t.shape
         ratio = z = None
@@ -304,17 +342,9 @@ class Scheduler:
             idx = (timesteps.int() - 1).to(self.device)
             ratio = torch.index_select(self.ratio_dev, 0, idx).contiguous()
             if self.rng_mode == "replay":
-                nh, rows = self._host_rows(N)
-                rc = ratio.cpu()
-                z = self._shift_draws(nh, C, H, W, rc if nh == N else rc[:1].expand(nh))[rows].to(self.device).contiguous()
-        # reference broadcast quirk: [N,*,H,W] * [N] lines up with the LAST axis when W == N (D10)
-        per_col = int(self.reference_quirks and kind in (3, 4) and N == W and N > 1)
-        s = torch.empty_like(x_t)
-        x_in = torch.empty_like(x_t)
-        dt, nh, Cp = want_nhwc if want_nhwc is not None else (0, None, 0)
-        call("mdm_shift", x_t=ptr(x_t), z=ptr(z), ratio=ptr(ratio), rng=ptr(self.dev_rng.dev), rng_stream=2, kind=kind,
-             noise_mean=float(getattr(self.args, "noise_mean", 0.0)), per_column=per_col, N=N, C=C, H=H, W=W, s=ptr(s), x_in=ptr(x_in),
-             dtype=dt, x_in_nhwc=ptr(nh), Cp=Cp, stream=stream())
+                z = self.host_shift_z(self._host_full(ratio.cpu(), N), N, C, H, W)
+        s, x_in = torch.empty_like(x_t), torch.empty_like(x_t)
+        self.emit_shift(x_t, s, x_in, kind=kind, ratio=ratio, z=z, nhwc=want_nhwc)
         return s, x_in
 
     def get_schedule_shift_time(self, timesteps, binarymasks):

@@ -32,7 +32,6 @@ import torch
 
 from . import _lib, ops
 from ._lib import call, ptr, stream
-from .scheduler import SHIFT_KINDS, _fill_mode
 
 
 class LossCell:
@@ -157,24 +156,14 @@ class TrainStep:
         self.force_cut = bool(getattr(args, "cut_step_graph", False))    # single GPU: run the data-parallel (cut) form of the step
 
     # ---- pieces shared by both modes -------------------------------------------------------
-    def _kind(self):
-        st = self.args.shift_type if self.mean_shift else "non_shift"
-        if st not in SHIFT_KINDS:
-            raise UnboundLocalError(f"shift_time undefined for shift_type={st!r}")
-        return SHIFT_KINDS[st]
-
-    def _emit_forward_loss(self, u, z, mask_in, Cm, weights_on):
+    def _emit_forward_loss(self, mask_src, z, weights_on):
+        """`mask_src`: where the degrade's keep-mask comes from, as keywords of `Scheduler.emit_degrade` (none: device Philox)."""
         m, S, a = self.model, self.S, self.args
         N, C, H, W = m.N, m.cin, m.H, m.W
-        fm, fc = _fill_mode(a.mean_option, a.mean_area)
-        kind = self._kind()
-        call("mdm_degrade", x0=ptr(self.x0), u=ptr(u), mask_in=ptr(mask_in), amount=ptr(self.amount), amount_stride=1,
-             rng=ptr(S.dev_rng.dev), rng_stream=1, N=N, C=C, HW=H * W, Cm=C if mask_in is not None else Cm, fill_mode=fm, fill_const=fc,
-             x_t=ptr(self.x_t), mask=ptr(self.mask), mean_pixel=ptr(self.mean_pixel), stream=stream())
-        per_col = int(S.reference_quirks and kind in (3, 4) and N == W and N > 1)
-        call("mdm_shift", x_t=ptr(self.x_t), z=ptr(z), ratio=ptr(self.ratio), rng=ptr(S.dev_rng.dev), rng_stream=2, kind=kind,
-             noise_mean=float(getattr(a, "noise_mean", 0.0)), per_column=per_col, N=N, C=C, H=H, W=W, s=ptr(self.s), x_in=ptr(self.x_in),
-             dtype=m.dt, x_in_nhwc=ptr(m.x_in.data), Cp=m.cin_p, stream=stream())
+        kind = S.shift_kind(self.mean_shift)
+        S.emit_degrade(self.x0, self.x_t, self.mean_pixel, rng_stream=1, mean_option=a.mean_option, mean_area=a.mean_area,
+                       amount=self.amount, mask_out=self.mask, **mask_src)
+        S.emit_shift(self.x_t, self.s, self.x_in, kind=kind, ratio=self.ratio, z=z, nhwc=(m.dt, m.x_in.data, m.cin_p))
         m.forward_plan.run() if _lib._recording is None else _lib._recording.extend(m.forward_plan)
         head = dict(dtype=m.dt, pred=ptr(m.y_out.data), x_in=ptr(self.x_in), s=ptr(self.s) if kind != 0 else None, x0=ptr(self.x0),
                     w=ptr(self.w) if weights_on else None, N=N, C=C, H=H, W=W, Cp=m.cout_p, gscale=1.0 / self.grad_accum,
@@ -228,29 +217,21 @@ class TrainStep:
         weights_on = bool(getattr(a, "loss_weight_use", False))
         if weights_on:
             self.w.copy_(S.get_weight_timesteps(timeindex, a.loss_weight_power_base))
-        u = mask_in = None
-        Cm = 1
+        S._check_counts(amount)
         if a.select_degrade_pixel == "indexing":
-            if amount.dtype.is_floating_point:
-                raise TypeError("indexing needs integer pixel counts (D7)")
             amount_all = S.get_black_area_num_pixels_time(t_all.to(dev)) if nh != N else amount
-            mk = torch.ones(nh, H * W)
-            for i, num in enumerate(amount_all.cpu()):
-                mk[i, torch.randperm(H * W)[:num]] = 0.0                                  # scheduler.py:281-282
-            mask_in = mk[rows].reshape(N, 1, H, W).expand(N, C, H, W).contiguous().to(dev)
+            mask_src = dict(mask_in=S.host_index_mask(amount_all.cpu(), N, C, H, W))
         else:
-            Cm = S._check_degrade_args(self.x0)
             self.amount.copy_(amount)
-            u = torch.empty(nh, Cm * H * W).uniform_(0.0, 1.0)[rows].contiguous().to(dev)  # scheduler.py:288/294
-        kind = self._kind()
+            mask_src = dict(u=S.host_uniforms(self.x0))
         z = None
-        if kind != 0:
+        if S.shift_kind(self.mean_shift) != 0:
             self.ratio.copy_(torch.index_select(S.ratio_dev, 0, (t.int() - 1).to(dev)))
             ratio_all = torch.index_select(S.ratio_list, 0, (t_all.int() - 1).long()) if nh != N else self.ratio.cpu()
-            z = S._shift_draws(nh, C, H, W, ratio_all)[rows].to(dev).contiguous()
+            z = S.host_shift_z(ratio_all, N, C, H, W)
         m.t_in.copy_(t.to(torch.float32))
         self.loss.zero_()                   # (the device path clears it in its first launch, mdm_draw_timesteps)
-        self._emit_forward_loss(u, z, mask_in, Cm, weights_on)
+        self._emit_forward_loss(mask_src, z, weights_on)
         m.store.G.zero_()
         m.run_backward()
         self.last = dict(timeindex=timeindex, t=t)
@@ -307,13 +288,8 @@ class TrainStep:
         call("mdm_draw_timesteps", rng=rng, used=ptr(self.used_dev), n_used=n_used, table=ptr(self.table_dev), wtab=ptr(self.wtab_dev),
              N=N, t_out=ptr(m.t_in), amount_out=ptr(self.amount), weight_out=ptr(self.w), idx_out=ptr(self.tidx),
              table2=ptr(S.ratio_dev), out2=ptr(self.ratio), zero_out=ptr(self.loss.raw), stream=stream())
-        mask_in, Cm = None, 1
-        if a.select_degrade_pixel == "indexing":
-            call("mdm_index_mask", ptr(self.amount), 1, rng, 1, N, C, H * W, ptr(self.mask), stream())
-            mask_in = self.mask
-        else:
-            Cm = S._check_degrade_args(self.x0)
-        self._emit_forward_loss(None, None, mask_in, Cm, self.wtab_dev is not None)
+        mask_src = dict(index_mask=(self.amount, self.mask)) if a.select_degrade_pixel == "indexing" else {}
+        self._emit_forward_loss(mask_src, None, self.wtab_dev is not None)
         m.emit_zero_grad()
 
     def _build_graphs(self):

@@ -297,6 +297,68 @@ def test_scheduler_timesteps_gather_weights(golden):
         mdm.Scheduler(base_args(ddpm_schedule="cosine"), device="cpu").update_ddpm_num_steps(10)
 
 
+def test_each_scheduler_kernel_is_launched_from_one_place():
+    """One statement of every quirk: `Scheduler.emit_shift` / `emit_degrade` hold the only calls of their kernels, `per_column`,
+    the `SHIFT_KINDS` lookup and `_fill_mode` live in scheduler.py alone (DESIGN finding 60)."""
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "masked-diffusion-model_amd", "mdm")
+    text = {f: open(os.path.join(pkg, f)).read() for f in sorted(os.listdir(pkg)) if f.endswith(".py")}
+    where = lambda needle: {f: t.count(needle) for f, t in text.items() if needle in t}
+    for needle in ('"mdm_shift"', '"mdm_degrade"', '"mdm_index_mask"', "per_column=", "SHIFT_KINDS["):
+        assert where(needle) == {"scheduler.py": 1}, (needle, where(needle))
+    assert set(where("_fill_mode(")) == {"scheduler.py"}
+    assert "_shift_draws" not in "".join(text.values()) and "def _kind" not in text["train_step.py"]
+
+
+@pytest.mark.parametrize("rows", [None, (1, 3, 4)])
+def test_scheduler_host_draws_consume_the_generator_like_the_reference(rows):
+    """The three replay-mode helpers draw for the WHOLE batch in the reference's order and shape and keep this rank's rows:
+    'noise_with_perturbation' consumes one uniform draw that it discards (D11), 'noise_std_reduction' draws image by image."""
+    import mdm
+    n = 4
+    lo, hi = (0, n) if rows is None else rows[:2]
+    ratio = torch.linspace(0.1, 0.9, n, dtype=torch.float64)
+
+    def sched(**kw):
+        s = mdm.Scheduler(base_args(data_size=4, noise_mean=0.25, **kw), device="cpu")
+        s.replay_rows = rows
+        return s
+    s = sched(shift_type="noise_with_perturbation")
+    torch.manual_seed(7)
+    z = s.host_shift_z(ratio, hi - lo, 3, 4, 4)
+    torch.manual_seed(7)
+    torch.empty(n, 1, 1, 1).uniform_(-1.0, 1.0)
+    want = torch.empty(n, 3, 4, 4).normal_(mean=0.25, std=1)
+    assert torch.equal(z, want[lo:hi]) and z.is_contiguous()
+    after = torch.get_rng_state()
+    torch.manual_seed(7)
+    s.host_shift_z(ratio, hi - lo, 3, 4, 4)
+    assert torch.equal(torch.get_rng_state(), after)
+
+    s = sched(shift_type="noise_std_reduction")
+    torch.manual_seed(8)
+    z = s.host_shift_z(ratio, hi - lo, 3, 4, 4)
+    torch.manual_seed(8)
+    want = torch.stack([torch.empty(1, 3, 4, 4).normal_(mean=0.25, std=float(r))[0] for r in ratio])
+    assert torch.equal(z, want[lo:hi])
+    assert sched(shift_type="non_shift").host_shift_z(ratio, hi - lo, 3, 4, 4) is None
+
+    s = sched(degrade_channel="3-channel")
+    torch.manual_seed(9)
+    u = s.host_uniforms(torch.zeros(hi - lo, 3, 4, 4))
+    torch.manual_seed(9)
+    assert torch.equal(u, torch.empty(n, 3 * 16).uniform_(0.0, 1.0)[lo:hi])
+
+    counts = torch.tensor([0, 5, 16, 9])
+    torch.manual_seed(10)
+    m = s.host_index_mask(counts, hi - lo, 3, 4, 4)
+    torch.manual_seed(10)
+    perms = [torch.randperm(16) for _ in range(n)]
+    assert m.shape == (hi - lo, 3, 4, 4) and torch.equal((m[:, 0] == 0).flatten(1).sum(1), counts[lo:hi])
+    for k, i in enumerate(range(lo, hi)):
+        assert set(torch.nonzero(m[k, 1].flatten() == 0).flatten().tolist()) == set(perms[i][:counts[i]].tolist())
+    assert torch.equal(s._host_full(counts[lo:hi], hi - lo), counts[lo:hi] if rows is None else counts[lo:lo + 1].expand(n))
+
+
 def test_state_dict_grammar_and_layout_roundtrip():
     from mdm.unet import ParamStore, UNet, unet6_config
     from oracle.unet_ref import param_shapes, random_params, unet6_config as ref_cfg

@@ -392,20 +392,31 @@ def test_sampler_bf16_and_history_off(golden):
     assert rel < 5e-2, rel
 
 
-@pytest.mark.parametrize("dep,mode,sel,sched", [("independent", "base_momentum", "thresholding", "linear"),
-                                               ("dependent_prev", "base_sampling", "thresholding", "linear"),
-                                               ("independent", "base_sampling", "indexing", "log")])
-def test_sampler_one_graph_per_step_equals_the_host_driven_loop(dep, mode, sel, sched, monkeypatch):
+@pytest.mark.parametrize("dep,mode,sel,sched,more", [
+    pytest.param("independent", "base_momentum", "thresholding", "linear", {}, id="independent-base_momentum-thresholding-linear"),
+    pytest.param("dependent_prev", "base_sampling", "thresholding", "linear", {}, id="dependent_prev-base_sampling-thresholding-linear"),
+    pytest.param("independent", "base_sampling", "indexing", "log", {}, id="independent-base_sampling-indexing-log"),
+    # (exponential: ratios 0.1 .. 1 -- on the linear schedule's 0.001 most images have no degraded pixel, whose mean is NaN)
+    pytest.param("dependent_t", "base_momentum", "thresholding", "exponential", dict(mean_option="degraded_area"), id="dependent_t-degraded_area"),
+    # sample_num == data_size: the shift ratio lines up with the image COLUMN (D10, per_column = 1), kind 3
+    pytest.param("dependent_prev", "base_momentum", "thresholding", "linear", dict(sample_num=16, shift_type="noise_reduction"),
+                 id="sample_num_eq_data_size-noise_reduction")])
+def test_sampler_one_graph_per_step_equals_the_host_driven_loop(dep, mode, sel, sched, more, monkeypatch):
     """Device RNG, history off: the reverse step as ONE hipGraph with device-side step parameters
-    (mdm_sampler_step_params) reproduces the host-driven loop (same Philox offsets, same kernels)."""
+    (mdm_sampler_step_params) reproduces the host-driven loop bit for bit: both run `Sampler._emit_step` over the same buffers,
+    so they launch the same kernels with the same Philox offsets.  (Before the two loops shared that body this test asked for
+    rel < 1e-3; the loops of that tree already agreed bit for bit on its three cases, profiles/r15_path_parity.md.)"""
     import mdm
     from oracle.unet_ref import random_params
     outs = []
+    n = more.get("sample_num", 4)
     for flag in (False, True):
-        model = mdm.UNet(TINY, N=4, H=16, W=16, dtype=1, params=random_params(TINY)).eval()
+        model = mdm.UNet(TINY, N=n, H=16, W=16, dtype=1, params=random_params(TINY)).eval()
         a = base_args(data_size=16, ddpm_schedule=sched, ddpm_num_steps=8, select_degrade_pixel=sel, degrade_channel="1-channel",
                       shift_type="noise_with_perturbation", sampling_mask_dependency=dep, momentum_adaptive=mode, sample_num=4,
                       sample_latent_shape="uniform", sample_history=False, rng_mode="device", seed=5, sampler_graph=flag)
+        for k, v in more.items():
+            setattr(a, k, v)
         s = mdm.Scheduler(a)
         s.update_ddpm_num_steps(8)
         smp = mdm.Sampler(None, a, s, [None] * 3)
@@ -413,9 +424,73 @@ def test_sampler_one_graph_per_step_equals_the_host_driven_loop(dep, mode, sel, 
         x0, hist = smp.sample(model, s.get_timesteps_epoch(0, 1))
         torch.cuda.synchronize()
         assert hist == [] and bool(torch.isfinite(x0).all())
+        assert hasattr(smp, "_graph_keep") == flag              # the graph loop ran exactly where it was asked for
         outs.append(x0.cpu().numpy().copy())
     rel = np.linalg.norm(outs[0] - outs[1]) / (np.linalg.norm(outs[0]) + 1e-12)
-    assert rel < 1e-3, rel
+    print(f"graph loop vs host-driven loop: rel {rel:.3e}, max |diff| {np.abs(outs[0] - outs[1]).max():.3e}")
+    assert np.array_equal(outs[0], outs[1]), rel
+
+
+@pytest.mark.parametrize("sel", ["thresholding", "indexing"])
+@pytest.mark.parametrize("rng_mode", ["device", "replay"])
+def test_scheduler_public_methods_equal_the_emitters_on_caller_owned_buffers(rng_mode, sel):
+    """`degrade_independent_base_sampling`, `degrade_with_mask`, `degrade_dependent_base_sampling` and `shift_and_perturb` allocate
+    and then call `Scheduler.emit_degrade` / `emit_shift`: the emitters over buffers the caller owns give the same bits from the
+    same random state (host generator reseeded in replay mode; the device Philox offset only moves with `dev_rng.advance()`)."""
+    from mdm import Scheduler
+    N, C, H = 2, 3, 8
+    a = base_args(data_size=H, ddpm_schedule="log" if sel == "indexing" else "linear", ddpm_num_steps=10, select_degrade_pixel=sel,
+                  degrade_channel="3-channel", shift_type="noise_with_perturbation", noise_mean=0.25, rng_mode=rng_mode, seed=9)
+    s = Scheduler(a)
+    T_ = s.update_ddpm_num_steps(10)
+    s.dev_rng.advance()
+    img = (torch.rand(N, C, H, H, generator=torch.Generator().manual_seed(3)) * 2 - 1).cuda()
+    t = torch.full((N,), float(T_ // 2)).cuda()
+    n_t, n_next = s.get_black_area_num_pixels_time(t), s.get_black_area_num_pixels_time(t - 1)
+    mo, ma = "degraded_area", "channel-wise"
+    new = lambda: torch.full_like(img, float("nan"))
+    f64 = lambda v: v.to(torch.float64).contiguous()
+
+    def mask_src(amount):           # the emitter's keywords for one drawn mask, as a caller of the emitter makes them
+        if sel == "indexing":
+            if rng_mode == "replay":
+                return dict(mask_in=s.host_index_mask(amount.cpu(), N, C, H, H))
+            return dict(index_mask=(f64(amount), new()))
+        return dict(amount=f64(amount), u=s.host_uniforms(img) if rng_mode == "replay" else None)
+
+    def emit(rng_stream, mask_out=True, **src):
+        x_t, m, mp = new(), new() if mask_out else None, torch.full((N, C), float("nan"), device="cuda")
+        s.emit_degrade(img, x_t, mp, rng_stream=rng_stream, mean_option=mo, mean_area=ma, mask_out=m, **src)
+        return x_t, m, mp[:, :, None, None] * torch.ones_like(x_t)
+
+    seed_all(61)
+    want = s.degrade_independent_base_sampling(n_t, img, mean_option=mo, mean_area=ma)
+    seed_all(61)
+    got = emit(3, **mask_src(n_t))
+    assert all(torch.equal(w, g) for w, g in zip(want, got)) and float((want[1] == 0).sum()) > 0
+
+    assert torch.equal(s.degrade_with_mask(img, want[1], mo, ma), emit(0, mask_out=False, mask_in=want[1])[0])
+
+    if sel == "indexing":           # no 'indexing' branch upstream (D5)
+        with pytest.raises(UnboundLocalError):
+            s.degrade_dependent_base_sampling(n_t, n_next, img, mo, ma)
+    else:
+        seed_all(62)
+        want = s.degrade_dependent_base_sampling(n_t, n_next, img, mo, ma)
+        seed_all(62)
+        src = mask_src(n_t)             # ONE draw, thresholded at both ratios
+        got = emit(3, **src) + emit(3, **dict(src, amount=f64(n_next)))
+        assert len(want) == len(got) == 6 and all(torch.equal(w, g) for w, g in zip(want, got))
+        assert bool((want[1] <= want[4]).all())
+
+    seed_all(63)
+    want_s, want_x = s.shift_and_perturb(t, img)
+    seed_all(63)
+    ratio = torch.index_select(s.ratio_dev, 0, t.int() - 1)
+    z = s.host_shift_z(ratio.cpu(), N, C, H, H) if rng_mode == "replay" else None
+    got_s, got_x = new(), new()
+    s.emit_shift(img, got_s, got_x, kind=s.shift_kind(), ratio=ratio, z=z)
+    assert torch.equal(want_s, got_s) and torch.equal(want_x, got_x) and float(want_s.abs().max()) > 0
 
 
 # --------------------------------------------------------------------------------- round-2 fixtures
