@@ -518,29 +518,28 @@ int mdm_unit_rows(const float* x, float* y, int R, int D, float eps, void* strea
 int mdm_col_argmax(const float* S, int M, int B, float* val, int64_t* idx, void* stream);
 
 /* ------------------------------------------------------------------------- *
- * Optimizer: global-norm clip + AdamW (or SGD / Adam, mdm_optim_update) + EMA + bf16 weight shadow in one pass over
- * flat fp32 buffers (trainer_masked_mean_shift.py:163-172, main_train_masked.py:134-141).
- *   hp (device, 8 floats): lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ema_decay
+ * Optimizer: global-norm clip + SGD / Adam / AdamW + EMA + bf16 weight shadow in one pass over flat fp32 buffers.  Replaces
+ * accelerator.clip_grad_norm_ + torch.optim.{SGD, Adam, AdamW}.step + EMAModel.step (trainer_masked_mean_shift.py:163-172;
+ * `--optim sgd | adam | adamw`, main_train_masked.py:134-141, 375).
  *   mdm_sqnorm stores sum(g^2) to *out (two-stage, fixed summation order: bit-identical on every rank).
- *   clip_coef = min(1, max_norm / (sqrt(*sqnorm) * gscale_inv + 1e-6)); g is multiplied by gmul first
- *   (gmul = 1/world for the DP mean).  ema / shadow may be NULL.
+ *   mdm_optim_update: coef = gmul min(1, max_norm / (sqrt(*sqnorm) gmul + 1e-6)) -- gmul alone when max_norm <= 0, and *sqnorm is
+ *   then not read -- (gmul = 1/world for the DP mean), then per element, in torch's order of operations:
+ *     kind  optimizer           buf0, buf1            update
+ *     0     SGD, momentum == 0  NULL, NULL            d = coef g + wd p;  p -= lr d
+ *     1     SGD with momentum   momentum buffer, NULL d as above;  buf = buf_decay buf + g_scale d;
+ *                                                     p -= lr (nesterov ? d + momentum buf : buf)
+ *     2     Adam                exp_avg, exp_avg_sq   d as above (COUPLED decay: it enters both moments);
+ *                                                     m = beta1 m + (1 - beta1) d;  v = beta2 v + (1 - beta2) d d;
+ *                                                     p -= (lr / bias_corr1) m / (sqrt(v) / sqrt(bias_corr2) + eps)
+ *     3     AdamW               exp_avg, exp_avg_sq   p *= 1 - lr wd (DECOUPLED decay);  d = coef g;  then m, v and p as kind 2
+ *   then ema -= (1 - ema_decay)(ema - p) and shadow = bf16(p), each where its pointer is not NULL.
+ *   hp (device, 8 floats)  kinds 0, 1:  lr, momentum, buf_decay, g_scale, weight_decay, nesterov (0 | 1), unused, ema_decay --
+ *                                       (buf_decay, g_scale) = (0, 1) on the optimizer's first step (torch: buf = d), (momentum,
+ *                                       1 - dampening) afterwards: the block is device memory, so a captured graph follows the rule
+ *                          kinds 2, 3:  lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ema_decay
+ *   every buffer 16-byte aligned; any n (kinds 0..2 take 8 elements per lane and handle the n % 8 behind them, kind 3 takes one).
  * ------------------------------------------------------------------------- */
 int mdm_sqnorm(const float* g, int64_t n, float* out, void* stream);
-int mdm_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, void* shadow_bf16,
-                  int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream);
-/* The reference's other two optimizers (`--optim sgd | adam`, main_train_masked.py:134-141, 375: `optim.SGD(params, lr=lr)`,
- * `optim.Adam(params, lr=lr)`) in the same sweep: clip coefficient from *sqnorm, gmul, update, EMA, bf16 shadow.  Replaces
- * accelerator.clip_grad_norm_ + torch.optim.SGD.step / torch.optim.Adam.step + EMAModel.step (trainer_masked_mean_shift.py:163-172).
- *   kind 0  SGD with momentum == 0: buf0 = buf1 = NULL, no state            d = coef g + wd p;  p -= lr d
- *   kind 1  SGD with momentum: buf0 = momentum buffer                       buf = buf_decay buf + g_scale d;
- *                                                                           p -= lr (nesterov ? d + momentum buf : buf)
- *   kind 2  Adam: buf0 = exp_avg, buf1 = exp_avg_sq; the weight decay is COUPLED (d = coef g + wd p enters both moments),
- *           then mdm_adamw_ema's moment updates, bias corrections and step
- *   hp (device, 8 floats)  SGD:  lr, momentum, buf_decay, g_scale, weight_decay, nesterov (0 | 1), unused, ema_decay --
- *                                (buf_decay, g_scale) = (0, 1) on the optimizer's first step (torch: buf = d), (momentum, 1 - dampening)
- *                                afterwards: the block is device memory, so a captured graph follows the rule
- *                          Adam: mdm_adamw_ema's block
- *   every buffer 16-byte aligned; any n (a tail of n % 8 elements is handled); ema / shadow may be NULL. */
 int mdm_optim_update(int kind, float* p, const float* g, float* buf0, float* buf1, float* ema, void* shadow_bf16,
                      int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream);
 int mdm_cast_bf16(const float* src, void* dst, int64_t n, void* stream);

@@ -37,42 +37,21 @@ __global__ __launch_bounds__(256) void sqnorm_final_kernel(float* out, int nblk)
     if (threadIdx.x == 0) *out = (part[0] + part[1]) + (part[2] + part[3]);      // stored: no zeroing launch in front
 }
 
-// hp: lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ema_decay
-__global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, float* ema, bf16_t* shadow,
-                                                    int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul) {
-    const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4], bc1 = hp[5], bc2 = hp[6], ed = hp[7];
-    float coef = gmul;
-    if (max_norm > 0.f) {
-        float norm = sqrtf(*sqnorm) * gmul;
-        float c = max_norm / (norm + 1e-6f);          // torch.nn.utils.clip_grad_norm_
-        if (c < 1.f) coef *= c;
-    }
-    const float step = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float gi = g[i] * coef;
-        float pi = p[i] * (1.f - lr * wd);            // decoupled weight decay first (torch AdamW)
-        float mi = b1 * m[i] + (1.f - b1) * gi;
-        float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        pi -= step * mi / denom;
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (ema) { float e = ema[i]; ema[i] = e - (1.f - ed) * (e - pi); }
-        if (shadow) shadow[i] = f2bf(pi);
-    }
-}
-
-// SGD and Adam (mdm_optim_update): the same sweep as adamw_kernel -- clip coefficient, gmul, update, EMA, bf16 shadow -- for the two
-// other optimizers of the reference's `--optim` switch, 8 elements per lane and iteration: two 16-byte loads per stream, two 16-byte
-// stores per fp32 stream and one 16-byte store of the shadow.  Bytes per parameter, EMA and shadow aside (+8 B and +2 B):
-//   KIND 0  SGD, momentum == 0: no state at all               8 B read +  4 B written
-//   KIND 1  SGD with a momentum buffer (s0)                   12 B read +  8 B written
-//   KIND 2  Adam, coupled (L2) weight decay (s0 = m, s1 = v)  16 B read + 12 B written
+// The one update sweep (mdm_optim_update): clip coefficient, gmul, update, EMA, bf16 shadow.  Bytes per parameter, EMA and shadow
+// aside (+8 B and +2 B), and elements per lane and iteration (W):
+//   KIND 0  SGD, momentum == 0: no state at all                 8 B read +  4 B written   W = 8
+//   KIND 1  SGD with a momentum buffer (s0)                     12 B read +  8 B written   W = 8
+//   KIND 2  Adam, coupled (L2) weight decay (s0 = m, s1 = v)    16 B read + 12 B written   W = 8
+//   KIND 3  AdamW, decoupled weight decay (s0 = m, s1 = v)      16 B read + 12 B written   W = 1
+// W = 8 is two 16-byte loads per stream, all issued up front, two 16-byte stores per fp32 stream and one 16-byte store of the shadow.
+// W = 1 is scalar loads and stores, the EMA read only behind the update's stores: the four-stream sweep of the default optimizer
+// runs 4 % faster that way than at W = 8, and 5 % slower with the EMA's load up front (profiles/r16_optim_one_kernel.md).
 // hp (device, 8 floats):
-//   SGD   lr, momentum, buf_decay, g_scale, weight_decay, nesterov (0 | 1), -, ema_decay
-//         buf = buf_decay buf + g_scale d: the host sends (0, 1) on the optimizer's first step (torch: buf = d) and (momentum,
-//         1 - dampening) afterwards -- the rule lives in the block, not in a kernel argument, so a captured graph replays it
-//   Adam  adamw_kernel's block: lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ema_decay
-enum { OPT_SGD = 0, OPT_SGD_MOMENTUM = 1, OPT_ADAM = 2 };
+//   SGD       lr, momentum, buf_decay, g_scale, weight_decay, nesterov (0 | 1), -, ema_decay
+//             buf = buf_decay buf + g_scale d: the host sends (0, 1) on the optimizer's first step (torch: buf = d) and (momentum,
+//             1 - dampening) afterwards -- the rule lives in the block, not in a kernel argument, so a captured graph replays it
+//   Adam[W]   lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, ema_decay
+enum { OPT_SGD = 0, OPT_SGD_MOMENTUM = 1, OPT_ADAM = 2, OPT_ADAMW = 3 };
 
 struct OptimConsts {
     float coef, lr, wd, ed, a, b, c, d, e;      // a..e: per kind, see optim_consts
@@ -87,7 +66,7 @@ __device__ __forceinline__ OptimConsts optim_consts(const float* hp, const float
         if (c < 1.f) k.coef *= c;
     }
     k.lr = hp[0]; k.wd = hp[4]; k.ed = hp[7];
-    if (KIND == OPT_ADAM) {
+    if (KIND >= OPT_ADAM) {
         k.a = hp[1]; k.b = hp[2]; k.c = hp[3];        // beta1, beta2, eps
         k.d = hp[0] / hp[5]; k.e = rsqrtf(hp[6]);     // lr / bias_corr1, 1 / sqrt(bias_corr2)
     } else {
@@ -95,62 +74,91 @@ __device__ __forceinline__ OptimConsts optim_consts(const float* hp, const float
     }
     return k;
 }
-// one element: p, s0, s1 updated in place (torch's single-tensor SGD / Adam, in their order of operations)
+// one element: p, s0, s1 updated in place (torch's single-tensor SGD / Adam / AdamW, in their order of operations).  Which product
+// of a sum of two the compiler fuses is its choice, and it moves with the code around the expression: kinds 0..2 are left to it and
+// held to their bits by scripts/optim_parity.py; AdamW's two sums, which it fused the other way round when the EMA's load moved,
+// are spelled out as they have always been rounded.
 template <int KIND>
 __device__ __forceinline__ void optim_elem(const OptimConsts& k, float& p, float g, float& s0, float& s1) {
     float d = g * k.coef;
-    d += k.wd * p;                                    // coupled (L2) decay: part of the gradient, unlike AdamW's
+    if (KIND == OPT_ADAMW) p *= 1.f - k.lr * k.wd;    // decoupled decay: the weight shrinks first, the moments never see it
+    else d += k.wd * p;                               // coupled (L2) decay: part of the gradient
     if (KIND == OPT_SGD_MOMENTUM) {
         s0 = k.b * s0 + k.c * d;
         d = k.d != 0.f ? d + k.a * s0 : s0;           // nesterov reads the NEW buffer
     }
-    if (KIND == OPT_ADAM) {
-        s0 = k.a * s0 + (1.f - k.a) * d;
-        s1 = k.b * s1 + (1.f - k.b) * d * d;
+    if (KIND >= OPT_ADAM) {
+        if (KIND == OPT_ADAM) {
+            s0 = k.a * s0 + (1.f - k.a) * d;
+            s1 = k.b * s1 + (1.f - k.b) * d * d;
+        } else {
+            s0 = __fmaf_rn(1.f - k.a, d, k.a * s0);
+            s1 = __fmaf_rn(d, (1.f - k.b) * d, k.b * s1);
+        }
         float denom = sqrtf(s1) * k.e + k.c;
         p -= k.d * s0 / denom;
     } else {
         p -= k.lr * d;
     }
 }
-template <int KIND>
+// W consecutive elements of one stream, in registers and to or from memory
+__device__ __forceinline__ void loadw(float8& r, const float* p) { r = load8(p); }
+__device__ __forceinline__ void loadw(float& r, const float* p) { r = *p; }
+__device__ __forceinline__ void storew(float* p, const float8& v) { store8(p, v); }
+__device__ __forceinline__ void storew(float* p, float v) { *p = v; }
+__device__ __forceinline__ void storew(bf16_t* p, const float8& v) { store8(p, v); }
+__device__ __forceinline__ void storew(bf16_t* p, float v) { *p = f2bf(v); }
+
+template <int KIND, typename V>
+__device__ __forceinline__ void store_state(float* p, float* s0, float* s1, int64_t o, const V& pv, const V& a, const V& b) {
+    storew(p + o, pv);
+    if (KIND >= OPT_SGD_MOMENTUM) storew(s0 + o, a);
+    if (KIND >= OPT_ADAM) storew(s1 + o, b);
+}
+
+template <int KIND, int W>
 __global__ __launch_bounds__(256) void optim_update_kernel(float* p, const float* g, float* s0, float* s1, float* ema, bf16_t* shadow,
                                                            int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul) {
+    static_assert(W == 1 || W == 8, "one scalar or two 16-byte words per stream");
+    using V = std::conditional_t<W == 8, float8, float>;
     const OptimConsts k = optim_consts<KIND>(hp, sqnorm, max_norm, gmul);
     const float ew = 1.f - k.ed;
-    const int64_t n8 = n >> 3;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
-        const int64_t o = i * 8;
-        float8 pv = load8(p + o), a = {}, b = {}, ev = {};
-        const float8 gv = load8(g + o);
-        if (KIND >= OPT_SGD_MOMENTUM) a = load8(s0 + o);
-        if (KIND == OPT_ADAM) b = load8(s1 + o);
-        if (ema) ev = load8(ema + o);
+    const int64_t nw = n / W;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nw; i += (int64_t)gridDim.x * 256) {
+        const int64_t o = i * W;
+        V pv, gv, a = {}, b = {}, ev = {};
+        loadw(pv, p + o);
+        loadw(gv, g + o);
+        if (KIND >= OPT_SGD_MOMENTUM) loadw(a, s0 + o);
+        if (KIND >= OPT_ADAM) loadw(b, s1 + o);
+        if (W > 1 && ema) loadw(ev, ema + o);
         float *pf = reinterpret_cast<float*>(&pv), *af = reinterpret_cast<float*>(&a), *bf = reinterpret_cast<float*>(&b);
         float* ef = reinterpret_cast<float*>(&ev);
         const float* gf = reinterpret_cast<const float*>(&gv);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) optim_elem<KIND>(k, pf[j], gf[j], af[j], bf[j]);
+        for (int j = 0; j < W; ++j) optim_elem<KIND>(k, pf[j], gf[j], af[j], bf[j]);
+        if (W == 1) {                              // one element per lane: the EMA is read behind the update's stores
+            store_state<KIND>(p, s0, s1, o, pv, a, b);
+            if (ema) loadw(ev, ema + o);
+        }
         if (ema) {
 #pragma unroll
-            for (int j = 0; j < 8; ++j) ef[j] = ef[j] - ew * (ef[j] - pf[j]);
+            for (int j = 0; j < W; ++j) ef[j] = ef[j] - ew * (ef[j] - pf[j]);
         }
-        store8(p + o, pv);
-        if (KIND >= OPT_SGD_MOMENTUM) store8(s0 + o, a);
-        if (KIND == OPT_ADAM) store8(s1 + o, b);
-        if (ema) store8(ema + o, ev);
-        if (shadow) store8(shadow + o, pv);
+        if (W > 1) store_state<KIND>(p, s0, s1, o, pv, a, b);
+        if (ema) storew(ema + o, ev);
+        if (shadow) storew(shadow + o, pv);
     }
-    // the n % 8 elements behind the last whole group (the parameter store's sizes are multiples of 8: plain tensors only)
-    const int64_t t = n8 * 8 + threadIdx.x;
-    if (blockIdx.x == 0 && t < n) {
+    // the n % W elements behind the last whole group (the parameter store's sizes are multiples of 8: plain tensors only)
+    const int64_t t = nw * W + threadIdx.x;
+    if (W > 1 && blockIdx.x == 0 && t < n) {
         float pi = p[t], a = 0.f, b = 0.f;
         if (KIND >= OPT_SGD_MOMENTUM) a = s0[t];
-        if (KIND == OPT_ADAM) b = s1[t];
+        if (KIND >= OPT_ADAM) b = s1[t];
         optim_elem<KIND>(k, pi, g[t], a, b);
         p[t] = pi;
         if (KIND >= OPT_SGD_MOMENTUM) s0[t] = a;
-        if (KIND == OPT_ADAM) s1[t] = b;
+        if (KIND >= OPT_ADAM) s1[t] = b;
         if (ema) { float e = ema[t]; ema[t] = e - ew * (e - pi); }
         if (shadow) shadow[t] = f2bf(pi);
     }
@@ -190,6 +198,14 @@ __global__ __launch_bounds__(256) void transpose_shadow_bf16_kernel(const bf16_t
     }
 }
 
+// One 32-bit word of each half of the split shadow: element xa of a block's first 16 in the low 16 bits, its partner xb of the second
+// 16 in the high ones -- `hi` = their bf16 roundings, `lo` = the bf16 roundings of what that left.
+__device__ __forceinline__ void split_pair(float xa, float xb, uint32_t& hi, uint32_t& lo) {
+    const bf16_t h0 = f2bf(xa), h1 = f2bf(xb);
+    hi = (uint32_t)h0 | ((uint32_t)h1 << 16);
+    lo = (uint32_t)f2bf(xa - bf2f(h0)) | ((uint32_t)f2bf(xb - bf2f(h1)) << 16);
+}
+
 // The split shadow of fp32 filters (mdm_gemm_desc.B_split; conv_halo_body<..., SPLIT>): per 32-element block, chunk g = 8 bf16 hi
 // halves of elements {4g..4g+3, 16+4g..16+4g+3} -- dword k = (element 4g+k, element 16+4g+k) --, chunk 4+g = their lo halves in the same
 // order.  One thread per (block, g): two 16-byte loads, two stores.
@@ -202,11 +218,7 @@ __global__ __launch_bounds__(256) void split_shadow_kernel(const float* P, float
         const float xa[4] = {a.x, a.y, a.z, a.w}, xb[4] = {b.x, b.y, b.z, b.w};
         uint32_t h[4], l[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {            // dword k: element k of the first chunk (low half) | element k of the second (high half)
-            const bf16_t h0 = f2bf(xa[k]), h1 = f2bf(xb[k]);
-            h[k] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-            l[k] = (uint32_t)f2bf(xa[k] - bf2f(h0)) | ((uint32_t)f2bf(xb[k] - bf2f(h1)) << 16);
-        }
+        for (int k = 0; k < 4; ++k) split_pair(xa[k], xb[k], h[k], l[k]);
         *reinterpret_cast<uint4*>(Ps + base) = make_uint4(h[0], h[1], h[2], h[3]);
         *reinterpret_cast<uint4*>(Ps + base + 16) = make_uint4(l[0], l[1], l[2], l[3]);
     }
@@ -226,12 +238,7 @@ __global__ __launch_bounds__(256) void split_shadow_t_kernel(const float* P, flo
         const float* src = P + off + (taps - 1 - tp) * co_n * ci_n + co * ci_n + ci;
         uint32_t h[4], l[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float xa = src[k * ci_n], xb = src[(16 + k) * ci_n];
-            const bf16_t h0 = f2bf(xa), h1 = f2bf(xb);
-            h[k] = (uint32_t)h0 | ((uint32_t)h1 << 16);
-            l[k] = (uint32_t)f2bf(xa - bf2f(h0)) | ((uint32_t)f2bf(xb - bf2f(h1)) << 16);
-        }
+        for (int k = 0; k < 4; ++k) split_pair(src[k * ci_n], src[(16 + k) * ci_n], h[k], l[k]);
         float* dst = PsT + off + tp * co_n * ci_n + ci * co_n + co;
         *reinterpret_cast<uint4*>(dst) = make_uint4(h[0], h[1], h[2], h[3]);
         *reinterpret_cast<uint4*>(dst + 16) = make_uint4(l[0], l[1], l[2], l[3]);
@@ -266,32 +273,27 @@ extern "C" int mdm_sqnorm(const float* g, int64_t n, float* out, void* stream) {
     hipLaunchKernelGGL(sqnorm_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, out, nb);
     return launch_status("sqnorm");
 }
-extern "C" int mdm_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, void* shadow_bf16, int64_t n,
-                             const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream) {
-    MDM_REQUIRE(p && g && m && v && hp && n > 0, "adamw: bad arguments");
-    MDM_REQUIRE(max_norm <= 0.f || sqnorm, "adamw: clipping needs the squared norm");
-    hipLaunchKernelGGL(adamw_kernel, dim3(ogrid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, (bf16_t*)shadow_bf16, n, hp,
-                       sqnorm, max_norm, gmul);
-    return launch_status("adamw");
-}
 extern "C" int mdm_optim_update(int kind, float* p, const float* g, float* buf0, float* buf1, float* ema, void* shadow_bf16, int64_t n,
                                 const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream) {
-    MDM_REQUIRE(kind == OPT_SGD || kind == OPT_SGD_MOMENTUM || kind == OPT_ADAM, "optim_update: kind must be 0 (SGD), 1 (SGD + momentum) or 2 (Adam)");
+    MDM_REQUIRE(kind >= OPT_SGD && kind <= OPT_ADAMW, "optim_update: kind must be 0 (SGD), 1 (SGD + momentum), 2 (Adam) or 3 (AdamW)");
     MDM_REQUIRE(p && g && hp && n > 0, "optim_update: bad arguments");
     MDM_REQUIRE(kind == OPT_SGD || buf0, "optim_update: this kind needs its first state buffer");
-    MDM_REQUIRE(kind != OPT_ADAM || buf1, "optim_update: Adam needs both state buffers");
+    MDM_REQUIRE(kind < OPT_ADAM || buf1, "optim_update: Adam and AdamW need both state buffers");
     MDM_REQUIRE(max_norm <= 0.f || sqnorm, "optim_update: clipping needs the squared norm");
     MDM_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf0 | (uintptr_t)buf1 | (uintptr_t)ema | (uintptr_t)shadow_bf16) & 15) == 0,
                 "optim_update: buffers must be 16-byte aligned");
-    const dim3 grid(ogrid(n / 8)), block(256);
+    const dim3 block(256);
     hipStream_t st = (hipStream_t)stream;
     bf16_t* sh = (bf16_t*)shadow_bf16;
+    // the one place a kind gets its width: the grid covers n / W groups, one per lane, up to ogrid's cap
     if (kind == OPT_SGD)
-        hipLaunchKernelGGL(optim_update_kernel<OPT_SGD>, grid, block, 0, st, p, g, nullptr, nullptr, ema, sh, n, hp, sqnorm, max_norm, gmul);
+        hipLaunchKernelGGL((optim_update_kernel<OPT_SGD, 8>), dim3(ogrid(n / 8)), block, 0, st, p, g, nullptr, nullptr, ema, sh, n, hp, sqnorm, max_norm, gmul);
     else if (kind == OPT_SGD_MOMENTUM)
-        hipLaunchKernelGGL(optim_update_kernel<OPT_SGD_MOMENTUM>, grid, block, 0, st, p, g, buf0, nullptr, ema, sh, n, hp, sqnorm, max_norm, gmul);
+        hipLaunchKernelGGL((optim_update_kernel<OPT_SGD_MOMENTUM, 8>), dim3(ogrid(n / 8)), block, 0, st, p, g, buf0, nullptr, ema, sh, n, hp, sqnorm, max_norm, gmul);
+    else if (kind == OPT_ADAM)
+        hipLaunchKernelGGL((optim_update_kernel<OPT_ADAM, 8>), dim3(ogrid(n / 8)), block, 0, st, p, g, buf0, buf1, ema, sh, n, hp, sqnorm, max_norm, gmul);
     else
-        hipLaunchKernelGGL(optim_update_kernel<OPT_ADAM>, grid, block, 0, st, p, g, buf0, buf1, ema, sh, n, hp, sqnorm, max_norm, gmul);
+        hipLaunchKernelGGL((optim_update_kernel<OPT_ADAMW, 1>), dim3(ogrid(n)), block, 0, st, p, g, buf0, buf1, ema, sh, n, hp, sqnorm, max_norm, gmul);
     return launch_status("optim_update");
 }
 extern "C" int mdm_transpose_shadow_bf16(const void* Pb, void* PT, const int64_t* tiles, int ntiles, void* stream) {

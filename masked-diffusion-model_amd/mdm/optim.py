@@ -24,7 +24,7 @@ class _FlatOptimizer:
     travels through, the squared gradient norm, the launches behind the update kernel, `step` / `zero_grad` / `grad_norm`, and the
     torch.optim `state_dict()` grammar (parameters indexed in `model.reference_param_order()`).  A subclass gives
       _fill(h, g, ema_decay)   write the block for step `self.t` into the pinned slot `h`
-      _emit_kernel(...)        enqueue (or record) its update kernel
+      _kernel()                (mdm_optim_update's kind, its first state buffer, its second)
       _state() / _load(st)     the per-parameter `state` entries, out and in
       _group() / _FIELDS       the `param_groups[0]` fields torch writes besides lr / initial_lr / params."""
 
@@ -46,11 +46,7 @@ class _FlatOptimizer:
     def _advance(self):
         self.t += 1
 
-    def _check_flags(self, g):
-        """Adam and SGD refuse a checkpoint whose group asks for what they do not implement (AdamW reads its fields as it always did)."""
-        for k in ("amsgrad", "maximize", "capturable", "differentiable"):
-            if g.get(k):
-                raise ValueError(f"{type(self).__name__}.load_state_dict: {k}=True is not implemented")
+    _LOAD_REFUSES = ("amsgrad", "maximize", "capturable", "differentiable")      # in a loaded group (AdamW: none, as it always read it)
 
     def hyper(self, ema_decay=0.0, advance=True):
         """Refresh the 8-float device block the update kernel reads (async H2D)."""
@@ -74,10 +70,11 @@ class _FlatOptimizer:
         """Enqueue (or record) grad-norm + clip + update + EMA + bf16 shadow over the flat buffers."""
         st = self.store
         call("mdm_sqnorm", ptr(st.G), st.size, ptr(self.sqnorm), stream())
-        self._emit_kernel(ema_buf, float(max_norm), float(gmul))
-        st.emit_transposed_shadow()
-        st.emit_split_shadow()          # fp32 stores with split products: the filters' hi / lo shadow follows the weights
-        st.emit_split_shadow_t()        # ... and so does the flipped, transposed one of split-product gradients
+        kind, buf0, buf1 = self._kernel()
+        call("mdm_optim_update", kind=kind, p=ptr(st.P), g=ptr(st.G), buf0=ptr(buf0), buf1=ptr(buf1), ema=ptr(ema_buf),
+             shadow_bf16=ptr(st.Pb), n=st.size, hp=ptr(self.hp), sqnorm=ptr(self.sqnorm), max_norm=float(max_norm), gmul=float(gmul),
+             stream=stream())
+        st.emit_shadows()               # the shadows derived from the weights follow them
 
     def step(self, max_norm=0.0):
         self.hyper()
@@ -107,7 +104,7 @@ class _FlatOptimizer:
 
     def load_state_dict(self, sd):
         g = sd["param_groups"][0]
-        self._check_flags(g)
+        _no(f"{type(self).__name__}.load_state_dict", **{k: g.get(k) for k in self._LOAD_REFUSES})
         new = dict(lr=g["lr"], initial_lr=g.get("initial_lr", g["lr"]))
         for k in self._FIELDS:
             new[k] = tuple(g[k]) if k == "betas" else g[k]
@@ -141,7 +138,7 @@ class _AdamBase(_FlatOptimizer):
     ema_decay.  `torch.optim.Adam[W].state_dict()` layout: per-parameter `step` / `exp_avg` / `exp_avg_sq` in the reference's
     shapes, indexed in `model.parameters()` order (what accelerate writes to optimizer.bin)."""
     _FIELDS = ("betas", "eps", "weight_decay")
-    _DECOUPLED = None
+    _DECOUPLED = None                   # True: AdamW, mdm_optim_update's kind 3; False: Adam, kind 2
 
     def __init__(self, model, lr, betas, eps, weight_decay):
         super().__init__(model, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -150,6 +147,9 @@ class _AdamBase(_FlatOptimizer):
 
     def _check(self, g):
         pass
+
+    def _kernel(self):
+        return (3 if self._DECOUPLED else 2), self.m, self.v
 
     def _fill(self, h, g, ema_decay):
         b1, b2 = g["betas"]
@@ -177,19 +177,12 @@ class _AdamBase(_FlatOptimizer):
 
 
 class AdamW(_AdamBase):
-    """`torch.optim.AdamW(params, lr)`: decoupled weight decay (mdm_adamw_ema)."""
+    """`torch.optim.AdamW(params, lr)`: decoupled weight decay (mdm_optim_update, kind 3)."""
     _DECOUPLED = True
+    _LOAD_REFUSES = ()
 
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
         super().__init__(model, lr, betas, eps, weight_decay)
-
-    def _check_flags(self, g):
-        pass
-
-    def _emit_kernel(self, ema_buf, max_norm, gmul):
-        st = self.store
-        call("mdm_adamw_ema", p=ptr(st.P), g=ptr(st.G), m=ptr(self.m), v=ptr(self.v), ema=ptr(ema_buf), shadow_bf16=ptr(st.Pb),
-             n=st.size, hp=ptr(self.hp), sqnorm=ptr(self.sqnorm), max_norm=max_norm, gmul=gmul, stream=stream())
 
 
 class Adam(_AdamBase):
@@ -203,11 +196,6 @@ class Adam(_AdamBase):
         super().__init__(model, lr, betas, eps, weight_decay)
 
     _check = staticmethod(_check_adam)
-
-    def _emit_kernel(self, ema_buf, max_norm, gmul):
-        st = self.store
-        call("mdm_optim_update", kind=2, p=ptr(st.P), g=ptr(st.G), buf0=ptr(self.m), buf1=ptr(self.v), ema=ptr(ema_buf),
-             shadow_bf16=ptr(st.Pb), n=st.size, hp=ptr(self.hp), sqnorm=ptr(self.sqnorm), max_norm=max_norm, gmul=gmul, stream=stream())
 
 
 def _check_sgd(g):
@@ -258,11 +246,8 @@ class SGD(_FlatOptimizer):
         h[3] = 1.0 if first else 1.0 - g["dampening"]
         h[4] = g["weight_decay"]; h[5] = float(bool(g["nesterov"])); h[6] = 0.0; h[7] = ema_decay
 
-    def _emit_kernel(self, ema_buf, max_norm, gmul):
-        st = self.store
-        call("mdm_optim_update", kind=0 if self.buf is None else 1, p=ptr(st.P), g=ptr(st.G), buf0=ptr(self.buf), buf1=None,
-             ema=ptr(ema_buf), shadow_bf16=ptr(st.Pb), n=st.size, hp=ptr(self.hp), sqnorm=ptr(self.sqnorm), max_norm=max_norm, gmul=gmul,
-             stream=stream())
+    def _kernel(self):
+        return (0 if self.buf is None else 1), self.buf, None
 
     def _group(self, g):
         return dict(momentum=g["momentum"], dampening=g["dampening"], weight_decay=g["weight_decay"], nesterov=g["nesterov"],

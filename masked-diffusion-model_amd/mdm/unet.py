@@ -178,12 +178,16 @@ class ParamStore:
             _lib.call("mdm_transpose_shadow_bf16", _lib.ptr(self.Pb), _lib.ptr(self.PbT), _lib.ptr(self.tiles),
                       int(self.tiles.shape[0]), _lib.stream())
 
+    def emit_shadows(self):
+        """The shadows derived from P (or from its bf16 shadow Pb), where the store has them: behind every change of the weights."""
+        self.emit_transposed_shadow()
+        self.emit_split_shadow()        # fp32 stores with split products: the filters' hi / lo shadow
+        self.emit_split_shadow_t()      # ... and the flipped, transposed one of split-product gradients
+
     def sync_shadow(self):
         if self.Pb is not None:
             ops.cast_bf16(self.P, self.Pb)
-            self.emit_transposed_shadow()
-        self.emit_split_shadow()
-        self.emit_split_shadow_t()
+        self.emit_shadows()
 
     # -- reference state_dict interchange (SURVEY App. E)
     def to_internal(self, name, t):

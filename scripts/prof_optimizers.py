@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """A short cfg2 loop (bench.py's workload: 32x3x32x32, unet6 preset, 35.75 M parameters, bf16, EMA) with each optimizer in ONE process,
-for one `rocprofv3 --kernel-trace --stats` run: the parent's `adamw_kernel` is the yardstick of the same run for the
-`optim_update_kernel<KIND>` instantiations (time per byte moved).  Bytes per parameter with EMA and bf16 shadow (csrc/optim.hip):
-AdamW / Adam 20 read + 18 written, SGD with momentum 16 + 14, SGD 12 + 10.
+for one `rocprofv3 --kernel-trace --stats` run: the four `optim_update_kernel<KIND, W>` instantiations next to each other (time per
+byte moved).  Bytes per parameter with EMA and bf16 shadow (csrc/optim.hip): AdamW / Adam 20 read + 18 written, SGD with momentum
+16 + 14, SGD 12 + 10.  (A trace of a revision that still had the separate `adamw_kernel` is summarised too.)
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python3 scripts/prof_optimizers.py [steps]
     python3 scripts/prof_optimizers.py --summarise OUT/.../kernel_stats.csv STORE_SIZE     # -> the optimizer rows + ps per byte
@@ -16,14 +16,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "masked-diffusion-model_amd")):
     sys.path.insert(0, p)
 
-BYTES = {"adamw_kernel": 38, "optim_update_kernel<2>": 38, "optim_update_kernel<1>": 30, "optim_update_kernel<0>": 22}
+BYTES = {3: 38, 2: 38, 1: 30, 0: 22}           # by kind: AdamW, Adam, SGD with momentum, SGD
 
 
 def _bytes_of(name):
-    m = re.search(r"optim_update_kernel<[^>]*?(\d)>", name)
+    m = re.search(r"optim_update_kernel<(?:\(int\))?(\d)", name)      # the kind is the first template argument
     if m:
-        return BYTES["optim_update_kernel<%s>" % m.group(1)]
-    return BYTES["adamw_kernel"] if "adamw_kernel" in name else None
+        return BYTES[int(m.group(1))]
+    return BYTES[3] if "adamw_kernel" in name else None
 
 
 def summarise(path, n):

@@ -2,8 +2,9 @@
 """Per-category summary of a rocprofv3 kernel_stats.csv: python scripts/prof_summary.py stats.csv <steps profiled>"""
 import csv, sys, collections
 rows = list(csv.DictReader(open(sys.argv[1])))
-# divisor = optimizer steps profiled = calls of adamw_kernel (one per step, warm-up and event-timed replays included)
-steps = float(sys.argv[2]) if len(sys.argv) > 2 else float(next(int(r["Calls"]) for r in rows if "adamw_kernel" in r["Name"]))
+# divisor = optimizer steps profiled = calls of the update kernel (optim_update_kernel; adamw_kernel in traces of older revisions):
+# one per step, warm-up and event-timed replays included
+steps = float(sys.argv[2]) if len(sys.argv) > 2 else float(next(int(r["Calls"]) for r in rows if "optim_update_kernel" in r["Name"] or "adamw_kernel" in r["Name"]))
 cats = collections.OrderedDict((k, [0, 0.0]) for k in ("wgrad_lin", "conv_pair", "conv_halo", "wgrad ring<.,.,2", "conv_lin", "gemm_ring other", "gemm_bf16", "gemm_f32", "splitk_reduce", "splitk_epilogue", "gn_bwd", "gn_fwd", "softmax", "adamw/sqnorm/transpose", "other"))
 def cat(n):
     if "gemm_ring_kernel" in n: return "wgrad ring<.,.,2" if ", 2, " in n.split("(")[0] else "gemm_ring other"
@@ -13,7 +14,7 @@ def cat(n):
     if "conv_halo" in n: return "conv_halo"
     for k in ("gemm_bf16", "gemm_f32", "splitk_reduce", "splitk_epilogue", "gn_bwd", "gn_fwd", "softmax"):
         if k in n: return k
-    if any(k in n for k in ("adamw", "sqnorm", "transpose_shadow")): return "adamw/sqnorm/transpose"
+    if any(k in n for k in ("optim_update", "adamw", "sqnorm", "transpose_shadow")): return "adamw/sqnorm/transpose"
     return "other"
 tot = 0.0; nk = 0
 for r in rows:

@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """Kernels of ONE optimizer step from a rocprofv3 kernel trace (…_kernel_trace.csv): the launches between two consecutive
-adamw_kernel dispatches in the middle of the run -- exact count, busy time, idle gaps: python scripts/step_kernels.py trace.csv"""
+update-kernel dispatches (optim_update_kernel; adamw_kernel in older traces) in the middle of the run -- exact count, busy time, idle gaps: python scripts/step_kernels.py trace.csv"""
 import collections
 import csv
 import sys
 
 rows = sorted(csv.DictReader(open(sys.argv[1])), key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "adamw_kernel" in r["Kernel_Name"]]
+idx = [i for i, r in enumerate(rows) if "optim_update_kernel" in r["Kernel_Name"] or "adamw_kernel" in r["Kernel_Name"]]
 k = len(idx) // 2
 seg = rows[idx[k] + 1:idx[k + 1] + 1]
 t0, t1 = int(seg[0]["Start_Timestamp"]), int(seg[-1]["End_Timestamp"])

@@ -12,8 +12,11 @@ constant 1e-6f, +, /, coef * c = 6.  Then
 Adam's moments are plain arithmetic too:
     m   :  6 + 3 + (1 - beta1, * d, beta1 m, +) 4                                                 = 13   in  mag(m)
     v   :  2 x 9 (d twice) + (1 - beta2, * d, * d, beta2 v, +) 5                                  = 23   in  mag(v)
+AdamW (kind 3) is Adam with the decay moved: p (1 - lr wd) in front of the moments instead of wd p inside d.  Its moments see one
+term less and keep Adam's counts as upper bounds; the product adds two roundings to the parameter's chain, which the CPU figure of
+torch.optim.AdamW carries.
 Adam's parameter goes through sqrtf, rsqrtf and a division whose errors under the build's flags are not documented: its bound is
-4 x the error torch.optim.Adam itself makes on the CPU in fp32 (`adam_cpu_figure`), both being fp32 chains of the same length.
+4 x the error torch.optim.Adam (AdamW for kind 3) itself makes on the CPU in fp32 (`adam_cpu_figure`), both being fp32 chains of the same length.
 None of this depends on the data.
 """
 import functools
@@ -22,7 +25,7 @@ import math
 import torch
 
 U = 2.0 ** -24
-SGD, SGD_M, ADAM = 0, 1, 2
+SGD, SGD_M, ADAM, ADAMW = 0, 1, 2, 3
 R_SGD_BUF, R_SGD_P, R_EMA, R_ADAM_M, R_ADAM_V = 12, 16, 4, 13, 23
 
 # name -> (kind, lr, keyword hyper-parameters): the variants the tests cover
@@ -32,6 +35,8 @@ VARIANTS = {
     "sgd_nesterov": (SGD_M, 0.1, dict(momentum=0.9, nesterov=True)),
     "adam": (ADAM, 1e-3, {}),
     "adam_wd": (ADAM, 1e-2, dict(weight_decay=0.1)),       # lr 1e-2: decoupled-instead-of-coupled then shows at 1e-3 |p|
+    "adamw": (ADAMW, 1e-3, dict(weight_decay=1e-2)),       # torch's default decay
+    "adamw_wd": (ADAMW, 1e-2, dict(weight_decay=0.1)),     # ... and coupled-instead-of-decoupled does
 }
 # (sqnorm, max_norm, gmul): the clip is active in the first two (norm 2.5 -> c = 0.4; 1.25 -> 0.8), inactive in the next two (c >= 1),
 # and switched off in the last (max_norm <= 0: the squared norm is not read)
@@ -46,7 +51,7 @@ def hp_block(kind, step, lr, momentum=0.0, dampening=0.0, weight_decay=0.0, nest
              ema_decay=0.0, first_step_rule=True, keep_dampening=True):
     """The 8 floats the host sends for the optimizer's step `step` (1-based), fp32.  Planted faults: `first_step_rule=False`,
     `keep_dampening=False`."""
-    if kind == ADAM:
+    if kind >= ADAM:
         b1, b2 = (float(torch.tensor(b, dtype=torch.float32)) for b in betas)      # what the block holds
         h = [lr, b1, b2, eps, weight_decay, 1 - b1 ** step, 1 - b2 ** step, ema_decay]
     else:
@@ -74,10 +79,10 @@ def ref_update(kind, hp, p, g, s0, s1, ema, sqnorm, max_norm, gmul, wrong=None):
     p, g = p.double(), g.double()
     coef = coef64(float(sqnorm), float(max_norm), float(gmul), wrong)
     out = {}
-    if kind == ADAM:
+    if kind >= ADAM:
         lr, b1, b2, eps, wd, bc1, bc2 = h[:7]
         m0, v0 = s0.double(), s1.double()
-        if wrong == "decoupled_decay":
+        if (kind == ADAMW and wrong != "coupled_decay") or wrong == "decoupled_decay":
             p_in, d, D = p * (1.0 - lr * wd), coef * g, (coef * g).abs()
         else:
             p_in, d, D = p, coef * g + wd * p, (coef * g).abs() + wd * p.abs()
@@ -114,15 +119,16 @@ def inputs(n, seed=0, device="cpu"):
     return [t.to(device) for t in (p, g, s0, s1, e)]
 
 
-def _torch_adam_step(p, g, m, v, step, hp, sqnorm, max_norm, gmul):
-    """torch.optim.Adam on the CPU in fp32 from the given state, behind torch's clip_grad_norm_ arithmetic (with the norm given)."""
+def _torch_adam_step(kind, p, g, m, v, step, hp, sqnorm, max_norm, gmul):
+    """torch.optim.Adam (AdamW for kind 3) on the CPU in fp32 from the given state, behind torch's clip_grad_norm_ arithmetic (with
+    the norm given)."""
     h = [float(x) for x in hp.double()]
     g = g * torch.tensor(gmul, dtype=torch.float32)
     if max_norm > 0:
         norm = torch.tensor(sqnorm, dtype=torch.float32).sqrt() * torch.tensor(gmul, dtype=torch.float32)
         g = g * torch.clamp(max_norm / (norm + 1e-6), max=1.0)
     P = torch.nn.Parameter(p.clone())
-    opt = torch.optim.Adam([P], lr=h[0], betas=(h[1], h[2]), eps=h[3], weight_decay=h[4], foreach=False)
+    opt = (torch.optim.AdamW if kind == ADAMW else torch.optim.Adam)([P], lr=h[0], betas=(h[1], h[2]), eps=h[3], weight_decay=h[4], foreach=False)
     opt.state[P] = dict(step=torch.tensor(float(step - 1)), exp_avg=m.clone(), exp_avg_sq=v.clone())
     P.grad = g
     opt.step()
@@ -132,19 +138,19 @@ def _torch_adam_step(p, g, m, v, step, hp, sqnorm, max_norm, gmul):
 
 @functools.lru_cache(maxsize=None)
 def adam_cpu_figure(name, n=1 << 16, steps=3):
-    """Largest |p - p64| / (u mag) torch.optim.Adam makes in fp32 on the CPU over `steps` steps from zero moments and every clip case,
+    """Largest |p - p64| / (u mag) torch.optim.Adam (AdamW for kind 3) makes in fp32 on the CPU over `steps` steps from zero moments and every clip case,
     each step against the fp64 evaluation from torch's own state before it."""
     kind, lr, kw = VARIANTS[name]
-    assert kind == ADAM
+    assert kind >= ADAM
     worst = 0.0
     for sq, mx, gm in CLIPS:
         p, g0, _, _, _ = inputs(n, seed=5)
         m, v = torch.zeros(n), torch.zeros(n)
         for k in range(1, steps + 1):
             g = torch.roll(g0, k)
-            hp = hp_block(ADAM, k, lr, **kw)
-            want, mag = ref_update(ADAM, hp, p, g, m, v, None, sq, mx, gm)["p"]
-            p, m, v = _torch_adam_step(p, g, m, v, k, hp, sq, mx, gm)
+            hp = hp_block(kind, k, lr, **kw)
+            want, mag = ref_update(kind, hp, p, g, m, v, None, sq, mx, gm)["p"]
+            p, m, v = _torch_adam_step(kind, p, g, m, v, k, hp, sq, mx, gm)
             worst = max(worst, float(((p.double() - want).abs() / (U * mag)).max()))
     return worst
 
@@ -153,7 +159,7 @@ def bounds(name, ref):
     """name of a variant, ref = ref_update(...) -> dict name -> per-element absolute bound."""
     kind = VARIANTS[name][0]
     tiny = 2.0 ** -140
-    if kind == ADAM:
+    if kind >= ADAM:
         b = {"p": 4.0 * adam_cpu_figure(name) * U * ref["p"][1], "s0": rbound(R_ADAM_M) * ref["s0"][1], "s1": rbound(R_ADAM_V) * ref["s1"][1]}
     else:
         b = {"p": rbound(R_SGD_P) * ref["p"][1]}
@@ -170,6 +176,7 @@ CONTROLS = {
     "dampening_dropped": ("sgd_momentum_dampening_wd", CLIPS[0], dict(keep_dampening=False), None),
     "nesterov_old_buffer": ("sgd_nesterov", CLIPS[0], {}, "nesterov_old_buffer"),
     "decoupled_decay": ("adam_wd", CLIPS[0], {}, "decoupled_decay"),
+    "coupled_decay": ("adamw_wd", CLIPS[0], {}, "coupled_decay"),
     # norm 1.5, gmul 0.5: the averaged gradient (0.75) is inside the ball, the summed one is not
     "gmul_after_clip_test": ("sgd", (2.25, 1.0, 0.5), {}, "gmul_after_clip_test"),
 }

@@ -17,14 +17,16 @@ def test_entry_point_declared_bound_and_exported():
     header = open(os.path.join(ROOT, "include", "mdm_hip.h")).read()
     declared = set(re.findall(r"\b(mdm_[a-z0-9_]+)\s*\(", header))
     assert "mdm_optim_update" in declared and "mdm_optim_update" in _lib.EXPORTS
+    assert "mdm_adamw_ema" not in header and "mdm_adamw_ema" not in _lib.EXPORTS      # AdamW is kind 3 of the one entry point
     args, res = _lib._PROTOS["mdm_optim_update"]
     assert len(args) == 13 and args[0] is _lib.i32 and args[7] is _lib.i64 and args[10] is args[11] is _lib.f32 and res is _lib.i32
     lib = _lib.load()
     fn = lib.mdm_optim_update
     # argument checks run before any launch: a bad kind, a missing state buffer, a misaligned buffer
-    assert fn(3, 16, 16, None, None, None, None, 8, 16, None, 0.0, 1.0, None) != 0 and b"kind" in lib.mdm_last_error()
+    assert fn(4, 16, 16, None, None, None, None, 8, 16, None, 0.0, 1.0, None) != 0 and b"kind" in lib.mdm_last_error()
     assert fn(1, 16, 16, None, None, None, None, 8, 16, None, 0.0, 1.0, None) != 0 and b"state buffer" in lib.mdm_last_error()
     assert fn(2, 16, 16, 16, None, None, None, 8, 16, None, 0.0, 1.0, None) != 0 and b"both" in lib.mdm_last_error()
+    assert fn(3, 16, 16, 16, None, None, None, 8, 16, None, 0.0, 1.0, None) != 0 and b"both" in lib.mdm_last_error()
     assert fn(0, 20, 16, None, None, None, None, 8, 16, None, 0.0, 1.0, None) != 0 and b"aligned" in lib.mdm_last_error()
     assert fn(0, 16, 16, None, None, None, None, 8, 16, None, 1.0, 1.0, None) != 0 and b"squared norm" in lib.mdm_last_error()
 
@@ -138,10 +140,10 @@ def test_planted_faults_clear_100x_the_bound(fault):
 
 
 def test_adam_cpu_figure_is_a_few_roundings():
-    """The yardstick of the Adam bound: torch.optim.Adam's own fp32 error on the CPU, in u = 2^-24 of |p| + lr mag(update).  A chain of
+    """The yardstick of the Adam and AdamW bounds: torch.optim.Adam's / AdamW's own fp32 error on the CPU, in u = 2^-24 of |p| + lr mag(update).  A chain of
     ~20 roundings cannot honestly sit below half a rounding or above its own length."""
     from _notes import note
-    for name in ("adam", "adam_wd"):
+    for name in ("adam", "adam_wd", "adamw", "adamw_wd"):
         f = R.adam_cpu_figure(name)
         note("adam_cpu_figure", dict(variant=name, torch_cpu_err_in_u=f, kernel_bound_in_u=4 * f))
         assert 0.5 <= f <= 24.0, (name, f)
