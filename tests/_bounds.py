@@ -63,6 +63,77 @@ are derived, never fitted to what a GPU returned.
 rel-L2 bar of the bf16 outputs: `attn_emulate_bf16` is the storage precision alone -- fp64 arithmetic with exactly the bf16
 roundings above.  A kernel's rel-L2 against fp64 may be at most REL_L2_MARGIN = 1.5 times the emulation's on the same inputs:
 the emulation does not depend on the tile order, while truncating P or the output instead of rounding lands at 1.7 - 2.0 times.
+
+GroupNorm (csrc/gn_kernels.inc, the fused epilogues of csrc/gemm.hip)
+----------------------------------------------------------------------
+x [N][P][C], G groups of cpg = C / G channels, n = cpg P elements per (image, group).  References are fp64 functions of exactly the
+stored inputs (bf16 upcasts exactly; eps is the fp32 value the descriptor carries).  u = 2^-8 | 2^-24 as above.
+
+forward, scheme "pivot" (the standalone kernels): K = the group's first element; the sums of d = x - K and d^2 are taken in fp32 in
+any order.  With g = (n + 8) 2^-23 (any-order fp32 summation of n terms: (n - 1) 2^-24 to first order, twice that taken), D1 =
+mean |d|, D2 = mean d^2, md = mean d:
+
+    e_md   = g D1                                                      the computed mean of d
+    e_mean = e_md + 2^-23 |mean|                                       K + md rounded, the product with 1 / n rounded
+    e_var  = (g + 2^-22) D2 + 2 |md| e_md + e_md^2 + 2^-23 (D2 + md^2)  d rounded (2^-23 on its square) and the square's fma; md^2
+                                                                       from the computed md; the products, the difference
+    w = var + eps,  e_var < w / 2 asserted (the rows are chosen so that it holds)
+    e_r    = e_var / (2 (w - e_var)) + EPS_RSQ                         RELATIVE error of rstd = rsqrtf(w)
+
+EPS_RSQ = 4 x 2^-23: four times the accuracy of rsqrtf.  What a ROCm installation itself states is only the mapping: its HIP header
+lib/llvm/lib/clang/<version>/include/__clang_hip_math.h defines rsqrtf(x) as __ocml_rsqrt_f32(x); no header or document it ships
+gives the accuracy.  The figure, 1 ULP, is quoted from AMD's PUBLIC documentation -- the OCML document of the ROCm device libraries
+("rsqrt", float) and the math API table of the HIP documentation -- and one ulp of an fp32 value is at most 2^-23 of it.  Derived
+from that figure, not fitted.  A constant group has D1 = D2 = md = 0, hence e_var = 0: its mean must be K (the tests ask for K's bits)
+and its rstd rsqrtf(eps); the tests hold the latter to the bits of fp32(1 / sqrt(eps)) or of a neighbour, which is what 1 ULP
+allows.
+
+    z = (x - mean) rstd gamma_c + beta_c
+    |dz| <= |rstd gamma_c| e_mean + |x - mean| |rstd gamma_c| (e_r + 2^-22) + 2^-24 |z|
+            (x - mean^ rounded, rstd gamma rounded, their product inside or in front of an fma: 1.5 x 2^-23 < 2^-22; the fma's own
+             rounding is the last term)
+    silu(z) = z rcp(1 + __expf(-z)):  |dsilu| <= 1.1 |dz| + (EPS_EXP + 2^-23 |z| + 2^-22) |silu(z)|     (1.1 >= sup |silu'|; the
+            exponential's argument rounding is 2^-24 |z| absolute = relative on exp, the add, the reciprocal, the product)
+    store:  u |ref| + (1 + u) (the above)
+    dropout: ref keep scale with one more 2^-24 |ref| for the product; a dropped element has ref = bound = 0: exactly zero.
+
+scheme "two_pass" (the fused forward epilogues: the mean of the bf16-rounded y, then centred squares): A1 = mean |y|,
+
+    e_mean = g A1 + 2^-23 |mean|                        nothing is subtracted before the first sum: it scales with |y|, not D1
+    mean (y - mean^)^2 = var + (mean - mean^)^2 <= V = var + e_mean^2       exactly
+    e_var  = e_mean^2 + (g + 2^-22 + 2^-23) V + 2^-24 w  the centred value rounded (2^-23 on its square), the square, the sum, the
+                                                        product with 1 / n; the sum with eps
+
+and everything after w as above.
+
+backward, as a function of (x, dy, mean, rstd, gamma, beta): the statistics handed to the kernel are fp32-rounded fp64 values --
+inputs of the reference, so no backward bound depends on a forward kernel.  With r = rstd, xh = (x - mean) r, z = xh gamma + beta,
+sigma = 1 / (1 + exp(-z)):
+
+    e_xh = 2^-23 (|x| + |mean|) r                      both (x - mean) r and fma(x, r, -mean r)
+    e_z  = 2^-22 ((|x| + |mean|) r |gamma| + |beta|)
+    e_sg = EPS_EXP + 2^-23 |z| + 2^-22                 relative error of sigma
+    silu'(z) = sigma (1 + z (1 - sigma)):  |dsilu'| <= (e_sg + 2^-22) (1 + 2 |z|) sigma + 0.5 e_z      ABSOLUTE: silu' crosses zero;
+                                                       0.5 >= sup |silu''|
+    gz = dy silu'(z),  e_gz = |dy| e_silu' + 2^-24 |gz|  (+ dy_err |silu'| where dy itself was computed; + 2^-24 |gz| with dropout,
+                                                       where dy is dy keep scale)
+    dbeta  = sum_{n,p} gz:      gNP sum |gz| + sum e_gz,                           gNP = (N P + 8) 2^-23
+    dgamma = sum_{n,p} gz xh:   gNP sum |gz xh| + sum (e_gz |xh| + |gz| e_xh)
+    A1 = sum_group gz gamma, A2 = sum_group gz gamma xh:   (n + cpg + 8) 2^-23 on their |.| sums (gn_bwd_reg_kernel forms them as
+                                                       gamma-weighted sums over the group's channels of the column sums), plus the
+                                                       propagated e_gz, e_xh
+    dx  = r (gamma gz - (A1 + xh A2) / n),   mag = the same on absolute values
+    e_dx = r (|gamma| e_gz + (e_A1 + |xh| e_A2 + e_xh |A2|) / n) + 2^-21 mag + 2^-22 (|x| + |mean|) r^2 |A2| / n
+                                                       (the last term: k1 = fma(q2, -mean r, q1) of gn_bwd_reg_kernel, whose two
+                                                       parts cancel against x k2)
+    stored = dx + adds:  + 2^-23 (|dx| + sum |add|), wrapped with u
+    sum_img[n][c] = sum_p dx (in front of the adds and of the store's rounding):  (P + 8) 2^-23 sum_p mag + sum_p e_dx
+    sum_all, dgamma, dbeta accumulate onto a prior value: + (N + 8) 2^-23 (|prior| + the |.| sum) for the N additions.
+A group's dx sums to zero, so the column sums are held against magnitudes, never relatively.
+
+A CPU emulation of each kernel's arithmetic in fp32 (tests/test_bounds_cpu.py: pivot sums in two orders, the two-pass forward, both
+backward forms, the adds, one store rounding) stays inside these bounds on every row the GPU tests use, and each planted fault
+leaves them.  rel-L2 bar of the bf16 y and dx: REL_L2_MARGIN times the rel-L2 of rne_bf16(ref), as for attention.
 """
 import torch
 import torch.nn.functional as F
@@ -71,6 +142,7 @@ U_BF16, U_F32 = 2.0 ** -8, 2.0 ** -24
 SPLIT_PRODUCT = 2.0 ** -15
 EPS_EXP = 2.0 ** -20          # fast exponential (module docstring)
 REL_L2_MARGIN = 1.5           # kernel rel-L2 <= this x the rel-L2 of the storage-precision emulation
+EPS_RSQ = 4 * 2.0 ** -23       # rsqrtf: 4 x its documented 1 ULP (module docstring)
 # guard pattern: a quiet NaN with a payload no kernel produces
 _PAT = {torch.float32: (torch.int32, 0x7FC0A5A5), torch.bfloat16: (torch.int16, 0x7FE5)}
 
@@ -390,3 +462,157 @@ def attn_fused_refs(qkv, do, scale, emulate=True):
     if emulate:
         R["emu"] = attn_emulate_bf16(q, k, v, do, scale, R["o_in"], R["lse_in"])
     return R
+
+
+# ------------------------------------------------------------------ GroupNorm (module docstring)
+def _f64(t):
+    return torch.as_tensor(t).detach().cpu().double()
+
+
+def _per_elem(t, cpg):
+    """[N][G] -> [N][1][C]"""
+    return t.repeat_interleave(cpg, 1)[:, None, :]
+
+
+def gn_fwd_ref(x, gamma, beta, G, eps, silu, store, scheme="pivot", keep=None, scale=1.0):
+    """x [N][P][C] as stored, gamma / beta [C] -> {"y": (ref, bound) [N][P][C], "stats": (ref, bound) [N][G][2]} with stats[..., 0] the
+    mean and stats[..., 1] rstd, each under its own bound.  scheme: "pivot" (csrc/gn_kernels.inc) | "two_pass" (the fused forward
+    epilogues).  keep (bool [N][P][C]) / scale: the host-predicted dropout mask and the fp32 scale."""
+    x, gamma, beta = _f64(x), _f64(gamma), _f64(beta)
+    N, P, C = x.shape
+    cpg = C // G
+    n = cpg * P
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    xg = x.reshape(N, P, G, cpg)
+    g = (n + 8) * 2.0 ** -23
+    if scheme == "pivot":
+        K = xg[:, :1, :, :1]
+        d = xg - K
+        D1, D2, md = d.abs().mean((1, 3)), (d * d).mean((1, 3)), d.mean((1, 3))
+        mean, var = K[:, 0, :, 0] + md, D2 - md * md
+        e_md = g * D1
+        e_mean = e_md + 2.0 ** -23 * mean.abs()
+        e_var = (g + 2.0 ** -22) * D2 + 2 * md.abs() * e_md + e_md ** 2 + 2.0 ** -23 * (D2 + md * md)
+        w = var + eps
+    else:
+        assert scheme == "two_pass", scheme
+        mean = xg.mean((1, 3))
+        var = ((xg - mean[:, None, :, None]) ** 2).mean((1, 3))
+        e_mean = g * xg.abs().mean((1, 3)) + 2.0 ** -23 * mean.abs()
+        w = var + eps
+        e_var = e_mean ** 2 + (g + 2.0 ** -22 + 2.0 ** -23) * (var + e_mean ** 2) + 2.0 ** -24 * w
+    assert bool((e_var < w / 2).all()), "gn_fwd_ref: the variance bound reaches var + eps on this draw: choose another row"
+    rstd = w.rsqrt()
+    e_r = e_var / (2 * (w - e_var)) + EPS_RSQ
+    m_e, r_e, em_e, er_e = (_per_elem(t, cpg) for t in (mean, rstd, e_mean, e_r))
+    a = r_e * gamma
+    z = (x - m_e) * a + beta
+    e = a.abs() * em_e + (x - m_e).abs() * a.abs() * (er_e + 2.0 ** -22) + 2.0 ** -24 * z.abs()
+    y = z
+    if silu:
+        y = z * torch.sigmoid(z)
+        e = 1.1 * e + (EPS_EXP + 2.0 ** -23 * z.abs() + 2.0 ** -22) * y.abs()
+    if keep is not None:
+        ks = torch.as_tensor(keep).reshape(N, P, C).double() * float(torch.tensor(scale, dtype=torch.float32))
+        y, e = y * ks, (e + 2.0 ** -24 * y.abs()) * ks
+    return {"y": _wrap(y, e, _u(store)), "stats": (torch.stack((mean, rstd), 2), torch.stack((e_mean, rstd * e_r), 2))}
+
+
+def gn_bwd_ref(x, dy, mean, rstd, gamma, beta, G, silu, store, adds=(), dy_err=None, N_all=None, keep=None, scale=1.0,
+               prior=None):
+    """The backward as a function of its inputs: x, dy [N][P][C] as stored, mean / rstd [N][G] as HANDED to the kernel, `adds` the
+    tensors [N][P][C] added to dx in front of the store, dy_err the absolute error of a dy that was itself computed, N_all the number
+    of images the per-channel sums run over when x holds a subset of them, keep / scale the dropout mask of dy, prior =
+    dict(dgamma=, dbeta=, sum_all=) the values accumulated onto.  -> (ref, bound) pairs "dx" (the stored value, adds included),
+    "dgamma", "dbeta" [C], "sum_img" [N][C], "sum_all" [C]; "dx_only" = (dx, mag) in front of the adds."""
+    x, dy, mean, rstd, gamma, beta = (_f64(t) for t in (x, dy, mean, rstd, gamma, beta))
+    N, P, C = x.shape
+    cpg = C // G
+    n = cpg * P
+    u = _u(store)
+    m, r = _per_elem(mean, cpg), _per_elem(rstd, cpg)
+    e_gz_extra = 0.0
+    if keep is not None:
+        dy = dy * torch.as_tensor(keep).reshape(N, P, C).double() * float(torch.tensor(scale, dtype=torch.float32))
+        e_gz_extra = 2.0 ** -24
+    xh = (x - m) * r
+    e_xh = 2.0 ** -23 * (x.abs() + m.abs()) * r
+    z = xh * gamma + beta
+    if silu:
+        sg = torch.sigmoid(z)
+        gp = sg * (1 + z * (1 - sg))
+        e_z = 2.0 ** -22 * ((x.abs() + m.abs()) * r * gamma.abs() + beta.abs())
+        e_gp = (EPS_EXP + 2.0 ** -23 * z.abs() + 2.0 ** -22 + 2.0 ** -22) * (1 + 2 * z.abs()) * sg + 0.5 * e_z
+    else:
+        gp, e_gp = torch.ones_like(z), torch.zeros_like(z)
+    gz = dy * gp
+    e_gz = dy.abs() * e_gp + (2.0 ** -24 + e_gz_extra) * gz.abs()
+    if dy_err is not None:
+        e_gz = e_gz + _f64(dy_err) * gp.abs()
+    prior = prior or {}
+    pr = lambda k: _f64(prior[k]) if prior.get(k) is not None else torch.zeros(C, dtype=torch.float64)
+    Nn = N if N_all is None else N_all
+    gNP, gN = (Nn * P + 8) * 2.0 ** -23, (Nn + 8) * 2.0 ** -23
+    out = {}
+    for name, t, et in (("dbeta", gz, e_gz), ("dgamma", gz * xh, e_gz * xh.abs() + gz.abs() * e_xh)):
+        s, sa = t.sum((0, 1)), t.abs().sum((0, 1))
+        out[name] = (pr(name) + s, gNP * sa + et.sum((0, 1)) + gN * (pr(name).abs() + sa))
+    gs = lambda t: _per_elem(t.reshape(N, P, G, cpg).sum((1, 3)), cpg)
+    gg = gz * gamma
+    A1, A2, M1, M2 = gs(gg), gs(gg * xh), gs(gg.abs()), gs((gg * xh).abs())
+    gn = (n + cpg + 8) * 2.0 ** -23
+    e_A1 = gn * M1 + gs(e_gz * gamma.abs())
+    e_A2 = gn * M2 + gs(e_gz * (gamma * xh).abs() + gg.abs() * e_xh)
+    dx = r * (gg - (A1 + xh * A2) / n)
+    mag = r * (gg.abs() + (A1.abs() + xh.abs() * A2.abs()) / n)
+    e_dx = (r * (gamma.abs() * e_gz + (e_A1 + xh.abs() * e_A2 + e_xh * A2.abs()) / n) + 2.0 ** -21 * mag
+            + 2.0 ** -22 * (x.abs() + m.abs()) * r * r * A2.abs() / n)
+    adds = [_f64(a) for a in adds]
+    stored, amag = dx + sum(adds), dx.abs() + sum(a.abs() for a in adds)
+    out["dx"] = _wrap(stored, e_dx + (2.0 ** -23 * amag if adds else 0.0), u)
+    out["dx_only"] = (dx, mag)
+    b_img = (P + 8) * 2.0 ** -23 * mag.sum(1) + e_dx.sum(1)
+    out["sum_img"] = (dx.sum(1), b_img)
+    out["sum_all"] = (pr("sum_all") + dx.sum((0, 1)), b_img.sum(0) + gN * (pr("sum_all").abs() + mag.sum((0, 1))))
+    return out
+
+
+def gn_stats_in(x, G, eps):
+    """The statistics a backward test hands to the kernel: fp64 (two-pass) mean and rstd of the stored x, rounded to fp32.
+    -> [N][G][2] fp32"""
+    x = _f64(x)
+    N, P, C = x.shape
+    xg = x.reshape(N, P, G, C // G)
+    mean = xg.mean((1, 3))
+    var = ((xg - mean[:, None, :, None]) ** 2).mean((1, 3))
+    return torch.stack((mean, (var + float(torch.tensor(eps, dtype=torch.float32))).rsqrt()), 2).float()
+
+
+def gn_draw(N, P, C, kind, seed, direction="fwd", G=32, dtype="bf16"):
+    """Inputs of the GroupNorm tests as fp32 tensors already rounded to `dtype`: (x, dy) [N][P][C].
+    "plain": x ~ 1.5 N(0, 1) + 0.3, dy ~ N(0, 1).  "spiked": pixels 1, P / 2 and P - 1 of every channel scaled by 40 -- in x for a
+    forward row, in dy for a backward row: one element missing from a sum of 4096 plain terms moves it by about as much as the
+    summation bound allows, a missing spike by 75 times that.  "offset": x = 1000 + 0.01 N(0, 1) (fp32 only): the forward's pivot; the
+    backward's bounds are loose here and no fault-detection claim is made for it.  "constant": as plain, but group G - 1 of image
+    N - 1 is the constant 0.75."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, P, C, generator=g) * 1.5 + 0.3
+    dy = torch.randn(N, P, C, generator=g)
+    if kind == "offset":
+        assert dtype == "f32"
+        x = 1000.0 + 0.01 * (x - 0.3) / 1.5
+    elif kind == "spiked":
+        (x if direction == "fwd" else dy)[:, [1, P // 2, P - 1]] *= 40.0
+    elif kind == "constant":
+        x[N - 1, :, (G - 1) * (C // G):] = 0.75
+    else:
+        assert kind == "plain", kind
+    if dtype == "bf16":
+        x, dy = x.bfloat16().float(), dy.bfloat16().float()
+    return x, dy
+
+
+def rel_l2_bar(ref):
+    """REL_L2_MARGIN x the rel-L2 of rne_bf16(ref): the bar of a bf16 output (module docstring)."""
+    ref = ref.double()
+    return REL_L2_MARGIN * float((rne_bf16(ref).double() - ref).norm() / (ref.norm() + 1e-300))

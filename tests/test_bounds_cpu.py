@@ -295,3 +295,335 @@ def test_attention_rel_l2_bar_rejects_truncated_store():
     assert rel > REL_L2_MARGIN * emu, (rel, emu)
     ok, _ = _emulate(256, 128, "flat")
     assert float((ok["o"].double() - ref).norm() / ref.norm()) <= REL_L2_MARGIN * emu
+
+
+# ------------------------------------------------------------------ GroupNorm
+# An fp32 emulation of the kernels' arithmetic (csrc/gn_kernels.inc, the fused epilogues of csrc/gemm.hip) on the rows of
+# tests/_gn_rows.py (the rows tests/test_gn_bounds_gpu.py runs): it must stay inside every bound of _bounds.gn_fwd_ref /
+# gn_bwd_ref, and each fault planted into it must leave them on every row it is claimed for.  Sums run in numpy fp32, sequentially ("seq") or pairwise ("pair").
+import numpy as np
+
+import _gn_rows as GN
+from _bounds import gn_bwd_ref, gn_draw, gn_fwd_ref, gn_stats_in, rel_l2_bar
+
+F32 = torch.float32
+
+
+def _np_sum(t, dim, order):
+    a = t.contiguous().numpy()
+    r = np.cumsum(a, axis=dim, dtype=np.float32).take(-1, axis=dim) if order == "seq" else a.sum(axis=dim, dtype=np.float32)
+    return torch.from_numpy(np.ascontiguousarray(r))
+
+
+def _sig32(z):
+    return 1.0 / (1.0 + torch.exp(-z))
+
+
+def _gn_store(t, dt, fault=None):
+    if dt == "f32":
+        return t
+    return trunc_bf16(t.double()) if fault == "trunc_store" else t.to(torch.bfloat16)
+
+
+def _pixel_mask(P, fault):
+    """1 for the pixels that enter the sums: all but the last one / the first one of the last 64-pixel stretch (the first pixel of a
+    tail loop; P / 2 on maps of one stretch: pixel 0 holds the pivots, and a pivot adds nothing to the shifted sums)"""
+    m = torch.ones(P)
+    if fault == "last_pixel":
+        m[P - 1] = 0
+    if fault == "tail_pixel":
+        m[(P - 1) // 64 * 64 or P // 2] = 0
+    return m
+
+
+def _per_c(t, cpg):
+    return t.repeat_interleave(cpg, 1)[:, None, :].clone()
+
+
+def _flip_lanes(keep):
+    """one kept lane dropped and one dropped lane kept"""
+    k = keep.clone().reshape(-1)
+    k[int(k.nonzero()[5])] = False
+    k[int((~keep.reshape(-1)).nonzero()[5])] = True
+    return k.reshape(keep.shape)
+
+
+def _gn_emul_fwd(x, gamma, beta, G, eps, silu, dt, order="pair", scheme="pivot", keep=None, scale=1.0, fault=None):
+    """gn_fwd_kernel / gn_fwd_reg_kernel ("pivot") or the fused forward epilogue ("two_pass") -> (y as stored, stats fp32)"""
+    x, gamma, beta = x.float(), gamma.float(), beta.float()
+    N, P, C = x.shape
+    cpg = C // G
+    xg = x.reshape(N, P, G, cpg)
+    inv = torch.tensor(1.0, dtype=F32) / torch.tensor(float(cpg * P), dtype=F32)
+    flat = lambda t: t.permute(0, 2, 1, 3).reshape(N, G, P * cpg)
+    msk = _pixel_mask(P, fault)[None, :, None, None]
+    if scheme == "pivot":
+        K = xg[:, :1, :, :1].clone()
+        if fault == "no_pivot":
+            K = torch.zeros_like(K)
+        d = (xg - K) * msk
+        md = _np_sum(flat(d), 2, order) * inv
+        var = (_np_sum(flat(d * d), 2, order) * inv - md * md).clamp_min(0)
+        mean = K[:, 0, :, 0] + md
+    else:
+        mean = _np_sum(flat(xg * msk), 2, order) * inv
+        c = (xg - mean[:, None, :, None]) * msk
+        var = _np_sum(flat(c * c), 2, order) * inv
+    rstd = torch.rsqrt(var + (0.0 if fault == "no_eps" else torch.tensor(eps, dtype=F32)))
+    stats = torch.stack((mean, rstd), 2)
+    m_e, r_e = _per_c(mean, cpg), _per_c(rstd.roll(1, 0) if fault == "rstd_neighbour_image" else rstd, cpg)
+    if fault == "group_off_by_one":          # the first channel of a block takes the statistics of the group in front of it
+        c0 = (G // 2) * cpg
+        m_e[..., c0], r_e[..., c0] = mean[:, G // 2 - 1, None], rstd[:, G // 2 - 1, None]
+    z = (x - m_e) * (r_e * gamma) + beta if scheme == "pivot" else ((x - m_e) * r_e) * gamma + beta
+    if silu:
+        z = z * _sig32(z)
+    if keep is not None:
+        kp = _flip_lanes(keep) if fault == "flip_lane" else keep
+        z = torch.where(kp, z * torch.tensor(scale, dtype=F32), torch.zeros(()))
+    return _gn_store(z, dt, fault), stats
+
+
+def _gn_emul_bwd(x, dy, stats, gamma, beta, G, silu, dt, kernel, adds=(), prior=None, order="pair", keep=None, scale=1.0, fault=None):
+    """gn_bwd_kernel ("stream") or gn_bwd_reg_kernel ("reg": xh and z as one fma from per-channel constants, the group sums as
+    gamma-weighted sums of the column sums, k1 = fma(q2, -mean rstd, q1)) -> dict of outputs"""
+    x, dy, gamma, beta = x.float(), dy.float(), gamma.float(), beta.float()
+    N, P, C = x.shape
+    cpg = C // G
+    mean, rstd = stats[..., 0], stats[..., 1]
+    if fault == "rstd_neighbour_image":
+        rstd = rstd.roll(1, 0)
+    m, r = _per_c(mean, cpg), _per_c(rstd, cpg)
+    if keep is not None:
+        kp = _flip_lanes(keep) if fault == "flip_lane" else keep
+        dy = torch.where(kp, dy * torch.tensor(scale, dtype=F32), torch.zeros(()))
+    if kernel == "stream":
+        xh = (x - m) * r
+        zz = xh * gamma + beta
+    else:
+        nmr, za = -m * r, r * gamma
+        zb = nmr * gamma + beta
+        xh, zz = x * r + nmr, x * za + zb
+    gz = dy
+    if silu and fault != "no_silu_grad":
+        s = _sig32(zz)
+        gz = dy * (s * (1.0 + zz * (1.0 - s)))
+    msk = _pixel_mask(P, fault)[None, :, None]
+    dg_img, db_img = _np_sum(gz * xh * msk, 1, order), _np_sum(gz * msk, 1, order)          # [N][C]
+    gsum = lambda t: _np_sum(t.reshape(N, P, G, cpg).permute(0, 2, 1, 3).reshape(N, G, P * cpg), 2, order)
+    if kernel == "stream":
+        gg = gz * gamma
+        a1, a2 = gsum(gg * msk), gsum(gg * xh * msk)
+    else:
+        a1, a2 = _np_sum((db_img * gamma).reshape(N, G, cpg), 2, order), _np_sum((dg_img * gamma).reshape(N, G, cpg), 2, order)
+    inv = torch.tensor(1.0, dtype=F32) / torch.tensor(float(cpg * P), dtype=F32)
+    A1, A2 = _per_c(a1, cpg), _per_c(a2, cpg)
+    if kernel == "stream":
+        k1, k2 = r * A1 * inv, r * A2 * inv
+        o = (r * gamma) * gz - (xh * k2 + k1)
+    else:
+        q1, q2 = r * A1 * inv, r * A2 * inv
+        k1, k2 = q2 * nmr + q1, q2 * r
+        o = za * gz - (x * k2 + k1)
+    dx = o
+    adds = [a.float() for a in adds]
+    use = adds[:-1] if fault == "drop_add0b" else ([adds[0]] + adds if fault == "add0_twice" else adds)
+    for a in use:
+        o = o + a
+    sum_img = _np_sum(o if fault == "sum_img_after_adds" else dx, 1, order)
+    if fault == "sum_img_neighbour":
+        sum_img = sum_img.roll(1, 0)
+    pr = lambda k: prior[k].float() if prior and prior.get(k) is not None else 0.0
+    dgam = _np_sum(_np_sum(gz * x * msk, 1, order), 0, order) if fault == "dgamma_x" else _np_sum(dg_img, 0, order)
+    return dict(dx=_gn_store(o, dt, fault), dgamma=pr("dgamma") + dgam, dbeta=pr("dbeta") + _np_sum(db_img, 0, order),
+                sum_img=sum_img, sum_all=pr("sum_all") + _np_sum(sum_img, 0, order))
+
+
+_GN = {}
+
+
+def _gn_fwd_problem(row):
+    if row not in _GN:
+        _GN[row] = GN.fwd_problem(row)
+    return _GN[row]
+
+
+def _gn_bwd_problem(row):
+    if row not in _GN:
+        _GN[row] = GN.bwd_problem(row)
+    return _GN[row]
+
+
+def _gn_fwd_emulate(row, order="pair", fault=None):
+    route, dt, drop, (C0, C1, P, G), N, draw, silu = row
+    x, gamma, beta, R = _gn_fwd_problem(row)
+    keep, scale = GN.row_keep(row)
+    y, stats = _gn_emul_fwd(x, gamma, beta, G, GN.EPS, silu, dt, order, "pivot", keep, scale, fault)
+    return dict(y=y, stats=stats), R
+
+
+def _gn_bwd_emulate(row, kernel, order="pair", fault=None):
+    route, dt, drop, (C0, C1, P, G), N, draw, silu, form = row
+    x, dy, stats, gamma, beta, adds, pri, R = _gn_bwd_problem(row)
+    keep, scale = GN.row_keep(row)
+    got = _gn_emul_bwd(x, dy, stats, gamma, beta, G, silu, dt, kernel, list(adds.values()), pri if form == "sums" else dict(pri, sum_all=None),
+                       order, keep, scale, fault)
+    return got, R
+
+
+def _gn_margin(got, R, names):
+    """largest err / bound over the named outputs (inf for a non-finite element)"""
+    worst = 0.0
+    for name in names:
+        ref, bound = R[name]
+        err = (got[name].double() - ref).abs()
+        ratio = torch.where(torch.isfinite(err), err / bound.clamp_min(1e-300), torch.full_like(err, float("inf")))
+        ratio = torch.where((err == 0) & (bound == 0), torch.zeros_like(ratio), ratio)
+        worst = max(worst, float(ratio.max()))
+    return worst
+
+
+BWD_OUT = ("dx", "dgamma", "dbeta", "sum_img", "sum_all")
+
+
+@pytest.mark.parametrize("row", GN.FWD_ROWS, ids=[GN.row_id(r) for r in GN.FWD_ROWS])
+def test_groupnorm_forward_bounds_accept_the_emulated_kernel(row):
+    for order in ("pair", "seq"):
+        got, R = _gn_fwd_emulate(row, order)
+        for name in ("y", "stats"):
+            ratio, rel = check_bound(f"{name} {order}", got[name], *R[name])
+            assert ratio <= 1.0
+            if name == "y" and row[1] == "bf16":
+                assert rel <= rel_l2_bar(R["y"][0]), (rel, rel_l2_bar(R["y"][0]))
+
+
+@pytest.mark.parametrize("row", GN.BWD_ROWS, ids=[GN.row_id(r) for r in GN.BWD_ROWS])
+def test_groupnorm_backward_bounds_accept_both_emulated_kernels(row):
+    for kernel, order in (("stream", "pair"), ("stream", "seq"), ("reg", "pair"), ("reg", "seq")):
+        got, R = _gn_bwd_emulate(row, kernel, order)
+        for name in BWD_OUT:
+            ratio, rel = check_bound(f"{name} {kernel} {order}", got[name], *R[name])
+            assert ratio <= 1.0
+            if name == "dx" and row[1] == "bf16":
+                assert rel <= rel_l2_bar(R["dx"][0]), (rel, rel_l2_bar(R["dx"][0]))
+
+
+def _gn_n(row):
+    C0, C1, P, G = row[3]
+    return (C0 + C1) // G * P
+
+
+# fault -> the rows it is claimed for.  A pixel missing from a sum moves it by that pixel's share: on a spike that is 40 times the
+# typical term, on a plain pixel about 1 / n of the sum, which the summation bound (n + 8) 2^-23 overtakes near n = 4096 -- so a plain
+# pixel is claimed up to n = 2048.  The backward's bounds are loose on the offset draw (e_xh carries |x| + |mean| = 2000 against a
+# spread of 0.01): only the fault that reads x itself is claimed there.
+_loose = lambda r: r[5] == "offset" and len(r) == 8
+GN_FWD_FAULTS = {
+    "last_pixel": lambda r: r[5] == "spiked" or _gn_n(r) <= 2048,
+    "tail_pixel": lambda r: _gn_n(r) <= 2048,
+    "no_pivot": lambda r: r[5] == "offset",
+    "group_off_by_one": lambda r: True,
+    "no_eps": lambda r: r[5] == "constant",
+    "rstd_neighbour_image": lambda r: True,
+    "flip_lane": lambda r: r[2] == 1,
+}
+GN_BWD_FAULTS = {
+    "last_pixel": lambda r: (r[5] == "spiked" or _gn_n(r) <= 2048) and not _loose(r),
+    "tail_pixel": lambda r: _gn_n(r) <= 2048 and not _loose(r),
+    "no_silu_grad": lambda r: r[6] == 1 and not _loose(r),
+    "rstd_neighbour_image": lambda r: not _loose(r),
+    "dgamma_x": lambda r: True,
+    "drop_add0b": lambda r: r[7] == "add2",
+    "add0_twice": lambda r: r[7] in ("acc", "add2", "sums"),
+    "sum_img_after_adds": lambda r: r[7] == "sums",
+    "sum_img_neighbour": lambda r: r[7] == "sums",
+    "flip_lane": lambda r: r[2] == 1,
+}
+_FWD_CLAIMS = [(f, r) for f, rule in GN_FWD_FAULTS.items() for r in GN.FWD_ROWS if rule(r)]
+_BWD_CLAIMS = [(f, r) for f, rule in GN_BWD_FAULTS.items() for r in GN.BWD_ROWS if rule(r)]
+
+
+@pytest.mark.parametrize("fault,row", _FWD_CLAIMS, ids=[f"{f}-{GN.row_id(r)}" for f, r in _FWD_CLAIMS])
+def test_groupnorm_forward_rejects_planted_fault(fault, row):
+    got, R = _gn_fwd_emulate(row, fault=fault)
+    margin = _gn_margin(got, R, ("y", "stats"))
+    print(f"{fault} on {GN.row_id(row)}: {margin:.3g} x the bound")
+    assert margin > 1.0
+    with pytest.raises(AssertionError, match="outside the bound|non-finite"):
+        for name in ("y", "stats"):
+            check_bound(name, got[name], *R[name])
+
+
+@pytest.mark.parametrize("fault,row", _BWD_CLAIMS, ids=[f"{f}-{GN.row_id(r)}" for f, r in _BWD_CLAIMS])
+def test_groupnorm_backward_rejects_planted_fault(fault, row):
+    """in the arithmetic of the kernel the row runs on; held against the outputs the GPU row checks"""
+    got, R = _gn_bwd_emulate(row, "reg" if "reg" in row[0] else "stream", fault=fault)
+    names = ("sum_img", "sum_all") if fault.startswith("sum_img") else ("dx", "dgamma", "dbeta") + (("sum_img", "sum_all") if row[7] == "sums" else ())
+    margin = _gn_margin(got, R, names)
+    print(f"{fault} on {GN.row_id(row)}: {margin:.3g} x the bound")
+    assert margin > 1.0
+
+
+def test_groupnorm_every_fault_is_claimed_somewhere():
+    assert {f for f, _ in _FWD_CLAIMS} == set(GN_FWD_FAULTS) and {f for f, _ in _BWD_CLAIMS} == set(GN_BWD_FAULTS)
+
+
+_BF16_FWD = [r for r in GN.FWD_ROWS if r[1] == "bf16"]
+_BF16_BWD = [r for r in GN.BWD_ROWS if r[1] == "bf16"]
+
+
+@pytest.mark.parametrize("row", _BF16_FWD + _BF16_BWD, ids=[GN.row_id(r) for r in _BF16_FWD + _BF16_BWD])
+def test_groupnorm_rel_l2_bar_rejects_truncated_store(row):
+    """truncation instead of round-to-nearest-even at the bf16 store stays inside twice the per-element bound; the rel-L2 bar of the
+    storage precision is what rejects it, on every bf16 row"""
+    if len(row) == 7:
+        (got, R), name = _gn_fwd_emulate(row, fault="trunc_store"), "y"
+    else:
+        (got, R), name = _gn_bwd_emulate(row, "reg" if "reg" in row[0] else "stream", fault="trunc_store"), "dx"
+    ref = R[name][0]
+    rel, bar = float((got[name].double() - ref).norm() / ref.norm()), rel_l2_bar(ref)
+    print(f"trunc_store on {GN.row_id(row)}: rel-L2 {rel:.3e} = {rel / bar:.2f} x the bar")
+    assert rel > bar
+
+
+# the fused forward epilogues: statistics in two passes over the bf16-rounded y.  (N, P, C, G) of the maps they run on
+TWO_PASS = sorted({(r[2], r[1] * r[1], r[4], GN.FUSED_G) for r in GN.GNF_ROWS})
+FUSED_BWD = sorted({(r[2], r[1] * r[1], r[3], GN.FUSED_G) for r in GN.GNB_ROWS})
+
+
+@pytest.mark.parametrize("N,P,C,G", FUSED_BWD)
+def test_groupnorm_fused_backward_shapes_accept_the_emulation(N, P, C, G):
+    """the fused backward epilogues compute as gn_bwd_kernel does, on an fp32 dz, with up to two addends and a bf16 store"""
+    x, dz = gn_draw(N, P, C, "plain", 3 * P + C, "bwd", G, "f32")
+    x = x.bfloat16().float()
+    g = torch.Generator().manual_seed(C + P)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    adds = [torch.randn(N, P, C, generator=g).bfloat16().float(), (0.5 * torch.randn(N, P, C, generator=g)).bfloat16().float()]
+    stats = gn_stats_in(x, G, 1e-6)
+    R = gn_bwd_ref(x, dz, stats[..., 0], stats[..., 1], gamma, beta, G, True, "bf16", adds)
+    for order in ("pair", "seq"):
+        got = _gn_emul_bwd(x, dz, stats, gamma, beta, G, True, "bf16", "stream", adds, None, order)
+        for name in BWD_OUT:
+            assert check_bound(name, got[name], *R[name])[0] <= 1.0
+    for fault in ("last_pixel", "drop_add0b", "add0_twice", "sum_img_after_adds"):
+        got = _gn_emul_bwd(x, dz, stats, gamma, beta, G, True, "bf16", "stream", adds, None, "pair", fault=fault)
+        margin = _gn_margin(got, R, ("sum_img",) if fault.startswith("sum_img") else ("dx", "dgamma", "dbeta"))
+        print(f"fused backward {fault} {N}x{P}x{C}: {margin:.3g} x the bound")
+        assert margin > 1.0
+
+
+@pytest.mark.parametrize("N,P,C,G", TWO_PASS)
+@pytest.mark.parametrize("draw", ["plain", "spiked", "constant"])
+def test_groupnorm_two_pass_bounds_accept_the_emulation_and_reject_a_missing_pixel(N, P, C, G, draw):
+    x, _ = gn_draw(N, P, C, draw, 5 * P + C, "fwd", G, "bf16")
+    g = torch.Generator().manual_seed(C)
+    gamma, beta = 1 + 0.2 * torch.randn(C, generator=g), 0.1 * torch.randn(C, generator=g)
+    R = gn_fwd_ref(x, gamma, beta, G, 1e-6, True, "bf16", "two_pass")
+    for order in ("pair", "seq"):
+        y, stats = _gn_emul_fwd(x, gamma, beta, G, 1e-6, True, "bf16", order, "two_pass")
+        assert check_bound("y", y, *R["y"])[0] <= 1.0 and check_bound("stats", stats, *R["stats"])[0] <= 1.0
+    for fault in ("last_pixel", "rstd_neighbour_image") + (("no_eps",) if draw == "constant" else ()):
+        y, stats = _gn_emul_fwd(x, gamma, beta, G, 1e-6, True, "bf16", "pair", "two_pass", fault=fault)
+        margin = _gn_margin(dict(y=y, stats=stats), R, ("y", "stats"))
+        print(f"two_pass {fault} {N}x{P}x{C}g{G} {draw}: {margin:.3g} x the bound")
+        assert margin > 1.0

@@ -25,8 +25,8 @@ REL_BAR = {"bf16": 6.5e-3, "f32_bf16": 1e-6, "f32": 2e-6, "f32_split": 1.8e-5}
 # Routes no row reaches, with the reason.
 EXCLUDED = {
     # conv_variant takes the 64-channel small-map tile only for a fused GroupNorm epilogue of 64 channels per group (gnb_/gnf_)
-    "halo<64,2,3,64>": "only with a fused GroupNorm epilogue of 64-channel groups (values: the GroupNorm tests)",
-    "halo<64,3,3,64>": "only with a fused GroupNorm epilogue of 64-channel groups (values: the GroupNorm tests)",
+    "halo<64,2,3,64>": "only with a fused GroupNorm epilogue of 64-channel groups (values, route and guard bands: tests/test_gn_bounds_gpu.py test_fused_backward_bounds / test_fused_forward_bounds)",
+    "halo<64,3,3,64>": "only with a fused GroupNorm epilogue of 64-channel groups (values, route and guard bands: tests/test_gn_bounds_gpu.py test_fused_backward_bounds / test_fused_forward_bounds)",
 }
 # Float atomics: only the bias gradient (`dbias`) of the bf16 layout-2 kernels sums with atomicAdd (csrc/gemm.hip:
 # `if (m < d.M) atomicAdd(&d.dbias[m], accb[i][0]);` in gemm_ring_kernel and wgrad_lin_kernel, and the per-wave
