@@ -369,7 +369,19 @@ int mdm_silu_bwd(const float* x, const float* dy, float* dx, int acc, int64_t n,
  *        embedding of t[M] (dimension K, as mdm_timestep_embedding2), also stored to emb_out[M][K] when that is not NULL.
  *   bwd: dx[M][N] = dy[M][K] W[K][N] (* silu'(pre[M][N]) when pre != NULL); with splits > 1 the reduction is cut into
  *        `splits` ranges whose fp32 partial results go to slabs[splits][M][N] (pre and dx unused) for mdm_silu_bwd_sum.
- *   mdm_silu_bwd_sum: dx[n] = (sum_s slabs[s][n]) * silu'(pre[n]) (pre may be NULL: plain sum). */
+ *   mdm_silu_bwd_sum: dx[n] = (sum_s slabs[s][n]) * silu'(pre[n]) (pre may be NULL: plain sum).
+ * Which instantiation runs (host arithmetic, one rule for the query and both launchers; no device is touched):
+ *   mdm_skinny_route_of     which = 0 forward, 1 backward; has_t != 0: the input is the embedding of t (forward only) ->
+ *                           "nt<MB,NB>", "nt<MB,1,temb>", "nn<MB,1>": MB = 2 (M <= 32) | 8 sixteen-row blocks, NB sixteen-column
+ *                           blocks per workgroup (2 for a forward from a matrix with N >= 2048, N % 32 == 0; else 1: the grid is
+ *                           N / (16 NB) workgroups, times `splits` in the backward).  NULL for a shape the entry points refuse
+ *                           (the split count and the pointers are not asked here: mdm_skinny_supported, the entry points).
+ *   mdm_skinny_last_route   what the last mdm_skinny_linear_fwd / _bwd call of this thread launched; "none" before the first
+ *                           call and after a refused one
+ *   mdm_skinny_route_names  every name the two can return: fills up to `cap` of them into out (may be NULL), returns how many */
+const char* mdm_skinny_route_of(int which, int M, int N, int K, int has_t);
+const char* mdm_skinny_last_route(void);
+int mdm_skinny_route_names(const char** out, int cap);
 int mdm_skinny_supported(int M, int N, int K, int splits);
 int mdm_skinny_linear_fwd(const float* x, int ldx, const float* t, int flip_sin_to_cos, float freq_shift, float* emb_out,
                           const float* W, int ldw, const float* bias, int M, int N, int K, float* y, int ldy, float* act_out,

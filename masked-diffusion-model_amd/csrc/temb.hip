@@ -261,32 +261,77 @@ extern "C" int mdm_skinny_supported(int M, int N, int K, int splits) {
     return (M >= 1 && M <= 128 && N >= 16 && N % 16 == 0 && K >= 64 && splits >= 1 && K % (64 * splits) == 0) ? 1 : 0;
 }
 
+// ---- the routes (mdm_skinny_route_of / mdm_skinny_last_route): which instantiation a shape runs on.  skinny_route is the only
+// statement of the rule; both launchers take the kernel AND the grid from the row it names.
+//   MB   (16-row blocks per workgroup)      2 for M <= 32, else 8
+//   NB   (16-column blocks per workgroup)   forward, from a matrix: 2 for N >= 2048 and N % 32 == 0 (wide layers: two column blocks
+//        per workgroup halve the re-reads of X), else 1.  From timesteps always 1: the embedding is generated per column block, and
+//        no <MB, 2, true> kernel is compiled.  Backward: 1.
+//   TEMB the input is the embedding of t
+enum { SK_NT_2_1, SK_NT_8_1, SK_NT_2_2, SK_NT_8_2, SK_NT_2_1_T, SK_NT_8_1_T, SK_NN_2_1, SK_NN_8_1, SK_ROUTES };
+static const struct SkinnyRouteRow { const char* name; int nb; } kSkinnyRoutes[SK_ROUTES] = {
+    {"nt<2,1>", 1}, {"nt<8,1>", 1}, {"nt<2,2>", 2}, {"nt<8,2>", 2}, {"nt<2,1,temb>", 1}, {"nt<8,1,temb>", 1}, {"nn<2,1>", 1}, {"nn<8,1>", 1},
+};
+static int skinny_route(int which, int M, int N, int K, int has_t) {      // -1: refused
+    if ((which != 0 && which != 1) || M < 1 || M > 128 || N < 16 || N % 16 != 0 || K < 64 || K % 64 != 0) return -1;
+    const int big = M <= 32 ? 0 : 1;
+    if (which == 1) return has_t ? -1 : SK_NN_2_1 + big;
+    if (has_t) return SK_NT_2_1_T + big;
+    return ((N >= 2048 && N % 32 == 0) ? SK_NT_2_2 : SK_NT_2_1) + big;
+}
+static thread_local int g_skinny_route = -1;
+
+extern "C" const char* mdm_skinny_route_of(int which, int M, int N, int K, int has_t) {
+    const int r = skinny_route(which, M, N, K, has_t);
+    return r >= 0 ? kSkinnyRoutes[r].name : nullptr;
+}
+extern "C" const char* mdm_skinny_last_route(void) { return g_skinny_route >= 0 ? kSkinnyRoutes[g_skinny_route].name : "none"; }
+extern "C" int mdm_skinny_route_names(const char** out, int cap) {
+    for (int i = 0; i < SK_ROUTES && i < cap; ++i)
+        if (out) out[i] = kSkinnyRoutes[i].name;
+    return SK_ROUTES;
+}
+
 extern "C" int mdm_skinny_linear_fwd(const float* x, int ldx, const float* t, int flip_sin_to_cos, float freq_shift, float* emb_out,
                                      const float* W, int ldw, const float* bias, int M, int N, int K, float* y, int ldy, float* act_out,
                                      void* stream) {
+    g_skinny_route = -1;
     MDM_REQUIRE(mdm_skinny_supported(M, N, K, 1), "skinny_linear_fwd: unsupported shape M=%d N=%d K=%d", M, N, K);
     MDM_REQUIRE((x != nullptr) != (t != nullptr), "skinny_linear_fwd: give the input matrix OR the timesteps");
     MDM_REQUIRE(W && y && ldw % 4 == 0 && ldy % 4 == 0 && (!x || ldx % 4 == 0), "skinny_linear_fwd: bad pointers / pitches");
+    const int r = skinny_route(0, M, N, K, t != nullptr);
+    MDM_REQUIRE(r >= 0, "skinny_linear_fwd: no route for M=%d N=%d K=%d", M, N, K);
     hipStream_t s = (hipStream_t)stream;
-    const int nb = (N >= 2048 && N % 32 == 0) ? 2 : 1;          // wide layers: two column blocks per workgroup halve the re-reads of X
-    dim3 grid((unsigned)(N / (16 * nb)));
+    dim3 grid((unsigned)cdiv(N, 16 * kSkinnyRoutes[r].nb));
 #define MDM_NT(MB, NB, TE) hipLaunchKernelGGL((skinny_nt_kernel<MB, NB, TE>), grid, dim3(256), 0, s, x, ldx, t, flip_sin_to_cos, freq_shift, \
                                               emb_out, W, ldw, bias, M, N, K, y, ldy, act_out)
-    if (t) { if (M <= 32) MDM_NT(2, 1, true); else MDM_NT(8, 1, true); }
-    else if (nb == 2) { if (M <= 32) MDM_NT(2, 2, false); else MDM_NT(8, 2, false); }
-    else { if (M <= 32) MDM_NT(2, 1, false); else MDM_NT(8, 1, false); }
+    switch (r) {
+        case SK_NT_2_1: MDM_NT(2, 1, false); break;
+        case SK_NT_8_1: MDM_NT(8, 1, false); break;
+        case SK_NT_2_2: MDM_NT(2, 2, false); break;
+        case SK_NT_8_2: MDM_NT(8, 2, false); break;
+        case SK_NT_2_1_T: MDM_NT(2, 1, true); break;
+        default: MDM_NT(8, 1, true); break;
+    }
 #undef MDM_NT
-    return launch_status("skinny_linear_fwd");
+    const int rc = launch_status("skinny_linear_fwd");
+    if (rc == 0) g_skinny_route = r;
+    return rc;
 }
 
 extern "C" int mdm_skinny_linear_bwd(const float* dy, int lddy, const float* W, int ldw, int M, int N, int K, int splits, const float* pre,
                                      float* dx, float* slabs, void* stream) {
+    g_skinny_route = -1;
     MDM_REQUIRE(mdm_skinny_supported(M, N, K, splits), "skinny_linear_bwd: unsupported shape M=%d N=%d K=%d splits=%d", M, N, K, splits);
     MDM_REQUIRE(dy && W && lddy % 4 == 0 && (splits > 1 ? slabs != nullptr : dx != nullptr), "skinny_linear_bwd: bad pointers / pitches");
-    dim3 grid((unsigned)(N / 16), (unsigned)splits);
-    if (M <= 32) hipLaunchKernelGGL((skinny_nn_kernel<2, 1>), grid, dim3(256), 0, (hipStream_t)stream, dy, lddy, W, ldw, M, N, K, pre, dx, slabs);
+    const int r = skinny_route(1, M, N, K, 0);
+    MDM_REQUIRE(r >= 0, "skinny_linear_bwd: no route for M=%d N=%d K=%d", M, N, K);
+    dim3 grid((unsigned)cdiv(N, 16 * kSkinnyRoutes[r].nb), (unsigned)splits);
+    if (r == SK_NN_2_1) hipLaunchKernelGGL((skinny_nn_kernel<2, 1>), grid, dim3(256), 0, (hipStream_t)stream, dy, lddy, W, ldw, M, N, K, pre, dx, slabs);
     else hipLaunchKernelGGL((skinny_nn_kernel<8, 1>), grid, dim3(256), 0, (hipStream_t)stream, dy, lddy, W, ldw, M, N, K, pre, dx, slabs);
-    return launch_status("skinny_linear_bwd");
+    const int rc = launch_status("skinny_linear_bwd");
+    if (rc == 0) g_skinny_route = r;
+    return rc;
 }
 
 extern "C" int mdm_silu_bwd_sum(const float* pre, const float* slabs, int nslab, int64_t n, float* dx, void* stream) {

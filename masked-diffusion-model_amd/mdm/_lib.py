@@ -470,6 +470,27 @@ def gn_route_names():
     return [v.decode() for v in arr]
 
 
+def skinny_route_of(which, M, N, K, has_t=False):
+    """The kernel mdm_skinny_linear_fwd (which = 0) / mdm_skinny_linear_bwd (1) would launch, e.g. "nt<2,1,temb>", without
+    launching (mdm_skinny_route_of); None for a shape they refuse."""
+    r = load().mdm_skinny_route_of(which, M, N, K, int(bool(has_t)))
+    return None if r is None else r.decode()
+
+
+def skinny_last_route():
+    """Kernel of the last mdm_skinny_linear_fwd / _bwd call on this thread (mdm_skinny_last_route); "none" after a refused one."""
+    return load().mdm_skinny_last_route().decode()
+
+
+def skinny_route_names():
+    """Every name skinny_route_of() / skinny_last_route() can return."""
+    lib = load()
+    n = lib.mdm_skinny_route_names(None, 0)
+    arr = (C.c_char_p * n)()
+    lib.mdm_skinny_route_names(arr, n)
+    return [v.decode() for v in arr]
+
+
 def wgrad_group_accepts(**kw):
     kw.pop("_flops", None)
     return bool(load().mdm_wgrad_group_accepts(C.byref(_desc(kw))))

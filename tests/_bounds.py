@@ -134,6 +134,61 @@ A group's dx sums to zero, so the column sums are held against magnitudes, never
 A CPU emulation of each kernel's arithmetic in fp32 (tests/test_bounds_cpu.py: pivot sums in two orders, the two-pass forward, both
 backward forms, the adds, one store rounding) stays inside these bounds on every row the GPU tests use, and each planted fault
 leaves them.  rel-L2 bar of the bf16 y and dx: REL_L2_MARGIN times the rel-L2 of rne_bf16(ref), as for attention.
+
+The time-embedding path (csrc/temb.hip) and the helper kernels at the end of csrc/norm.hip
+-------------------------------------------------------------------------------------------
+All fp32; every reference is an fp64 function of exactly the stored inputs.
+
+skinny forward, y = x W^T + b:  `check` with k_terms = K + 1, store "f32", mag = |x| |W|^T + |b| (four wave partials, their sum in
+LDS order, the bias: fp32 additions in some order).  act_out is held against silu of the y THE KERNEL STORED (the register value it
+applied silu to), not of the reference:
+
+    |act - silu(y)| <= u |silu(y)| + (1 + u) (EPS_EXP + 2^-23 |y| + 2^-22) |silu(y)|         (the silu term above, u = 2^-24)
+
+so an act_out taken from another element or from the sum before the bias is off by the full difference, not by the error of y.
+
+embedding (emb_out of the skinny kernel, temb_kernel):  e[n][j | half + j] = sin | cos (a), a = t_n exp(-j c), c = ln(1e4) / (half -
+shift), in fp32 as  a^ = t * expf(-(float)j * (logf(10000.f) / ((float)half - shift))).  logf, expf, sinf and cosf are
+__ocml_{log,exp,sin,cos}_f32 (__clang_hip_math.h), which AMD's public tables -- the OCML document of the ROCm device libraries
+and the math API table of the HIP documentation, the sources EPS_RSQ quotes -- give as 1 ULP (logf, expf) and 2 ULP at most (sinf,
+cosf over the full range).  EPS_LIBM = 4 x 2^-23 takes four times one ulp (<= 2^-23 relative) for logf and expf; E_TRIG = 4 x 2 x
+2^-24 = 2^-21 ABSOLUTE takes four times two ulps of a value below 1 (2^-24 each; of the value 1 itself: four ulps).  (float)half - shift is
+exact.  c^ = c (1 + d), |d| <= EPS_LIBM + 2^-24 (logf, the division); the exponent -(float)j c^ takes one more 2^-24, and |j c| <=
+ln(1e4) because j <= half - shift: its ABSOLUTE error is at most ln(1e4) (EPS_LIBM + 2^-23), which is relative on the exponential;
+expf adds EPS_LIBM, the product with t 2^-24:
+
+    e_a = exp(ln(1e4) (EPS_LIBM + 2^-23)) (1 + EPS_LIBM) (1 + 2^-24) - 1            (6.0e-6: 51 x 2^-23)
+    |e - ref| <= |a| e_a + E_TRIG                                                   sin, cos are 1-Lipschitz
+
+At j = 0 the exponent is -0.0, expf gives exactly 1 and a^ = t exactly: that column is held to E_TRIG alone, at t up to 1000.  The
+pad column of an odd dim (temb_kernel) is exactly +0.
+
+TEMB layer (x == NULL): y is held against the emb_out the kernel stored -- the register tile it multiplied -- so the contraction
+bound is the plain one.  Without emb_out the reference is the fp64 embedding and the bound grows by (embedding bound) |W|^T.
+
+skinny backward, dx = dy W.  Slab s of a split launch is held against the fp64 partial sum over k in [s K / splits, (s + 1) K /
+splits) with k_terms = K / splits.  silu'(p) = sigma (1 + p (1 - sigma)) as in the GroupNorm section with an exact argument:
+
+    e_silu' = (EPS_EXP + 2^-23 |p| + 2^-22 + 2^-22) (1 + 2 |p|) sigma                ABSOLUTE
+    unsplit with pre:   |silu'| (u |acc| + (1 + u) gamma mag) + mag e_silu',   gamma = (K + 8) 2^-23
+    silu_bwd_sum of the slabs HANDED to it:  ref = (sum_s slab_s) silu'(pre),
+        u |ref| + (1 + u) ((nslab + 8) 2^-23 sum |slab| |silu'| + sum |slab| e_silu');     pre == NULL: silu' = 1, e_silu' = 0
+
+silu_fwd: the silu term, wrapped with u.  silu_bwd: dx = dy silu'(x): u |ref| + (1 + u) |dy| e_silu' (e_silu' carries 2^-22 for the
+two products); acc = 1 adds 2^-24 (|prior| + |g|) for the addition.
+
+colsum of dY [N][P][C] (bf16 upcasts exactly):  per_img[n][c] = sum_p: (P + 8) 2^-23 sum_p |dY| (32 pixel-lane partials, then their
+32-term sum), + 2^-24 (|prior| + sum_p |dY|) when acc_img = 1.  dbias[c] = prior + sum_{n,p}: (N P + 8) 2^-23 (|prior| + sum |dY|).
+fp32: one writer per channel and a fixed order, two runs give the same bits.  bf16: the images meet through float atomics -- bound
+only.
+
+add, add3, sumpool2 with acc = 1, the layout converters: bit exact.  add3(x, y) has the bits of (x.float() + y.float()).to(storage),
+add3(x, NULL) and the converters move bits unchanged, pad channels C .. Cp - 1 are +0, sumpool2 with acc = 1 is ((a + b) + c) + d in
+fp32, + prior, one rounding (as test_avgpool2's accumulate case).
+
+A CPU emulation in fp32 (tests/_temb_rows.py: four wave partials over k summed w0 + w1 + w2 + w3, slabs summed in order, silu and
+silu' in fp32, the embedding in fp32 numpy, colsum as 32 pixel-lane partials and their 32-term sum) stays inside these bounds on
+every row, and each planted fault leaves them (tests/test_bounds_cpu.py).
 """
 import torch
 import torch.nn.functional as F
@@ -616,3 +671,105 @@ def rel_l2_bar(ref):
     """REL_L2_MARGIN x the rel-L2 of rne_bf16(ref): the bar of a bf16 output (module docstring)."""
     ref = ref.double()
     return REL_L2_MARGIN * float((rne_bf16(ref).double() - ref).norm() / (ref.norm() + 1e-300))
+
+
+# ------------------------------------------------------------------ time-embedding path and helper kernels (module docstring)
+LN1E4 = 9.210340371976184            # ln(1e4)
+EPS_LIBM = 4 * 2.0 ** -23            # logf, expf: 4 x 1 ULP, relative
+E_TRIG = 2.0 ** -21                  # sinf, cosf: 4 x 2 ULP of a value below 1, absolute
+E_ARG = float(torch.tensor(LN1E4 * (EPS_LIBM + 2.0 ** -23), dtype=torch.float64).exp()) * (1 + EPS_LIBM) * (1 + 2.0 ** -24) - 1
+
+
+def temb_ref(t, dim, flip, shift):
+    """t [M] as stored -> (ref, bound) [M][dim] of the sinusoidal embedding: [sin | cos] (flip = 0) or [cos | sin] of
+    t exp(-j ln(1e4) / (dim // 2 - shift)); the pad column of an odd dim is 0 with bound 0."""
+    t = _f64(t).reshape(-1)
+    half = dim // 2
+    a = t[:, None] * torch.exp(-torch.arange(half, dtype=torch.float64) * (LN1E4 / (half - float(shift))))[None]
+    e = a.abs() * E_ARG + E_TRIG
+    e[:, 0] = E_TRIG
+    s, c = torch.sin(a), torch.cos(a)
+    parts, bounds = ([c, s] if flip else [s, c]), [e, e]
+    if dim & 1:
+        z = torch.zeros(t.shape[0], 1, dtype=torch.float64)
+        parts, bounds = parts + [z], bounds + [z]
+    return torch.cat(parts, 1), torch.cat(bounds, 1)
+
+
+def linear_ref(x, W, bias=None):
+    """(ref, mag) of x W^T + bias: x [M][K], W [N][K], bias [N] as stored"""
+    x, W = _f64(x), _f64(W)
+    ref, mag = x @ W.t(), x.abs() @ W.abs().t()
+    if bias is not None:
+        ref, mag = ref + _f64(bias), mag + _f64(bias).abs()
+    return ref, mag
+
+
+def silu_ref(y):
+    """(silu(y), bound) of the fp32 v / (1 + expf(-v)) of the stored y"""
+    y = _f64(y)
+    s = y * torch.sigmoid(y)
+    return _wrap(s, (EPS_EXP + 2.0 ** -23 * y.abs() + 2.0 ** -22) * s.abs(), U_F32)
+
+
+def silu_grad_ref(p):
+    """(silu'(p), its ABSOLUTE error bound) of the fp32 sigma (1 + p (1 - sigma)); p None: (1, 0)"""
+    if p is None:
+        return 1.0, 0.0
+    p = _f64(p)
+    sg = torch.sigmoid(p)
+    return sg * (1 + p * (1 - sg)), (EPS_EXP + 2.0 ** -23 * p.abs() + 2.0 ** -22 + 2.0 ** -22) * (1 + 2 * p.abs()) * sg
+
+
+def skinny_bwd_ref(dy, W, splits, pre=None):
+    """dy [M][K], W [K][N] as stored -> (ref, bound) of slabs [splits][M][N] (splits > 1: the partial sums over the k ranges) or of
+    dx [M][N] = dy W silu'(pre) (splits == 1)."""
+    dy, W = _f64(dy), _f64(W)
+    K = dy.shape[1]
+    ks = K // splits
+    g = (ks + 8) * 2.0 ** -23
+    acc = torch.stack([dy[:, s * ks:(s + 1) * ks] @ W[s * ks:(s + 1) * ks] for s in range(splits)])
+    mag = torch.stack([dy[:, s * ks:(s + 1) * ks].abs() @ W[s * ks:(s + 1) * ks].abs() for s in range(splits)])
+    cb = U_F32 * acc.abs() + (1 + U_F32) * g * mag
+    if splits > 1:
+        assert pre is None
+        return acc, cb
+    gp, e_gp = silu_grad_ref(pre)
+    if pre is None:
+        return acc[0], cb[0]
+    return acc[0] * gp, gp.abs() * cb[0] + mag[0] * e_gp
+
+
+def silu_bwd_sum_ref(slabs, pre=None):
+    """slabs [nslab][...] as HANDED to the kernel, pre [...] or None -> (ref, bound) of (sum_s slab_s) silu'(pre)"""
+    slabs = _f64(slabs)
+    nslab = slabs.shape[0]
+    gp, e_gp = silu_grad_ref(None if pre is None else _f64(pre).reshape(slabs.shape[1:]))
+    sa = slabs.abs().sum(0)
+    gpa = gp.abs() if pre is not None else 1.0
+    return _wrap(slabs.sum(0) * gp, (nslab + 8) * 2.0 ** -23 * sa * gpa + sa * e_gp, U_F32)
+
+
+def silu_bwd_ref(x, dy, prior=None):
+    """(ref, bound) of dx = (prior +) dy silu'(x)"""
+    gp, e_gp = silu_grad_ref(x)
+    dy = _f64(dy)
+    g, b = _wrap(dy * gp, dy.abs() * e_gp, U_F32)
+    if prior is not None:
+        pr = _f64(prior)
+        g, b = pr + g, b + 2.0 ** -24 * (pr.abs() + g.abs())
+    return g, b
+
+
+def colsum_ref(dY, prior_img=None, prior_bias=None):
+    """dY [N][P][C] as stored -> {"per_img": (ref, bound) [N][C], "dbias": (ref, bound) [C]}; prior_img: the values per_img
+    accumulates onto (acc_img = 1), prior_bias: what dbias held."""
+    d = _f64(dY)
+    N, P, C = d.shape
+    s, sa = d.sum(1), d.abs().sum(1)
+    r, b = s, (P + 8) * 2.0 ** -23 * sa
+    if prior_img is not None:
+        pi = _f64(prior_img)
+        r, b = pi + s, b + 2.0 ** -24 * (pi.abs() + sa)
+    pb = _f64(prior_bias) if prior_bias is not None else torch.zeros(C, dtype=torch.float64)
+    return {"per_img": (r, b), "dbias": (pb + s.sum(0), (N * P + 8) * 2.0 ** -23 * (pb.abs() + sa.sum(0)))}

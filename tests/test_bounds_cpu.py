@@ -627,3 +627,118 @@ def test_groupnorm_two_pass_bounds_accept_the_emulation_and_reject_a_missing_pix
         margin = _gn_margin(dict(y=y, stats=stats), R, ("y", "stats"))
         print(f"two_pass {fault} {N}x{P}x{C}g{G} {draw}: {margin:.3g} x the bound")
         assert margin > 1.0
+
+
+# ------------------------------------------------------------------ the time-embedding path and the helper kernels
+# An fp32 emulation of each kernel's arithmetic (tests/_temb_rows.py) stays inside the bounds of tests/_bounds.py on every row the
+# GPU tests run, and every planted fault leaves them on every row that can show it.
+import _temb_rows as TE  # noqa: E402
+from _bounds import colsum_ref, silu_bwd_ref, silu_bwd_sum_ref, silu_ref, temb_ref  # noqa: E402
+
+
+@pytest.mark.parametrize("row", TE.FWD_ROWS, ids=[TE.fwd_id(r) for r in TE.FWD_ROWS])
+def test_skinny_forward_bounds_accept_the_emulated_kernel(row):
+    T = TE.fwd_problem(row)
+    ratios = TE.check_fwd(row, T, TE.emulate_fwd(row, T))
+    print("emulation err / bound", TE.fwd_id(row), ratios)
+    assert max(ratios.values()) <= 1.0
+
+
+@pytest.mark.parametrize("row", TE.BWD_ROWS, ids=[TE.bwd_id(r) for r in TE.BWD_ROWS])
+def test_skinny_backward_bounds_accept_the_emulated_kernel(row):
+    T = TE.bwd_problem(row)
+    ratios = TE.check_bwd(row, T, TE.emulate_bwd(row, T))
+    print("emulation err / bound", TE.bwd_id(row), ratios)
+    assert max(ratios.values()) <= 1.0
+
+
+_TE_FWD_CLAIMS = [(f, r) for f, rule in TE.FWD_FAULTS.items() for r in TE.FWD_ROWS if rule(r)]
+_TE_BWD_CLAIMS = [(f, r) for f, rule in TE.BWD_FAULTS.items() for r in TE.BWD_ROWS if rule(r)]
+
+
+@pytest.mark.parametrize("fault,row", _TE_FWD_CLAIMS, ids=[f"{f}-{TE.fwd_id(r)}" for f, r in _TE_FWD_CLAIMS])
+def test_skinny_forward_rejects_planted_fault(fault, row):
+    T = TE.fwd_problem(row)
+    with pytest.raises(AssertionError, match="outside the bound|non-finite"):
+        TE.check_fwd(row, T, TE.emulate_fwd(row, T, fault))
+
+
+@pytest.mark.parametrize("fault,row", _TE_BWD_CLAIMS, ids=[f"{f}-{TE.bwd_id(r)}" for f, r in _TE_BWD_CLAIMS])
+def test_skinny_backward_rejects_planted_fault(fault, row):
+    T = TE.bwd_problem(row)
+    with pytest.raises(AssertionError, match="outside the bound|non-finite"):
+        TE.check_bwd(row, T, TE.emulate_bwd(row, T, fault))
+
+
+def test_skinny_every_fault_is_claimed_somewhere():
+    assert {f for f, _ in _TE_FWD_CLAIMS} == set(TE.FWD_FAULTS) and {f for f, _ in _TE_BWD_CLAIMS} == set(TE.BWD_FAULTS)
+    # the suspected launcher defect is claimed on the row that was added for it
+    assert [r for f, r in _TE_FWD_CLAIMS if f == "upper_half_unwritten"] == [TE.FWD_ROWS[-1]]
+
+
+@pytest.mark.parametrize("nslab,pre,n", TE.SUM_ROWS)
+def test_silu_bwd_sum_bounds_accept_the_emulation_and_reject_its_faults(nslab, pre, n):
+    g = torch.Generator().manual_seed(nslab + n)
+    slabs, p = torch.randn(nslab, n, generator=g), (torch.randn(n, generator=g) * 2.5 if pre else None)
+    ratio, _ = check_bound("sum", TE.emulate_sum(slabs, p), *silu_bwd_sum_ref(slabs, p))
+    assert ratio <= 1.0
+    for fault in (["last_slab_left_out"] if nslab > 1 else []) + (["no_silu_grad_on_split"] if pre else []):
+        with pytest.raises(AssertionError, match="outside the bound"):
+            check_bound(fault, TE.emulate_sum(slabs, p, fault), *silu_bwd_sum_ref(slabs, p))
+
+
+@pytest.mark.parametrize("variant", TE.VARIANTS)
+@pytest.mark.parametrize("dim", [4, 64, 128, 129])
+def test_embedding_bound_accepts_fp32_numpy_and_rejects_its_faults(dim, variant):
+    t = TE.timesteps(5, dim)
+    ref, bound = temb_ref(t, dim, *variant)
+    ratio, _ = check_bound("temb", TE.temb32(t, dim, *variant), ref, bound)
+    print("emulation err / bound", dim, variant, ratio)
+    assert ratio <= 1.0
+    for fault in ("shift_swapped", "j_off_by_one", "sin_cos_swapped"):
+        with pytest.raises(AssertionError, match="outside the bound"):
+            check_bound(fault, TE.temb32(t, dim, *variant, fault=fault), ref, bound)
+    if dim & 1:
+        assert float(ref[:, -1].abs().max()) == 0.0 and float(bound[:, -1].max()) == 0.0
+    # column j = 0 is held to the accuracy of sinf / cosf alone, at t up to 1000
+    assert float(bound[:, 0].max()) == 2.0 ** -21 and float(t.max()) == 1000.0
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_silu_bounds_accept_fp32_and_reject_a_missing_factor(n):
+    g = torch.Generator().manual_seed(n)
+    x = torch.rand(n, generator=g) * 40 - 20
+    dy, prior = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    assert check_bound("silu", TE.silu32(x), *silu_ref(x))[0] <= 1.0
+    gz = dy * TE.silu_grad32(x)
+    assert check_bound("silu_bwd", gz, *silu_bwd_ref(x, dy))[0] <= 1.0
+    assert check_bound("silu_bwd acc", prior + gz, *silu_bwd_ref(x, dy, prior))[0] <= 1.0
+    with pytest.raises(AssertionError, match="outside the bound"):
+        check_bound("ignored acc", gz, *silu_bwd_ref(x, dy, prior))
+    with pytest.raises(AssertionError, match="outside the bound"):
+        check_bound("sigmoid for silu'", dy / (1 + torch.exp(-x)), *silu_bwd_ref(x, dy))
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("C", TE.COLSUM_CS)
+def test_colsum_bounds_accept_the_emulation_and_reject_its_faults(dt, C):
+    for P, N, per_img, acc_img, dbias in TE.colsum_rows(dt, C):
+        d, pi, pb = TE.colsum_problem(dt, C, P, N)
+        R = colsum_ref(d, pi if acc_img else None, pb)
+        got = dict(zip(("per_img", "dbias"), TE.emulate_colsum(d, pi if acc_img else None, pb)))
+        names = (["per_img"] if per_img else []) + (["dbias"] if dbias else [])
+        for name in names:
+            assert check_bound(f"colsum {name}", got[name], *R[name])[0] <= 1.0
+        for fault in (["no_lane_31"] if P >= 32 else []) + (["store_not_accumulate"] if acc_img or dbias else []):
+            bad = dict(zip(("per_img", "dbias"), TE.emulate_colsum(d, pi if acc_img else None, pb, fault)))
+            with pytest.raises(AssertionError, match="outside the bound"):
+                for name in names:
+                    check_bound(f"{fault} {name}", bad[name], *R[name])
+
+
+def test_add3_bit_test_rejects_a_truncating_bf16_store():
+    g = torch.Generator().manual_seed(3)
+    x, y = torch.randn(4096, generator=g).bfloat16(), torch.randn(4096, generator=g).bfloat16()
+    want = (x.float() + y.float()).to(torch.bfloat16)
+    bad = trunc_bf16((x.float() + y.float()).double())
+    assert not torch.equal(want.view(torch.int16), bad.view(torch.int16))

@@ -122,7 +122,9 @@ def test_the_parsed_tables_are_the_types_the_wrappers_rely_on():
     assert _lib._PROTOS["mdm_gn_last_route"] == ([], C.c_char_p) and _lib._PROTOS["mdm_gn_route_names"] == ([C.c_void_p, C.c_int32], C.c_int32)
     assert dict(_lib.GnDesc._fields_)["drop_base"] is C.c_uint64 and dict(_lib.GemmDesc._fields_)["wtap"] is C.c_int64
     assert _lib._PARAMS["mdm_add"] == ["dtype", "dst", "src", "n", "stream"]
-    assert len(_lib._PROTOS) == 87 and len(_lib.EXPORTS) == 87
+    assert _lib._PROTOS["mdm_skinny_route_of"] == ([C.c_int32] * 5, C.c_char_p) and _lib._PROTOS["mdm_skinny_last_route"] == ([], C.c_char_p)
+    assert _lib._PROTOS["mdm_skinny_route_names"] == ([C.c_void_p, C.c_int32], C.c_int32)
+    assert len(_lib._PROTOS) == 90 and len(_lib.EXPORTS) == 90
 
 
 def test_call_binds_keywords_against_the_header_names():
