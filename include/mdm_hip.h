@@ -146,6 +146,12 @@ const char* mdm_gemm_last_route(void);
  * touched and the record of the last launch stays as it is.  "none" (and mdm_last_error) when the descriptor is refused. */
 const char* mdm_gemm_route_of(const mdm_gemm_desc* desc_host);
 const char* mdm_gemm_pair_route_of(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host);
+/* The first launch mdm_gemm(desc) would make, without making it.  out[0] workgroups (grid.x), out[1] grid.z, out[2] threads per
+   workgroup, out[3] dynamic LDS bytes, out[4], out[5] the route's output tile (0, 0: the grid is not a tiling of the output).
+   0, or -1 with mdm_last_error set exactly where mdm_gemm refuses.  Host arithmetic; pointers are not dereferenced. */
+int mdm_gemm_launch_of(const mdm_gemm_desc* desc, int32_t out[6]);
+/* The fused launch of mdm_gemm_pair(a, b); 1 and zeros for "pair:two launches" (ask mdm_gemm_launch_of about each). */
+int mdm_gemm_pair_launch_of(const mdm_gemm_desc* a, const mdm_gemm_desc* b, int32_t out[6]);
 /* every route name mdm_gemm_last_route can return: fills up to `cap` of them into out (may be NULL), returns how many there are */
 int mdm_gemm_route_names(const char** out, int cap);
 

@@ -3519,65 +3519,89 @@ static int lds_opt_in(int bytes) {
     return 0;
 }
 
-// What mdm_gemm decides before it launches: the tile family, the reduction split, where split-K partials go.
+// What mdm_gemm decides before it chooses a route: the reduction split and where split-K partials go.
 struct Resolved {
     mdm_gemm_desc d;
-    bool big, tap_split;
+    bool tap_split;
     int zouter;
-    int64_t tiles, slab;        // output tiles of the chosen shape; bytes of one dense fp32 copy of the output
+    int64_t slab;               // bytes of one dense fp32 copy of the output
 };
-// The grid of a launch: tiles of the shape resolve chose -- or of the BM x BN shape a route took instead -- by the batch / tap / split count
-static dim3 grid_of(const Resolved& r) { return dim3((unsigned)r.tiles, 1, (unsigned)(r.zouter * r.d.splitk)); }
-template <int BM, int BN>
-static dim3 grid_of(const Resolved& r) {
-    return dim3((unsigned)((int64_t)cdiv(r.d.M, BM) * cdiv(r.d.N, BN)), 1, (unsigned)(r.zouter * r.d.splitk));
+// The generic tile rule of the bf16 routes that come in a 128 x 128 and a 64 x 64 form: 128 x 128 when that still yields enough
+// workgroups; weight gradients (layout 2: small output, huge reduction, split-K supplies the parallelism) take the big tile
+// whenever it fits.  A rule about the descriptor, not a launch geometry: a route launches the grid of its own row's tile.
+static bool big_tile(const mdm_gemm_desc& d, int zouter) {
+    return d.dtype == MDM_BF16 && d.N >= 128 && d.M >= 128 &&
+           (d.layout == 2 ? d.K >= 2048 : (int64_t)cdiv(d.M, 128) * cdiv(d.N, 128) * zouter >= kBigMinTiles);
 }
+// The first launch of a route, planned from the resolved descriptor alone (route_geometry): what the launcher hands to
+// hipLaunchKernelGGL and what mdm_gemm_launch_of reports.
+struct Launch {
+    int64_t gx, gz;             // workgroups (grid.x); grid.z
+    int threads, lds;           // per workgroup; dynamic LDS bytes
+    int tile_m, tile_n;         // the route's output tile (0, 0: the grid is not a tiling of the output)
+    int arg[2];                 // kernel arguments that are geometry: wgrad_lin's tiles per tap / split, halo_mixed's count of 256-pixel
+                                // tiles and the pixels they cover, a pair's workgroups of `a`
+};
+// What is left of a launcher: the LDS opt-in, the planned numbers, the kernel's arguments.
+template <auto KERNEL, typename... Args>
+static int launch_planned(const Launch& L, hipStream_t s, const Args&... args) {
+    if (int rc = lds_opt_in<KERNEL>(L.lds)) return rc;
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)L.gx, 1, (unsigned)L.gz), dim3((unsigned)L.threads), (unsigned)L.lds, s, args...);
+    return 0;
+}
+// Geometry of the kernels whose workgroup size and dynamic LDS are fixed by the instantiation (ring, f32_mfma, bf16, lin_split)
+template <int THREADS, int LDS>
+static int geom_fixed(const Resolved&, Launch& L) {
+    L.threads = THREADS;
+    L.lds = LDS;
+    return 0;
+}
+constexpr int ring_lds(int BM, int BN, int NSTAGE) { return NSTAGE * (BM + BN) * 64 * 2; }
 // LDS floor of the fused GroupNorm-backward epilogue (epilogue_tile_gnb, 64-pixel tiles): the fp32 tile (16 KiB), the column-sum
 // scratch [32 quantities][512] behind it (64 KiB), the partial sums [32 x 8 columns][4 parts] (4 KiB), the group sums [4][16][2] (512 B)
 constexpr int kGnbLdsBytes = 16384 + 65536 + 4096 + 512;
 
-template <int BM, int BN, int LAYOUT, int NSTAGE, bool CONV>
-static int launch_ring_one(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
-    constexpr int bytes = NSTAGE * (BM + BN) * 64 * 2;
-    if (int rc = lds_opt_in<&gemm_ring_kernel<BM, BN, LAYOUT, NSTAGE, CONV, 8>>(bytes)) return rc;
-    hipLaunchKernelGGL((gemm_ring_kernel<BM, BN, LAYOUT, NSTAGE, CONV, 8>), grid, dim3(512), bytes, s, d);
-    return 0;
-}
 template <int BM, int BN, int NSTAGE>
-static int launch_ring(const Resolved& r, hipStream_t s) {
+static int launch_ring(const Resolved& r, const Launch& L, hipStream_t s) {
     const mdm_gemm_desc& d = r.d;
-    const dim3 grid = grid_of(r);
     const bool c = d.conv != 0;
     switch (d.layout) {
-        case 0: return c ? launch_ring_one<BM, BN, 0, NSTAGE, true>(d, grid, s) : launch_ring_one<BM, BN, 0, NSTAGE, false>(d, grid, s);
-        case 1: return c ? launch_ring_one<BM, BN, 1, NSTAGE, true>(d, grid, s) : launch_ring_one<BM, BN, 1, NSTAGE, false>(d, grid, s);
-        default: return c ? launch_ring_one<BM, BN, 2, NSTAGE, true>(d, grid, s) : launch_ring_one<BM, BN, 2, NSTAGE, false>(d, grid, s);
+        case 0: return c ? launch_planned<&gemm_ring_kernel<BM, BN, 0, NSTAGE, true, 8>>(L, s, d)
+                        : launch_planned<&gemm_ring_kernel<BM, BN, 0, NSTAGE, false, 8>>(L, s, d);
+        case 1: return c ? launch_planned<&gemm_ring_kernel<BM, BN, 1, NSTAGE, true, 8>>(L, s, d)
+                        : launch_planned<&gemm_ring_kernel<BM, BN, 1, NSTAGE, false, 8>>(L, s, d);
+        default: return c ? launch_planned<&gemm_ring_kernel<BM, BN, 2, NSTAGE, true, 8>>(L, s, d)
+                        : launch_planned<&gemm_ring_kernel<BM, BN, 2, NSTAGE, false, 8>>(L, s, d);
     }
 }
 
-// dynamic LDS of a conv_lin2_body tile (launch_lin2, and the 1x1 role of launch_pair / launch_pair_small)
-template <int BM, int BN, int NSTAGE>
-static int lin2_lds_bytes(const mdm_gemm_desc& d) {
-    int bytes = NSTAGE * (BM + BN) * 64 * 2;
-    return d.gnb_x && bytes < kGnbLdsBytes ? kGnbLdsBytes : bytes;      // fused GroupNorm backward (64 x 64 tiles)
+// conv_lin2_body tiles (launch_lin2, and the 1x1 role of a pair): the software-pipelined variant
+template <int BM, int BN, int NSTAGE, int WR, int WC>
+static int geom_lin2(const Resolved& r, Launch& L) {
+    L.threads = 64 * WR * WC;
+    L.lds = ring_lds(BM, BN, NSTAGE);
+    if (r.d.gnb_x && L.lds < kGnbLdsBytes) L.lds = kGnbLdsBytes;      // fused GroupNorm backward (64 x 64 tiles)
+    return 0;
 }
 template <int BM, int BN, int NSTAGE, int WR, int WC>
-static int launch_lin2(const Resolved& r, hipStream_t s) {         // the software-pipelined variant
-    const mdm_gemm_desc& d = r.d;
-    const int bytes = lin2_lds_bytes<BM, BN, NSTAGE>(d);
-    const dim3 grid = BM == 64 && BN == 128 ? grid_of<64, 128>(r) : grid_of(r);      // (64 x 128 is not a tile shape of resolve)
-    if (int rc = lds_opt_in<&conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>>(bytes)) return rc;
-    hipLaunchKernelGGL((conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>), grid, dim3(64 * WR * WC), bytes, s, d);
-    return 0;
+static int launch_lin2(const Resolved& r, const Launch& L, hipStream_t s) {
+    return launch_planned<&conv_lin2_kernel<BM, BN, NSTAGE, WR, WC, 1, true, false>>(L, s, r.d);
 }
 
+// wgrad_lin: a flat grid, one work item per (tile, tap / split)
 template <int BM, int BN, int NSTAGE, int NW>
-static int launch_wgrad_lin(const Resolved& r, hipStream_t s) {      // a flat grid: one work item per (tile, tap / split)
-    constexpr int bytes = NSTAGE * (BM + BN) * 64 * 2;
-    const dim3 g = grid_of(r);
-    if (int rc = lds_opt_in<&wgrad_lin_kernel<BM, BN, NSTAGE, NW>>(bytes)) return rc;
-    hipLaunchKernelGGL((wgrad_lin_kernel<BM, BN, NSTAGE, NW>), dim3((unsigned)(int)(g.x * g.z)), dim3(64 * NW), bytes, s, r.d, (int)g.x);
+static int geom_wgrad_lin(const Resolved&, Launch& L) {
+    L.threads = 64 * NW;
+    L.lds = ring_lds(BM, BN, NSTAGE);
+    L.arg[0] = (int)L.gx;
+    L.gx *= L.gz;
+    L.gz = 1;
+    MDM_REQUIRE(L.gx < (1ll << 30), "gemm: grid too large");
     return 0;
+}
+template <int BM, int BN, int NSTAGE, int NW>
+static int launch_wgrad_lin(const Resolved& r, const Launch& L, hipStream_t s) {
+    return launch_planned<&wgrad_lin_kernel<BM, BN, NSTAGE, NW>>(L, s, r.d, L.arg[0]);
 }
 static bool wgrad_lin_eligible(const mdm_gemm_desc& d) {
     if (!(d.dtype == MDM_BF16 && d.layout == 2 && d.conv && d.OW > 0 && 64 % d.OW == 0 && (d.OH & (d.OH - 1)) == 0 &&
@@ -3604,27 +3628,25 @@ static int halo_pieces(int bm, int OH, int OW) {           // 1-KiB pieces of on
 }
 // Halo pieces per wave.  A 256-pixel tile always needs the 6-piece kernels: it has at least 41 pieces (16x16 maps: 18 * 18 / 8 -> 41;
 // 32x32: 10 * 34 / 8 -> 43; 64-wide maps give 50 > 48 and are not eligible; 8- and 4-row maps with several images per tile give 45
-// and more), so there is no "<= 4 pieces per wave" 256-pixel route; launch_halo's NPA <= 8 * NPW check is the guard.
+// and more), so there is no "<= 4 pieces per wave" 256-pixel route; geom_halo's NPA <= 8 * NPW check is the guard.
 static int halo_npw(int bm, const mdm_gemm_desc& d) { return (halo_pieces(bm, d.OH, d.OW) + 7) / 8; }
-// dynamic LDS of a conv_halo_body tile (launch_halo, and the 3x3 role of launch_pair)
-template <int BM, int NSB, int BN, int TG>
-static int halo_lds_bytes(const mdm_gemm_desc& d) {
-    int bytes = 2 * halo_pieces(BM, d.OH, d.OW) * 1024 + NSB * TG * BN * 128 + 1024;
-    if (bytes < BM * BN * 4) bytes = BM * BN * 4;                 // the tile epilogue parks the fp32 tile there
-    if (BM == 64 && d.gnb_x && bytes < kGnbLdsBytes) bytes = kGnbLdsBytes;   // fused GroupNorm backward
-    return bytes;
-}
-// The launcher's arguments are the ones a halo route's name spells.  One filter row (3 taps) per barrier; the 128-channel tile one tap.
-template <int BM, int NPW, int NSB, int BN, typename T, bool SPLIT>
-static int launch_halo(const Resolved& r, hipStream_t s) {
-    constexpr int TG = BN == 128 ? 1 : 3;
+// The arguments are the ones a halo route's name spells.  One filter row (3 taps) per barrier; the 128-channel tile one tap.
+constexpr int halo_tg(int BN) { return BN == 128 ? 1 : 3; }
+// conv_halo_body tiles of all three families (launch_halo, and the 3x3 role of a pair): do the halo and the filter stages fit
+template <int BM, int NPW, int NSB, int BN>
+static int geom_halo(const Resolved& r, Launch& L) {
     const mdm_gemm_desc& d = r.d;
-    const int NPA = halo_pieces(BM, d.OH, d.OW), bytes = halo_lds_bytes<BM, NSB, BN, TG>(d);
-    MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_halo: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
-    if (int rc = lds_opt_in<&conv_halo_kernel<BM, NPW, BN, NSB, TG, T, SPLIT>>(bytes)) return rc;
-    dim3 grid((unsigned)((int64_t)(d.M / BM) * cdiv(d.N, BN)));
-    hipLaunchKernelGGL((conv_halo_kernel<BM, NPW, BN, NSB, TG, T, SPLIT>), grid, dim3(512), bytes, s, d);
+    const int NPA = halo_pieces(BM, d.OH, d.OW);
+    L.threads = 512;
+    L.lds = 2 * NPA * 1024 + NSB * halo_tg(BN) * BN * 128 + 1024;
+    if (L.lds < BM * BN * 4) L.lds = BM * BN * 4;                 // the tile epilogue parks the fp32 tile there
+    if (BM == 64 && d.gnb_x && L.lds < kGnbLdsBytes) L.lds = kGnbLdsBytes;   // fused GroupNorm backward
+    MDM_REQUIRE(NPA <= 8 * NPW && L.lds <= 160 * 1024, "conv_halo: tile does not fit (NPA=%d, %d bytes)", NPA, L.lds);
     return 0;
+}
+template <int BM, int NPW, int NSB, int BN, typename T, bool SPLIT>
+static int launch_halo(const Resolved& r, const Launch& L, hipStream_t s) {
+    return launch_planned<&conv_halo_kernel<BM, NPW, BN, NSB, halo_tg(BN), T, SPLIT>>(L, s, r.d);
 }
 static int small_pieces(const mdm_gemm_desc& d, int bm = 64) {           // 1-KiB pieces of one conv_small halo buffer (256-byte pixel rows)
     const int imgs = bm / (d.OH * d.OW);
@@ -3638,15 +3660,18 @@ static int small_lds_bytes(const mdm_gemm_desc& d, int bm = 64, int bn = 32) {
 // only, which needs C / G == 8 and N0 % 8 == 0 (the 64 x 32 tiles fall back to the LDS epilogues)
 static int fused_gn_cpg(const mdm_gemm_desc& d) { return d.gnb_x ? d.N / d.gnb_G : (d.gnf_out ? d.N / d.gnf_G : 8); }
 template <int NPW, int BM, int BN>
-static int launch_small(const Resolved& r, hipStream_t s) {
+static int geom_small(const Resolved& r, Launch& L) {          // (launch_small, and the 3x3 role of a pair_small)
     const mdm_gemm_desc& d = r.d;
-    const int bytes = small_lds_bytes(d, BM, BN);
-    MDM_REQUIRE(small_pieces(d, BM) <= 8 * NPW && bytes <= 160 * 1024 && (BM != 64 || bytes >= kGnbLdsBytes),
-                "conv_small: tile does not fit (%d bytes)", bytes);
+    L.threads = 512;
+    L.lds = small_lds_bytes(d, BM, BN);
+    MDM_REQUIRE(small_pieces(d, BM) <= 8 * NPW && L.lds <= 160 * 1024 && (BM != 64 || L.lds >= kGnbLdsBytes),
+                "conv_small: tile does not fit (%d bytes)", L.lds);
     MDM_REQUIRE(BM == 64 || (fused_gn_cpg(d) == 8 && d.N0 % 8 == 0), "conv_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
-    if (int rc = lds_opt_in<&conv_small_kernel<NPW, BM, BN>>(bytes)) return rc;
-    hipLaunchKernelGGL((conv_small_kernel<NPW, BM, BN>), dim3((unsigned)((int64_t)(d.M / BM) * cdiv(d.N, BN))), dim3(512), bytes, s, d);
     return 0;
+}
+template <int NPW, int BM, int BN>
+static int launch_small(const Resolved& r, const Launch& L, hipStream_t s) {
+    return launch_planned<&conv_small_kernel<NPW, BM, BN>>(L, s, r.d);
 }
 // ---- the 3x3 "same" convolutions of the halo kernels: one geometry rule (halo_same3), one "does this tile fit" rule (halo_fits,
 // halo_small_map); halo_tile / halo_tile_f32 / halo_tile_f32_split / halo_small_n_split / halo_mixed_tiling add their own terms and
@@ -3716,17 +3741,22 @@ static bool halo_mixed_tiling(const mdm_gemm_desc& d, HaloMixed& t) {      // do
     t = {(int)(big_m * tn), (int)(big_m * 256), (int)rest};
     return true;
 }
-static int launch_halo_mixed(const Resolved& r, hipStream_t s) {
+static int geom_halo_mixed(const Resolved& r, Launch& L) {
     const mdm_gemm_desc& d = r.d;
     HaloMixed t;
     MDM_REQUIRE(halo_mixed_tiling(d, t), "conv_halo_mixed: the mixed tiling does not apply");
     const int npa = halo_pieces(256, d.OH, d.OW), npb = halo_pieces(128, d.OH, d.OW);
-    int bytes = std::max(2 * npa * 1024 + 2 * 3 * 64 * 128 + 1024, 2 * npb * 1024 + 3 * 3 * 64 * 128 + 1024);
-    bytes = std::max(bytes, 256 * 64 * 4);
-    MDM_REQUIRE(bytes <= 160 * 1024, "conv_halo_mixed: tile does not fit (%d bytes)", bytes);
-    if (int rc = lds_opt_in<&conv_halo_mixed_kernel<6, 2, 4, 3>>(bytes)) return rc;
-    hipLaunchKernelGGL((conv_halo_mixed_kernel<6, 2, 4, 3>), dim3((unsigned)(t.n_big + t.n_rest)), dim3(512), bytes, s, d, t.n_big, t.m_split);
+    L.gx = t.n_big + t.n_rest;
+    L.threads = 512;
+    L.lds = std::max(2 * npa * 1024 + 2 * 3 * 64 * 128 + 1024, 2 * npb * 1024 + 3 * 3 * 64 * 128 + 1024);
+    L.lds = std::max(L.lds, 256 * 64 * 4);
+    L.arg[0] = t.n_big;
+    L.arg[1] = t.m_split;
+    MDM_REQUIRE(L.lds <= 160 * 1024, "conv_halo_mixed: tile does not fit (%d bytes)", L.lds);
     return 0;
+}
+static int launch_halo_mixed(const Resolved& r, const Launch& L, hipStream_t s) {
+    return launch_planned<&conv_halo_mixed_kernel<6, 2, 4, 3>>(L, s, r.d, L.arg[0], L.arg[1]);
 }
 
 // The LAST convolution of the net (128 -> 3, padded to 8 output channels; unet6.py:505) with split products: on the register-staged
@@ -3751,15 +3781,12 @@ static int lin_split_tile(const mdm_gemm_desc& d) {
     if (d.N % 128 == 0 && (int64_t)cdiv(d.M, 128) * (d.N / 128) >= kBigMinTiles) return 128;
     return 64;
 }
+constexpr int lin_split_ns(int BN) { return BN == 64 ? MDM_LIN_SPLIT_NS64 : 4; }
+constexpr int lin_split_lds(int BN) { return lin_split_ns(BN) * (128 * 128 + BN * 128); }
 template <int BN>
-static int launch_lin_split(const Resolved& r, hipStream_t s) {
-    const mdm_gemm_desc& d = r.d;
-    constexpr int NS = BN == 64 ? MDM_LIN_SPLIT_NS64 : 4;
-    constexpr int bytes = NS * (128 * 128 + BN * 128);
-    static_assert(bytes <= 160 * 1024 && bytes >= 128 * BN * 4, "lin_split: ring / epilogue tile do not fit");
-    if (int rc = lds_opt_in<&lin_split_kernel<BN, NS>>(bytes)) return rc;
-    hipLaunchKernelGGL((lin_split_kernel<BN, NS>), dim3((unsigned)((int64_t)cdiv(d.M, 128) * (d.N / BN))), dim3(512), bytes, s, d);
-    return 0;
+static int launch_lin_split(const Resolved& r, const Launch& L, hipStream_t s) {      // 128 x BN tiles
+    static_assert(lin_split_lds(BN) <= 160 * 1024 && lin_split_lds(BN) >= 128 * BN * 4, "lin_split: ring / epilogue tile do not fit");
+    return launch_planned<&lin_split_kernel<BN, lin_split_ns(BN)>>(L, s, r.d);
 }
 constexpr int MDM_NSB256 = 2;          // filter stages of the 256-pixel bf16 halo tiles
 constexpr int MDM_SPLIT_MIN128 = 160;
@@ -3801,81 +3828,67 @@ static bool ring_eligible(const mdm_gemm_desc& d) {
     return d.K % 64 == 0;
 }
 
-template <int BM, int BN, int LAYOUT, bool SPLIT = false>
-static int launch_f32_mfma_one(const mdm_gemm_desc& d, dim3 grid, hipStream_t s) {
-    constexpr int bytes = 2 * (BM + BN) * 36 * 4;
-    if (int rc = lds_opt_in<&gemm_f32_mfma_kernel<BM, BN, LAYOUT, SPLIT>>(bytes)) return rc;
-    hipLaunchKernelGGL((gemm_f32_mfma_kernel<BM, BN, LAYOUT, SPLIT>), grid, dim3(256), bytes, s, d);
-    return 0;
-}
+constexpr int f32_mfma_lds(int BM, int BN) { return 2 * (BM + BN) * 36 * 4; }
 template <int BM, int BN>
-static int launch_f32_mfma(const Resolved& r, hipStream_t s) {      // exact products, on BM x BN tiles (resolve counts 64 x 64 ones)
+static int launch_f32_mfma(const Resolved& r, const Launch& L, hipStream_t s) {      // exact products
     switch (r.d.layout) {
-        case 0: return launch_f32_mfma_one<BM, BN, 0>(r.d, grid_of<BM, BN>(r), s);
-        case 1: return launch_f32_mfma_one<BM, BN, 1>(r.d, grid_of<BM, BN>(r), s);
-        default: return launch_f32_mfma_one<BM, BN, 2>(r.d, grid_of<BM, BN>(r), s);
+        case 0: return launch_planned<&gemm_f32_mfma_kernel<BM, BN, 0, false>>(L, s, r.d);
+        case 1: return launch_planned<&gemm_f32_mfma_kernel<BM, BN, 1, false>>(L, s, r.d);
+        default: return launch_planned<&gemm_f32_mfma_kernel<BM, BN, 2, false>>(L, s, r.d);
     }
 }
-static int launch_f32_mfma_split(const Resolved& r, hipStream_t s) {      // split products: layout 0, 128 x 128 tiles only (choose_route)
-    return launch_f32_mfma_one<128, 128, 0, true>(r.d, grid_of<128, 128>(r), s);
+static int launch_f32_mfma_split(const Resolved& r, const Launch& L, hipStream_t s) {      // split products: layout 0, 128 x 128 tiles only (choose_route)
+    return launch_planned<&gemm_f32_mfma_kernel<128, 128, 0, true>>(L, s, r.d);
 }
 
 template <int BM, int BN>
-static int launch_bf16(const Resolved& r, hipStream_t s) {
-    const mdm_gemm_desc& d = r.d;
-    const dim3 grid = grid_of(r);
-    switch (d.layout) {
-        case 0: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 0>), grid, dim3(256), 0, s, d); break;
-        case 1: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 1>), grid, dim3(256), 0, s, d); break;
-        default: hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, 2>), grid, dim3(256), 0, s, d); break;
+static int launch_bf16(const Resolved& r, const Launch& L, hipStream_t s) {
+    switch (r.d.layout) {
+        case 0: return launch_planned<&gemm_bf16_kernel<BM, BN, 0>>(L, s, r.d);
+        case 1: return launch_planned<&gemm_bf16_kernel<BM, BN, 1>>(L, s, r.d);
+        default: return launch_planned<&gemm_bf16_kernel<BM, BN, 2>>(L, s, r.d);
     }
-    return 0;
 }
 
+// ---- the routes whose grid is not a tiling of the output: geom_* gives grid.x as well
+static int geom_thin(const Resolved& r, Launch& L) {
+    L.gx = std::min(cdiv(cdiv(r.d.M, 16), 4), 1024);
+    L.threads = 256;
+    return 0;
+}
 template <int NJ>
-static int launch_thin(const Resolved& r, hipStream_t s) {
-    const unsigned nb = (unsigned)std::min(cdiv(cdiv(r.d.M, 16), 4), 1024);
-    hipLaunchKernelGGL((conv_thin_k_kernel<NJ>), dim3(nb), dim3(256), 0, s, r.d);
+static int launch_thin(const Resolved& r, const Launch& L, hipStream_t s) {
+    return launch_planned<&conv_thin_k_kernel<NJ>>(L, s, r.d);
+}
+static int geom_skinny_f32(const Resolved& r, Launch& L) {
+    L.gx = cdiv(r.d.N, 16);
+    L.threads = 256;
+    L.lds = 32 * (r.d.K > 16 * 17 ? r.d.K : 16 * 17) * 4;
     return 0;
 }
-static int launch_skinny_f32(const Resolved& r, hipStream_t s) {      // opts in to its largest tile (K = 512) on first use, whatever K is
-    const mdm_gemm_desc& d = r.d;
+static int launch_skinny_f32(const Resolved& r, const Launch& L, hipStream_t s) {      // opts in to its largest tile (K = 512) on first use, whatever K is
     if (int rc = lds_opt_in<&linear_skinny_f32_kernel>(32 * 512 * 4)) return rc;
-    hipLaunchKernelGGL(linear_skinny_f32_kernel, dim3((unsigned)cdiv(d.N, 16)), dim3(256), 32 * (d.K > 16 * 17 ? d.K : 16 * 17) * 4, s, d);
+    return launch_planned<&linear_skinny_f32_kernel>(L, s, r.d);
+}
+static int geom_tn_skinny_f32(const Resolved& r, Launch& L) {
+    L.gx = (int64_t)cdiv(r.d.M, 64) * cdiv(r.d.N, 64);
+    L.threads = 256;
+    L.lds = r.d.K * 128 * 4;
     return 0;
 }
-static int launch_tn_skinny_f32(const Resolved& r, hipStream_t s) {
-    const mdm_gemm_desc& d = r.d;
-    if (int rc = lds_opt_in<&tn_skinny_f32_kernel>(d.K * 128 * 4)) return rc;
-    hipLaunchKernelGGL(tn_skinny_f32_kernel, dim3((unsigned)((int64_t)cdiv(d.M, 64) * cdiv(d.N, 64))), dim3(256), d.K * 128 * 4, s, d);
-    return 0;
+static int launch_tn_skinny_f32(const Resolved& r, const Launch& L, hipStream_t s) {
+    return launch_planned<&tn_skinny_f32_kernel>(L, s, r.d);
 }
 
-// ---- two independent convolutions in one launch (conv_pair_kernel): workgroups of `b` on the tile shape resolve chose
+// ---- two independent convolutions in one launch (conv_pair_kernel, conv_pair_small_kernel): the workgroups of `a`, those of `b`
+// behind them (plan_pair)
 template <int BM, int NPW, int BN, int NSB, int LBM, int LBN, int LNS, int LWR, int LWC>
-static int launch_pair(const Resolved& ra, const Resolved& rb, hipStream_t s) {
-    const mdm_gemm_desc &a = ra.d, &b = rb.d;
-    const int nb = LBM == 64 && LBN == 128 ? (int)grid_of<64, 128>(rb).x : (int)rb.tiles;      // (64 x 128 is not a tile shape of resolve)
-    const int NPA = halo_pieces(BM, a.OH, a.OW);
-    const int bytes = std::max(halo_lds_bytes<BM, NSB, BN, 3>(a), lin2_lds_bytes<LBM, LBN, LNS>(b));
-    MDM_REQUIRE(NPA <= 8 * NPW && bytes <= 160 * 1024, "conv_pair: tile does not fit (NPA=%d, %d bytes)", NPA, bytes);
-    if (int rc = lds_opt_in<&conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>>(bytes)) return rc;
-    const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
-    hipLaunchKernelGGL((conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
-    return 0;
+static int launch_pair(const Resolved& ra, const Resolved& rb, const Launch& L, hipStream_t s) {
+    return launch_planned<&conv_pair_kernel<BM, NPW, BN, NSB, LBM, LBN, LNS, LWR, LWC>>(L, s, ra.d, rb.d, L.arg[0]);
 }
-
 template <int NPW, int BM, int BN>
-static int launch_pair_small(const Resolved& ra, const Resolved& rb, hipStream_t s) {
-    const mdm_gemm_desc &a = ra.d, &b = rb.d;
-    const int nb = (int)rb.tiles;
-    const int bytes = std::max(small_lds_bytes(a, BM, BN), lin2_lds_bytes<64, 64, 4>(b));
-    MDM_REQUIRE(small_pieces(a, BM) <= 8 * NPW && bytes <= 160 * 1024, "conv_pair_small: tile does not fit (%d bytes)", bytes);
-    MDM_REQUIRE(BM == 64 || (fused_gn_cpg(a) == 8 && a.N0 % 8 == 0), "conv_pair_small: %d x %d tiles need C / G == 8 and N0 %% 8 == 0", BM, BN);
-    if (int rc = lds_opt_in<&conv_pair_small_kernel<NPW, BM, BN>>(bytes)) return rc;
-    const int na = (int)((int64_t)(a.M / BM) * (a.N / BN));
-    hipLaunchKernelGGL((conv_pair_small_kernel<NPW, BM, BN>), dim3((unsigned)(na + nb)), dim3(512), bytes, s, a, b, na);
-    return 0;
+static int launch_pair_small(const Resolved& ra, const Resolved& rb, const Launch& L, hipStream_t s) {
+    return launch_planned<&conv_pair_small_kernel<NPW, BM, BN>>(L, s, ra.d, rb.d, L.arg[0]);
 }
 
 static mdm_gemm_desc with_n0(mdm_gemm_desc d) {      // N0 == 0 means one destination: N0 = N
@@ -3890,16 +3903,14 @@ static int resolve(const mdm_gemm_desc* dh, bool planning, Resolved& r) {
     if (int rc = validate(d)) return rc;
     r.zouter = d.batch;
     if (d.layout == 2 && d.conv) r.zouter = d.KH * d.KW;
-    // tile choice: 128x128 when that still yields enough workgroups; weight gradients (layout 2: small
-    // output, huge reduction, split-K supplies the parallelism) take the big tile whenever it fits.
-    r.big = d.dtype == MDM_BF16 && d.N >= 128 && d.M >= 128 &&
-            (d.layout == 2 ? d.K >= 2048 : (int64_t)cdiv(d.M, 128) * cdiv(d.N, 128) * r.zouter >= kBigMinTiles);
-    const int BM = d.dtype == MDM_F32 ? 64 : (r.big ? 128 : 64), BN = BM;
+    // the split heuristics count tiles of the generic rule (fp32: 64 x 64), whatever tile the route then launches
+    const bool big = big_tile(d, r.zouter);
+    const int BM = d.dtype == MDM_F32 ? 64 : (big ? 128 : 64), BN = BM;
     const int BK = d.dtype == MDM_F32 ? 16 : 64;
-    r.tiles = (int64_t)cdiv(d.M, BM) * cdiv(d.N, BN);
+    const int64_t tiles = (int64_t)cdiv(d.M, BM) * cdiv(d.N, BN);
     if (d.layout == 2) {
         if (d.splitk <= 0) {     // auto: aim at ~kWgradBlocks workgroups, at least kWgradMinSlabs k-steps each
-            int64_t want = (r.big ? kWgradBlocks : 4 * kWgradBlocks) / (r.tiles * r.zouter);
+            int64_t want = (big ? kWgradBlocks : 4 * kWgradBlocks) / (tiles * r.zouter);
             int64_t cap = d.K / (kWgradMinSlabs * BK);
             d.splitk = (int)(want < 1 ? 1 : (want > cap ? (cap < 1 ? 1 : cap) : want));
         }
@@ -3910,8 +3921,8 @@ static int resolve(const mdm_gemm_desc* dh, bool planning, Resolved& r) {
         const int taps = d.KH * d.KW;
         if (halo_tile(d) == 64) {
             /* single launch on the halo kernel: no tap split */
-        } else if (d.ws && d.dtype == MDM_BF16 && ring_eligible(d) && taps >= 9 && taps % 3 == 0 && r.tiles <= 160) {
-            int sk = r.tiles <= 48 ? taps : 3;
+        } else if (d.ws && d.dtype == MDM_BF16 && ring_eligible(d) && taps >= 9 && taps % 3 == 0 && tiles <= 160) {
+            int sk = tiles <= 48 ? taps : 3;
             if (taps % sk) sk = 3;
             if (d.ws_bytes >= (int64_t)sk * d.M * d.N * 4) d.splitk = sk;
         }
@@ -3937,26 +3948,41 @@ static int resolve(const mdm_gemm_desc* dh, bool planning, Resolved& r) {
 }
 
 // ---- the routes (mdm_gemm_last_route): which kernel and which second stage the last call on this host thread launched.
-// ONE table: X(enum, kernel name, second stages it can take: T = tap-split epilogue, K = split-K reduce, its launcher from mdm_gemm,
-// its launcher from mdm_gemm_pair).  A route is kernel * 3 + stage; the names of all three stages exist, mdm_gemm_route_names lists
-// the ones the mask allows.  launch_route / launch_pair_route are one indexed call; the routes without a launcher are entry points
-// of their own.  The halo, conv_small and conv_thin_k rows spell their template arguments once: the name is those arguments
-// (two rows excepted, whose filter-stage count is a tuning constant that the name calls NSB).
+// ONE table: X(enum, kernel name, second stages it can take: T = tap-split epilogue, K = split-K reduce, its output tile (rows,
+// columns), its geometry step, its launcher from mdm_gemm).  A route launches the grid of its OWN row's tile -- route_tiles, by the
+// batch / tap / split count -- and nothing else counts tiles for a launch; the geometry step (pure: the resolved descriptor in, a
+// Launch or a refusal out) adds workgroup size, dynamic LDS and the "tile does not fit" checks, and for the rows with tile 0, 0,
+// whose grid is not a tiling of the output, grid.x as well.  The tile and the template arguments of geometry step and launcher
+// come from the same macro arguments.  A PAIR row names the mdm_gemm routes of its two roles instead: its geometry is theirs,
+// one grid behind the other (plan_pair), and its launcher is the one of mdm_gemm_pair.  plan_route / plan_pair run the
+// geometry before a route is recorded and before any HIP call, mdm_gemm_launch_of / mdm_gemm_pair_launch_of report it, the
+// launchers pass it to hipLaunchKernelGGL.  A route is kernel * 3 + stage; the names of all three stages exist,
+// mdm_gemm_route_names lists the ones the mask allows.  The routes without a launcher are entry points of their own.  The halo,
+// conv_small and conv_thin_k rows spell their template arguments once: the name is those arguments (two rows excepted, whose
+// filter-stage count is a tuning constant that the name calls NSB).
 enum RouteStage { S_NONE = 0, S_TAPSPLIT = 1, S_SPLITK = 2 };
 constexpr int TSPLIT = 1 << S_TAPSPLIT, KSPLIT = 1 << S_SPLITK;
 #define HALO_ARGS(BM, NPW, NSB, BN) "halo<" #BM "," #NPW "," #NSB "," #BN
-#define HB(X, e, BM, NPW, NSB, BN) X(e, HALO_ARGS(BM, NPW, NSB, BN) ">", 0, (launch_halo<BM, NPW, NSB, BN, bf16_t, false>))
-#define HF(X, e, BM, NPW, NSB, BN) X(e, HALO_ARGS(BM, NPW, NSB, BN) ",f32>", 0, (launch_halo<BM, NPW, NSB, BN, float, false>))
-#define HS(X, e, BM, NPW, NSB, BN) X(e, HALO_ARGS(BM, NPW, NSB, BN) ",f32,split>", 0, (launch_halo<BM, NPW, NSB, BN, float, true>))
-#define SMALL(X, e, NPW, BM, BN) X(e, "conv_small<" #NPW "," #BM "," #BN ">", 0, (launch_small<NPW, BM, BN>))
-#define THIN(X, e, NJ) X(e, "conv_thin_k<" #NJ ">", 0, launch_thin<NJ>)
-#define PAIR(X, e, n, ...) X(e, n, 0, nullptr, (__VA_ARGS__))
+#define HALO(X, e, n, BM, NPW, NSB, BN, T, SPLIT) X(e, n, 0, BM, BN, (geom_halo<BM, NPW, NSB, BN>), (launch_halo<BM, NPW, NSB, BN, T, SPLIT>))
+#define HB(X, e, BM, NPW, NSB, BN) HALO(X, e, HALO_ARGS(BM, NPW, NSB, BN) ">", BM, NPW, NSB, BN, bf16_t, false)
+#define HF(X, e, BM, NPW, NSB, BN) HALO(X, e, HALO_ARGS(BM, NPW, NSB, BN) ",f32>", BM, NPW, NSB, BN, float, false)
+#define HS(X, e, BM, NPW, NSB, BN) HALO(X, e, HALO_ARGS(BM, NPW, NSB, BN) ",f32,split>", BM, NPW, NSB, BN, float, true)
+#define SMALL(X, e, NPW, BM, BN) X(e, "conv_small<" #NPW "," #BM "," #BN ">", 0, BM, BN, (geom_small<NPW, BM, BN>), (launch_small<NPW, BM, BN>))
+#define THIN(X, e, NJ) X(e, "conv_thin_k<" #NJ ">", 0, 0, 0, geom_thin, launch_thin<NJ>)
+#define LIN_SPLIT(X, e, BN) X(e, "lin_split<" #BN ">", 0, 128, BN, (geom_fixed<512, lin_split_lds(BN)>), launch_lin_split<BN>)
+#define F32_MFMA(X, e, n, BT, launcher) X(e, n, KSPLIT, BT, BT, (geom_fixed<256, f32_mfma_lds(BT, BT)>), launcher)
+#define LIN2(X, e, n, m, BM, BN, NS, WR, WC) X(e, n, m, BM, BN, (geom_lin2<BM, BN, NS, WR, WC>), (launch_lin2<BM, BN, NS, WR, WC>))
+#define WGRAD_LIN(X, e, BT, NS) X(e, "wgrad_lin<" #BT ">", KSPLIT, BT, BT, (geom_wgrad_lin<BT, BT, NS, 8>), (launch_wgrad_lin<BT, BT, NS, 8>))
+#define RING(X, e, m, BT, NS) X(e, "ring<" #BT ">", m, BT, BT, (geom_fixed<512, ring_lds(BT, BT, NS)>), (launch_ring<BT, BT, NS>))
+#define PLAIN_BF16(X, e, BT) X(e, "bf16<" #BT ">", KSPLIT, BT, BT, (geom_fixed<256, 0>), (launch_bf16<BT, BT>))
+#define PAIR(X, e, n, RA, RB, ...) X(e, n, 0, 0, 0, nullptr, nullptr, (__VA_ARGS__), RA, RB)
 #define MDM_GEMM_ROUTES(X)                                                                                                      \
-    X(R_SKINNY_F32, "linear_skinny_f32", 0, launch_skinny_f32) X(R_TN_SKINNY_F32, "tn_skinny_f32", 0, launch_tn_skinny_f32)     \
-    X(R_LIN_SPLIT_128, "lin_split<128>", 0, launch_lin_split<128>) X(R_LIN_SPLIT_64, "lin_split<64>", 0, launch_lin_split<64>)  \
+    X(R_SKINNY_F32, "linear_skinny_f32", 0, 0, 0, geom_skinny_f32, launch_skinny_f32)                                           \
+    X(R_TN_SKINNY_F32, "tn_skinny_f32", 0, 0, 0, geom_tn_skinny_f32, launch_tn_skinny_f32)                                      \
+    LIN_SPLIT(X, R_LIN_SPLIT_128, 128) LIN_SPLIT(X, R_LIN_SPLIT_64, 64)                                                         \
     HS(X, R_HS_256_6_32, 256, 6, 2, 32) HS(X, R_HS_256_6_128, 256, 6, 4, 128)                                                   \
-    X(R_HS_MIXED, "halo_mixed<256|128,f32,split>", 0, launch_halo_mixed)                                                        \
-    X(R_HS_256_6, "halo<256,6,NSB,64,f32,split>", 0, (launch_halo<256, 6, MDM_SPLIT_NSB256, 64, float, true>))                  \
+    X(R_HS_MIXED, "halo_mixed<256|128,f32,split>", 0, 0, 0, geom_halo_mixed, launch_halo_mixed)                                 \
+    HALO(X, R_HS_256_6, "halo<256,6,NSB,64,f32,split>", 256, 6, MDM_SPLIT_NSB256, 64, float, true)                              \
     HS(X, R_HS_128_3, 128, 3, 3, 64) HS(X, R_HS_128_4, 128, 4, 3, 64) HS(X, R_HS_128_6, 128, 6, 3, 64)                          \
     HS(X, R_HS_64_2_32, 64, 2, 3, 32) HS(X, R_HS_64_3_32, 64, 3, 3, 32)                                                         \
     HS(X, R_HS_64_2_64, 64, 2, 3, 64) HS(X, R_HS_64_3_64, 64, 3, 3, 64)                                                         \
@@ -3964,32 +3990,33 @@ constexpr int TSPLIT = 1 << S_TAPSPLIT, KSPLIT = 1 << S_SPLITK;
     HF(X, R_HF_128_3, 128, 3, 3, 64) HF(X, R_HF_128_4, 128, 4, 3, 64) HF(X, R_HF_128_6, 128, 6, 3, 64)                          \
     HF(X, R_HF_64_2_32, 64, 2, 3, 32) HF(X, R_HF_64_3_32, 64, 3, 3, 32)                                                         \
     HF(X, R_HF_64_2_64, 64, 2, 3, 64) HF(X, R_HF_64_3_64, 64, 3, 3, 64)                                                         \
-    X(R_F32_128, "f32_mfma<128>", KSPLIT, (launch_f32_mfma<128, 128>))                                                          \
-    X(R_F32_128_SPLIT, "f32_mfma<128,split>", KSPLIT, launch_f32_mfma_split)                                                    \
-    X(R_F32_64, "f32_mfma<64>", KSPLIT, (launch_f32_mfma<64, 64>))                                                              \
+    F32_MFMA(X, R_F32_128, "f32_mfma<128>", 128, (launch_f32_mfma<128, 128>))                                                   \
+    F32_MFMA(X, R_F32_128_SPLIT, "f32_mfma<128,split>", 128, launch_f32_mfma_split)                                             \
+    F32_MFMA(X, R_F32_64, "f32_mfma<64>", 64, (launch_f32_mfma<64, 64>))                                                        \
     THIN(X, R_THIN_1, 1) THIN(X, R_THIN_2, 2) THIN(X, R_THIN_4, 4) THIN(X, R_THIN_8, 8)                                         \
-    X(R_H256_6, "halo<256,6,NSB,64>", 0, (launch_halo<256, 6, MDM_NSB256, 64, bf16_t, false>))                                  \
+    HALO(X, R_H256_6, "halo<256,6,NSB,64>", 256, 6, MDM_NSB256, 64, bf16_t, false)                                              \
     HB(X, R_H128_3, 128, 3, 3, 64) HB(X, R_H128_4, 128, 4, 3, 64) HB(X, R_H128_6, 128, 6, 3, 64)                                \
     HB(X, R_H64_2_32, 64, 2, 3, 32) HB(X, R_H64_3_32, 64, 3, 3, 32)                                                             \
     HB(X, R_H64_2_64, 64, 2, 3, 64) HB(X, R_H64_3_64, 64, 3, 3, 64)                                                             \
     SMALL(X, R_SMALL_4, 4, 64, 32) SMALL(X, R_SMALL_5, 5, 64, 32) SMALL(X, R_SMALL_3, 3, 32, 16)                                \
-    X(R_LIN2_128, "lin2<128,128>", 0, (launch_lin2<128, 128, 3, 4, 2>))                                                         \
-    X(R_LIN2_64x128, "lin2<64,128>", TSPLIT, (launch_lin2<64, 128, 3, 2, 4>))                                                   \
-    X(R_LIN2_64, "lin2<64,64>", TSPLIT, (launch_lin2<64, 64, 4, 4, 2>))                                                         \
-    X(R_WGRAD_LIN_128, "wgrad_lin<128>", KSPLIT, (launch_wgrad_lin<128, 128, 3, 8>))                                            \
-    X(R_WGRAD_LIN_64, "wgrad_lin<64>", KSPLIT, (launch_wgrad_lin<64, 64, 4, 8>))                                                \
-    X(R_RING_128, "ring<128>", KSPLIT, (launch_ring<128, 128, 3>)) X(R_RING_64, "ring<64>", TSPLIT | KSPLIT, (launch_ring<64, 64, 4>)) \
-    X(R_BF16_128, "bf16<128>", KSPLIT, (launch_bf16<128, 128>)) X(R_BF16_64, "bf16<64>", KSPLIT, (launch_bf16<64, 64>))         \
-    PAIR(X, R_PAIR_SMALL_4, "pair_small<4>", launch_pair_small<4, 64, 32>)                                                      \
-    PAIR(X, R_PAIR_SMALL_5, "pair_small<5>", launch_pair_small<5, 64, 32>)                                                      \
-    PAIR(X, R_PAIR_SMALL_3, "pair_small<3,32,16>", launch_pair_small<3, 32, 16>)                                                \
-    PAIR(X, R_PAIR_64_2, "pair<halo<64,2,3,32>,lin2<64,64>>", launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>)                       \
-    PAIR(X, R_PAIR_64_3, "pair<halo<64,3,3,32>,lin2<64,64>>", launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>)                       \
-    PAIR(X, R_PAIR_128_L64x128, "pair<halo<128,3,3,64>,lin2<64,128>>", launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>)            \
-    PAIR(X, R_PAIR_128_L64, "pair<halo<128,3,3,64>,lin2<64,64>>", launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>)                  \
-    PAIR(X, R_PAIR_256_L128, "pair<halo<256,6,NSB,64>,lin2<128,128>>", launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>)  \
-    X(R_PAIR_TWO, "pair:two launches", 0, nullptr)                                                                              \
-    X(R_WGROUP, "wgrad_group", KSPLIT, nullptr) X(R_WGROUP_TAPS, "wgrad_taps_group", KSPLIT, nullptr)
+    LIN2(X, R_LIN2_128, "lin2<128,128>", 0, 128, 128, 3, 4, 2)                                                                  \
+    LIN2(X, R_LIN2_64x128, "lin2<64,128>", TSPLIT, 64, 128, 3, 2, 4)                                                            \
+    LIN2(X, R_LIN2_64, "lin2<64,64>", TSPLIT, 64, 64, 4, 4, 2)                                                                  \
+    WGRAD_LIN(X, R_WGRAD_LIN_128, 128, 3) WGRAD_LIN(X, R_WGRAD_LIN_64, 64, 4)                                                   \
+    RING(X, R_RING_128, KSPLIT, 128, 3) RING(X, R_RING_64, TSPLIT | KSPLIT, 64, 4)                                              \
+    PLAIN_BF16(X, R_BF16_128, 128) PLAIN_BF16(X, R_BF16_64, 64)                                                                 \
+    PAIR(X, R_PAIR_SMALL_4, "pair_small<4>", R_SMALL_4, R_LIN2_64, launch_pair_small<4, 64, 32>)                                \
+    PAIR(X, R_PAIR_SMALL_5, "pair_small<5>", R_SMALL_5, R_LIN2_64, launch_pair_small<5, 64, 32>)                                \
+    PAIR(X, R_PAIR_SMALL_3, "pair_small<3,32,16>", R_SMALL_3, R_LIN2_64, launch_pair_small<3, 32, 16>)                          \
+    PAIR(X, R_PAIR_64_2, "pair<halo<64,2,3,32>,lin2<64,64>>", R_H64_2_32, R_LIN2_64, launch_pair<64, 2, 32, 3, 64, 64, 4, 4, 2>) \
+    PAIR(X, R_PAIR_64_3, "pair<halo<64,3,3,32>,lin2<64,64>>", R_H64_3_32, R_LIN2_64, launch_pair<64, 3, 32, 3, 64, 64, 4, 4, 2>) \
+    PAIR(X, R_PAIR_128_L64x128, "pair<halo<128,3,3,64>,lin2<64,128>>", R_H128_3, R_LIN2_64x128,                                 \
+         launch_pair<128, 3, 64, 3, 64, 128, 3, 2, 4>)                                                                          \
+    PAIR(X, R_PAIR_128_L64, "pair<halo<128,3,3,64>,lin2<64,64>>", R_H128_3, R_LIN2_64, launch_pair<128, 3, 64, 3, 64, 64, 4, 4, 2>) \
+    PAIR(X, R_PAIR_256_L128, "pair<halo<256,6,NSB,64>,lin2<128,128>>", R_H256_6, R_LIN2_128,                                    \
+         launch_pair<256, 6, 64, MDM_NSB256, 128, 128, 3, 4, 2>)                                                                \
+    X(R_PAIR_TWO, "pair:two launches", 0, 0, 0, nullptr)                                                                        \
+    X(R_WGROUP, "wgrad_group", KSPLIT, 0, 0, nullptr) X(R_WGROUP_TAPS, "wgrad_taps_group", KSPLIT, 0, 0, nullptr)
 enum GemmRoute {
 #define MDM_ROUTE_ENUM(e, ...) e,
     MDM_GEMM_ROUTES(MDM_ROUTE_ENUM)
@@ -3999,13 +4026,34 @@ enum GemmRoute {
 static const struct RouteRow {
     const char* name[3];        // by RouteStage
     int stages;                 // mask of the stages it can take
-    int (*launch)(const Resolved&, hipStream_t);
-    int (*launch_pair)(const Resolved&, const Resolved&, hipStream_t);
+    int tile_m, tile_n;         // its output tile (0, 0: the grid is not a tiling of the output)
+    int (*geom)(const Resolved&, Launch&);
+    int (*launch)(const Resolved&, const Launch&, hipStream_t);
+    int (*launch_pair)(const Resolved&, const Resolved&, const Launch&, hipStream_t);
+    GemmRoute role_a, role_b;   // of a pair: the mdm_gemm routes of `a` and of `b`
 } kRoutes[R_COUNT] = {
 #define MDM_ROUTE_ROW(e, n, m, ...) {{n, n "+tapsplit", n "+splitk"}, 1 | (m), __VA_ARGS__},
     MDM_GEMM_ROUTES(MDM_ROUTE_ROW)
 #undef MDM_ROUTE_ROW
 };
+// The output tiles of a tiled route: the only tile count a launch is made from
+static int64_t route_tiles(GemmRoute rt, const mdm_gemm_desc& d) {
+    return (int64_t)cdiv(d.M, kRoutes[rt].tile_m) * cdiv(d.N, kRoutes[rt].tile_n);
+}
+// The launch of route `rt` for a resolved descriptor, or a refusal.  Host arithmetic only.
+static int route_geometry(GemmRoute rt, const Resolved& r, Launch& L) {
+    MDM_REQUIRE(rt >= 0 && rt < R_COUNT && kRoutes[rt].geom, "gemm: route %d is not an mdm_gemm route", (int)rt);
+    const RouteRow& row = kRoutes[rt];
+    L = Launch{1, 1, 0, 0, row.tile_m, row.tile_n, {0, 0}};
+    if (row.tile_m) {
+        L.gx = route_tiles(rt, r.d);
+        L.gz = (int64_t)r.zouter * r.d.splitk;
+    }
+    MDM_REQUIRE(L.gz <= 65535, "gemm: grid.z=%u too large", (unsigned)L.gz);      // (of wgrad_lin too, which folds it into grid.x)
+    if (int rc = row.geom(r, L)) return rc;
+    MDM_REQUIRE(L.gx < (1ll << 31), "gemm: grid too large");
+    return 0;
+}
 static const char* route_name(int route) { return kRoutes[route / 3].name[route % 3]; }
 static thread_local int g_route = -1;
 static inline void route(GemmRoute r) { g_route = 3 * r; }
@@ -4062,7 +4110,7 @@ static GemmRoute conv_variant(const Resolved& r) {          // ... and which one
         return halo_route(HK_BF16, hb, halo_npw(hb, d), half_n);
     }
     if ((d.gnb_x || d.gnf_out) && lin2_gn_tile(d)) return R_LIN2_64;      // the fused epilogues live on the 64 x 64 tile
-    if (r.big) return R_LIN2_128;
+    if (big_tile(d, r.zouter)) return R_LIN2_128;
     // (the qkv projection of the 8x8 maps is 192 such tiles -- 384 tiles of 64 x 64 = 1.5 rounds today; taking them from 180 on was level:
     //  3.582 vs 3.586 ms/step)
     if (d.N >= 128 && t_mid >= kBigMinTiles) return R_LIN2_64x128;
@@ -4080,7 +4128,8 @@ static int check_fused_gn(const mdm_gemm_desc& d) {
 }
 
 // ---- the dispatch rule, in two halves: choose_route decides (host arithmetic on the resolved descriptor only: no HIP call, no
-// state), launch_route launches what was chosen.  mdm_gemm_route_of asks the first half alone.
+// state), route_geometry plans its launch (as pure), the row's launcher launches what was planned.  mdm_gemm_route_of and
+// mdm_gemm_launch_of ask the pure part alone.
 static GemmRoute choose_route(const Resolved& r) {
     const mdm_gemm_desc& d = r.d;
     if (d.dtype == MDM_F32 && d.layout == 0 && !d.conv && d.M <= 32 && d.K % 64 == 0 && d.K <= 512 && d.splitk <= 1 &&
@@ -4122,38 +4171,31 @@ static GemmRoute choose_route(const Resolved& r) {
         return nj == 1 ? R_THIN_1 : nj == 2 ? R_THIN_2 : nj <= 4 ? R_THIN_4 : R_THIN_8;
     }
     if (conv_family(d)) return conv_variant(r);
-    if (wgrad_lin_eligible(d)) return r.big ? R_WGRAD_LIN_128 : R_WGRAD_LIN_64;
-    if (ring_eligible(d)) return r.big ? R_RING_128 : R_RING_64;
-    return r.big ? R_BF16_128 : R_BF16_64;
+    const bool big = big_tile(d, r.zouter);
+    if (wgrad_lin_eligible(d)) return big ? R_WGRAD_LIN_128 : R_WGRAD_LIN_64;
+    if (ring_eligible(d)) return big ? R_RING_128 : R_RING_64;
+    return big ? R_BF16_128 : R_BF16_64;
 }
 // the second launch of a split reduction, if any
 static RouteStage second_stage(const Resolved& r) { return r.tap_split ? S_TAPSPLIT : (r.d.splitk > 1 && r.d.ws) ? S_SPLITK : S_NONE; }
 
-// What mdm_gemm settles before it launches: the resolved descriptor and its route, or an error.
-static int plan_route(const mdm_gemm_desc* dh, Resolved& r, GemmRoute& rt) {
+// What mdm_gemm settles before it launches: the resolved descriptor, its route and the route's launch, or an error.
+static int plan_route(const mdm_gemm_desc* dh, Resolved& r, GemmRoute& rt, Launch& L) {
     if (int rc = resolve(dh, false, r)) return rc;
     if (int rc = check_fused_gn(r.d)) return rc;
-    const int64_t grid_z = (int64_t)r.zouter * r.d.splitk;
-    MDM_REQUIRE(r.tiles < (1ll << 31), "gemm: grid too large");
-    MDM_REQUIRE(grid_z <= 65535, "gemm: grid.z=%u too large", (unsigned)grid_z);
     rt = choose_route(r);
-    if (rt == R_WGRAD_LIN_128 || rt == R_WGRAD_LIN_64) MDM_REQUIRE(r.tiles * grid_z < (1ll << 30), "gemm: grid too large");
-    return 0;
-}
-
-static int launch_route(GemmRoute rt, const Resolved& r, hipStream_t s) {      // (pairs and groups: entry points of their own)
-    MDM_REQUIRE(rt >= 0 && rt < R_COUNT && kRoutes[rt].launch, "gemm: route %d is not an mdm_gemm route", (int)rt);
-    return kRoutes[rt].launch(r, s);
+    return route_geometry(rt, r, L);
 }
 
 static int gemm_launch(const mdm_gemm_desc* dh, hipStream_t s) {
     Resolved r;
     GemmRoute rt;
+    Launch L;
     g_route = -1;
-    if (int rc = plan_route(dh, r, rt)) return rc;
+    if (int rc = plan_route(dh, r, rt, L)) return rc;
     const mdm_gemm_desc& d = r.d;
     route(rt);                  // before the launch: a failing launch still reports the route it took
-    if (int rc = launch_route(rt, r, s)) return rc;
+    if (int rc = kRoutes[rt].launch(r, L, s)) return rc;      // (pairs and groups: entry points of their own)
     const RouteStage st = second_stage(r);
     route_stage(st);
     if (st == S_TAPSPLIT) {
@@ -4218,8 +4260,23 @@ extern "C" const char* mdm_gemm_last_route(void) { return g_route >= 0 ? route_n
 extern "C" const char* mdm_gemm_route_of(const mdm_gemm_desc* desc_host) {
     Resolved r;
     GemmRoute rt;
-    if (plan_route(desc_host, r, rt)) return "none";
+    Launch L;
+    if (plan_route(desc_host, r, rt, L)) return "none";
     return route_name(3 * rt + second_stage(r));
+}
+
+static int launch_numbers(const Launch& L, int32_t out[6]) {
+    const int32_t v[6] = {(int32_t)L.gx, (int32_t)L.gz, L.threads, L.lds, L.tile_m, L.tile_n};
+    std::copy(v, v + 6, out);
+    return 0;
+}
+extern "C" int mdm_gemm_launch_of(const mdm_gemm_desc* desc_host, int32_t out[6]) {
+    MDM_REQUIRE(out != nullptr, "gemm_launch_of: null output");
+    Resolved r;
+    GemmRoute rt;
+    Launch L;
+    if (int rc = plan_route(desc_host, r, rt, L)) return rc;
+    return launch_numbers(L, out);
 }
 
 extern "C" int mdm_gemm_route_names(const char** out, int cap) {
@@ -4232,42 +4289,48 @@ extern "C" int mdm_gemm_route_names(const char** out, int cap) {
     return n;
 }
 
-static int plan_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, Resolved& ra, Resolved& rb) {
-    if (int rc = resolve(a_host, false, ra)) return rc;
-    if (int rc = resolve(b_host, false, rb)) return rc;
-    if (int rc = check_fused_gn(ra.d)) return rc;
-    return check_fused_gn(rb.d);
-}
-// One of the fused routes, or R_PAIR_TWO: `b` must be a conv_lin2 launch of its own with no second stage (no split reduction),
-// `a` a halo launch; the pairs below are the ones a unet6 step produces (4x4, 8x8, 16x16, 32x32 maps).  Anything else: two
-// launches, same results.  (No HIP call, no state: mdm_gemm_pair_route_of asks this alone.)
+// One of the fused routes, or R_PAIR_TWO: `b` must be a conv_lin2 launch of its own with no second stage (no split reduction)
+// and fewer than 2^20 workgroups, `a` a halo launch; the fused rows of the table are the pairs a unet6 step produces (4x4, 8x8,
+// 16x16, 32x32 maps).  Anything else: two launches, same results.  (No HIP call, no state.)
 static GemmRoute choose_pair_route(const Resolved& ra, const Resolved& rb) {
     const mdm_gemm_desc &a = ra.d, &b = rb.d;
     const int za = ra.zouter * a.splitk, zb = rb.zouter * b.splitk;
-    const bool b_plain = zb == 1 && !rb.tap_split && !(b.splitk > 1) && rb.tiles < (1ll << 20) && !b.gnb_x && !b.gnf_out;
+    const bool b_plain = zb == 1 && !rb.tap_split && !(b.splitk > 1) && !b.gnb_x && !b.gnf_out;
     if (!(b_plain && za == 1 && conv_family(a) && conv_family(b))) return R_PAIR_TWO;
     const GemmRoute va = conv_variant(ra), vb = conv_variant(rb);
-    if (va == R_SMALL_4 && vb == R_LIN2_64) return R_PAIR_SMALL_4;
-    if (va == R_SMALL_5 && vb == R_LIN2_64) return R_PAIR_SMALL_5;
-    if (va == R_SMALL_3 && vb == R_LIN2_64) return R_PAIR_SMALL_3;
-    if (va == R_H64_2_32 && vb == R_LIN2_64) return R_PAIR_64_2;
-    if (va == R_H64_3_32 && vb == R_LIN2_64) return R_PAIR_64_3;
-    if (va == R_H128_3 && vb == R_LIN2_64x128) return R_PAIR_128_L64x128;
-    if (va == R_H128_3 && vb == R_LIN2_64) return R_PAIR_128_L64;
-    if (va == R_H256_6 && vb == R_LIN2_128) return R_PAIR_256_L128;
+    for (int rt = 0; rt < R_COUNT; ++rt)
+        if (kRoutes[rt].launch_pair && kRoutes[rt].role_a == va && kRoutes[rt].role_b == vb)
+            return route_tiles(vb, b) < (1ll << 20) ? (GemmRoute)rt : R_PAIR_TWO;
     return R_PAIR_TWO;
 }
-static int launch_pair_route(GemmRoute rt, const Resolved& ra, const Resolved& rb, hipStream_t s) {
-    MDM_REQUIRE(rt >= 0 && rt < R_COUNT && kRoutes[rt].launch_pair, "gemm_pair: route %d is not a fused pair", (int)rt);
-    return kRoutes[rt].launch_pair(ra, rb, s);
+// What mdm_gemm_pair settles before it launches.  A fused pair launches the grids of its two roles' rows, `b` behind `a`, with the
+// larger of their LDS needs; two launches are planned as mdm_gemm plans each (L is then the one of `b` and not used).
+static int plan_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, Resolved& ra, Resolved& rb, GemmRoute& rt, Launch& L) {
+    if (int rc = resolve(a_host, false, ra)) return rc;
+    if (int rc = resolve(b_host, false, rb)) return rc;
+    if (int rc = check_fused_gn(ra.d)) return rc;
+    if (int rc = check_fused_gn(rb.d)) return rc;
+    rt = choose_pair_route(ra, rb);
+    const bool fused = rt != R_PAIR_TWO;
+    Launch lb;
+    if (int rc = route_geometry(fused ? kRoutes[rt].role_a : choose_route(ra), ra, L)) return rc;
+    if (int rc = route_geometry(fused ? kRoutes[rt].role_b : choose_route(rb), rb, lb)) return rc;
+    if (!fused) { L = lb; return 0; }
+    MDM_REQUIRE(L.threads == lb.threads && L.gz == 1 && lb.gz == 1, "gemm_pair: the two roles of route %d do not share a launch", (int)rt);
+    L.arg[0] = (int)L.gx;
+    L.gx += lb.gx;
+    L.lds = std::max(L.lds, lb.lds);
+    MDM_REQUIRE(L.gx < (1ll << 31), "gemm_pair: grid too large");
+    return 0;
 }
 
 extern "C" int mdm_gemm_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, void* stream) {
     hipStream_t s = pick_stream(stream);
     Resolved ra, rb;
-    if (int rc = plan_pair(a_host, b_host, ra, rb)) return rc;
+    GemmRoute rt;
+    Launch L;
+    if (int rc = plan_pair(a_host, b_host, ra, rb, rt, L)) return rc;
     g_route = -1;
-    const GemmRoute rt = choose_pair_route(ra, rb);
     if (rt == R_PAIR_TWO) {
         int rc = gemm_launch(a_host, s);
         if (rc == 0) rc = gemm_launch(b_host, s);
@@ -4275,14 +4338,27 @@ extern "C" int mdm_gemm_pair(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b
         return rc;
     }
     route(rt);
-    if (int rc = launch_pair_route(rt, ra, rb, s)) return rc;
+    if (int rc = kRoutes[rt].launch_pair(ra, rb, L, s)) return rc;
     return launch_status("gemm pair launch");
 }
 
 extern "C" const char* mdm_gemm_pair_route_of(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host) {
     Resolved ra, rb;
-    if (plan_pair(a_host, b_host, ra, rb)) return "none";
-    return route_name(3 * choose_pair_route(ra, rb));
+    GemmRoute rt;
+    Launch L;
+    if (plan_pair(a_host, b_host, ra, rb, rt, L)) return "none";
+    return route_name(3 * rt);
+}
+
+extern "C" int mdm_gemm_pair_launch_of(const mdm_gemm_desc* a_host, const mdm_gemm_desc* b_host, int32_t out[6]) {
+    MDM_REQUIRE(out != nullptr, "gemm_pair_launch_of: null output");
+    Resolved ra, rb;
+    GemmRoute rt;
+    Launch L;
+    if (int rc = plan_pair(a_host, b_host, ra, rb, rt, L)) return rc;
+    if (rt != R_PAIR_TWO) return launch_numbers(L, out);
+    std::fill(out, out + 6, 0);
+    return 1;
 }
 
 // the tail of both predicates: whole channel groups of 4 .. 64 channels on a tile of whole images
@@ -4512,9 +4588,9 @@ static int plan_wgrad_group(const mdm_gemm_desc* descs_host, int n, const GroupK
         // tile: 256 x 128 where the filter has >= 256 output channels (a multiple of 256) and the reduction is long
         // (short reductions -- the 4x4 maps: 8 slabs -- take 64x64 tiles when a layer has to fill the chip on its own; in the static
         //  queues of a nine-tap group the big tiles' 2.7x fewer cycles per flop count instead)
-        const bool big = r.big || (use_taps && d.M >= 128 && d.N >= 128 && sk == 1);
+        const bool big = big_tile(d, r.zouter) || (use_taps && d.M >= 128 && d.N >= 128 && sk == 1);
         const GroupKind kind = !big ? GK_64 : (d.M % 256 == 0 && d.N >= 128 ? GK_256x128 : GK_128);
-        const int tiles_i = kind == GK_256x128 ? (d.M / 256) * cdiv(d.N, 128) : kind == GK_128 ? cdiv(d.M, 128) * cdiv(d.N, 128) : (int)r.tiles;
+        const int tiles_i = kind == GK_256x128 ? (d.M / 256) * cdiv(d.N, 128) : kind == GK_128 ? cdiv(d.M, 128) * cdiv(d.N, 128) : cdiv(d.M, 64) * cdiv(d.N, 64);
         const int n_local = tiles_i * r.zouter * sk;
         for (int it = 0; it < n_local; ++it) items.push_back(GroupItem{i, it, tiles_i, kind, split_slabs(d, it / (tiles_i * r.zouter))});
         if (sk > 1) {

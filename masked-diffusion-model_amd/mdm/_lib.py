@@ -26,15 +26,16 @@ vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 _SCALARS = {"int": i32, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32}
 
 _TOP = re.compile(r'\s*(?:extern\s+"C"\s*\{|\}|typedef\s+struct\s+\w+\s*\{([^{}]*)\}\s*(\w+)\s*;|([^;{}()]+)\(([^;{}()]*)\)\s*;)')
-_DECL = re.compile(r"(?:const\s+)?(\w+)\s*(\**)\s*(\w*)")
+_DECL = re.compile(r"(?:const\s+)?(\w+)\s*(\**)\s*(\w*)\s*(\[\d+\])?")
 
 
-def _declaration(text, where):
-    """`[const] T[*..] name` -> (name, type): type "T" for a known scalar, "T*" / "T**" for any pointer.  Everything else raises."""
+def _declaration(text, where, param=False):
+    """`[const] T[*..] name` -> (name, type): type "T" for a known scalar, "T*" / "T**" for any pointer; a parameter `T name[n]`
+    is the pointer C makes of it.  Everything else raises."""
     m = _DECL.fullmatch(text.strip())
-    if not m:
+    if not m or (m.group(4) and not param):
         raise ValueError(f"mdm_hip.h: cannot split `{text.strip()}` into type and name in `{where}`")
-    base, stars, name = m.groups()
+    base, stars, name = m.group(1), m.group(2) + ("*" if m.group(4) else ""), m.group(3)
     if not name:
         raise ValueError(f"mdm_hip.h: `{text.strip()}` has no name in `{where}`")
     if not stars and base not in _SCALARS:
@@ -65,7 +66,7 @@ def parse_header(text):
                 fields += [(name, typ)] + [_declaration(f"{typ} {n}", f"{struct}: {stmt}") for n in more]
         elif head:
             name, rtype = _declaration(head, where)
-            protos[name] = (rtype, [] if params.strip() in ("", "void") else [_declaration(p, where) for p in params.split(",")])
+            protos[name] = (rtype, [] if params.strip() in ("", "void") else [_declaration(p, where, param=True) for p in params.split(",")])
     return structs, protos
 
 
@@ -383,6 +384,23 @@ def pair_route_of(kw_a, kw_b):
     """What last_route() would name after gemm_pair(kw_a, kw_b), without launching (mdm_gemm_pair_route_of)."""
     da, db = (_desc({k: v for k, v in kw.items() if k != "_flops"}) for kw in (kw_a, kw_b))
     return load().mdm_gemm_pair_route_of(C.byref(da), C.byref(db)).decode()
+
+
+def launch_of(**kw):
+    """The first launch gemm(**kw) would make, without making it (mdm_gemm_launch_of): (workgroups, grid z, threads per workgroup,
+    dynamic LDS bytes, tile rows, tile columns), or None for a refused descriptor."""
+    kw.pop("_flops", None)
+    out = (i32 * 6)()
+    return tuple(out) if load().mdm_gemm_launch_of(C.byref(_desc(kw)), out) == 0 else None
+
+
+def pair_launch_of(kw_a, kw_b):
+    """The fused launch of gemm_pair(kw_a, kw_b) like launch_of (mdm_gemm_pair_launch_of); the two launch_of tuples where the pair
+    runs as two launches; None for a refused pair."""
+    da, db = (_desc({k: v for k, v in kw.items() if k != "_flops"}) for kw in (kw_a, kw_b))
+    out = (i32 * 6)()
+    rc = load().mdm_gemm_pair_launch_of(C.byref(da), C.byref(db), out)
+    return tuple(out) if rc == 0 else (launch_of(**kw_a), launch_of(**kw_b)) if rc == 1 else None
 
 
 def wgrad_split_last_route():

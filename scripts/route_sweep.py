@@ -3,6 +3,7 @@
 
     python scripts/route_sweep.py [--out FILE] [--tree DIR]            # one line per case
     python scripts/route_sweep.py --reasons [--out FILE] [--tree DIR]  # ops.split_grad_reason over the sweep's conv geometries
+    python scripts/route_sweep.py --launch [--out FILE] [--tree DIR]   # mdm_gemm_launch_of / _pair_launch_of: the planned geometry
 
 One line per case: the case, `mdm_gemm_route_of`, `mdm_gemm_plan` (split count, workspace bytes), `mdm_gemm_can_fuse_gn_fwd` and
 `_bwd` (G = 32); for a pair of convolutions `mdm_gemm_pair_route_of`.  Everything asked is host arithmetic on the descriptor: no GPU,
@@ -192,6 +193,21 @@ def sweep(_lib, ops):
     return lines, seen
 
 
+def launches(_lib, ops):
+    """One line per case of the sweep: the six numbers of `mdm_gemm_launch_of` (workgroups, grid z, threads, dynamic LDS bytes, tile
+    rows, tile columns) or `refused`; for a pair those of `mdm_gemm_pair_launch_of`, or both members' where it runs as two launches."""
+    show = lambda t: "refused" if t is None else " ".join(map(str, t))
+    lines = []
+    for i, case in enumerate(list(conv_cases(ops)) + list(plain_cases())):
+        if len(case) == 3:
+            t = _lib.pair_launch_of(dict(case[1]), dict(case[2]))
+            text = show(t) if t is None or len(t) == 6 else f"two: {show(t[0])} || {show(t[1])}"
+        else:
+            text = show(_lib.launch_of(**case[1]))
+        lines.append(f"{i} {case[0]} | {text}")
+    return lines
+
+
 def reasons(ops):
     """One line per distinct convolution geometry of the sweep: ops.split_grad_reason of its two gradients."""
     lines, done = [], set()
@@ -218,12 +234,15 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=None, help="write the lines here instead of stdout")
     ap.add_argument("--reasons", action="store_true", help="the split_grad_reason table instead of the routes")
+    ap.add_argument("--launch", action="store_true", help="the planned launch geometry of every case instead of the routes")
     ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                     help="checkout to import mdm from (default: the one this script lies in)")
     opt = ap.parse_args()
     _lib, ops = load(opt.tree)
     if opt.reasons:
         lines, note = reasons(ops), ""
+    elif opt.launch:
+        lines, note = launches(_lib, ops), ""
     else:
         lines, seen = sweep(_lib, ops)
         missing = [n for n in _lib.route_names() if n not in seen and n.split("+")[0] not in NOT_FROM_MDM_GEMM]

@@ -233,6 +233,17 @@ GNF_ROWS = [
     ("lin2<64,64>", 4, 4, 64, 128, 1),
     ("lin2<64,64>", 8, 4, 64, 256, 1),
 ]
+# The fused 1x1 rows again where the generic tile rule of the unfused routes says 128 x 128 (M = 6400 pixels by 512 channels: 50 x 4 =
+# 200 such tiles, the smallest count that sets it, at K = 64): the fused epilogues live on the 64 x 64 tile, whose grid is 800
+# workgroups.  A launch with the 200 of the other tile leaves three quarters of every output unwritten.
+GNB_BIG_ROWS = [
+    ("lin2<64,64>", 8, 100, 512, 64, 1),
+    ("lin2<64,64>", 4, 400, 512, 64, 1),
+]
+GNF_BIG_ROWS = [
+    ("lin2<64,64>", 8, 100, 64, 512, 1),
+    ("lin2<64,64>", 4, 400, 64, 512, 1),
+]
 
 
 def fused_id(row):

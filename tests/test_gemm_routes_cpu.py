@@ -77,6 +77,9 @@ SWEEP_CASES, SWEEP_SHA256 = 21890, "acbf675c38408ee594e59488c4c4aaac43d15b2d3772
 # ops.split_grad_reason of both gradients over the sweep's convolution geometries, recorded from the parent's mdm/ops.py (which
 # restated the tile rule in Python; it now asks mdm_gemm_route_of)
 REASON_ROWS, REASON_SHA256 = 5433, "89d1a19e206d444a7a4c65bf4a8049bc673efda265b35b5a4aa22fd8b080fd93"
+# `route_sweep.py --launch`: mdm_gemm_launch_of / mdm_gemm_pair_launch_of over the same cases, recorded from the change that made the
+# launch geometry part of the plan (profiles/r20_gemm_launch_plan.md: on the sweep's cases it is what the parent launched)
+LAUNCH_CASES, LAUNCH_SHA256 = 21890, "513492324af3e454bbbcc957a67151ae4300bbe43c51f89a4e89110706b506b5"
 
 
 @pytest.fixture(scope="module")
@@ -103,3 +106,46 @@ def test_split_grad_reason_matches_the_recorded_table(route_sweep):
     lines = route_sweep.reasons(ops)
     assert {ln.split(" | ")[1] for ln in lines} == {"dgrad None", "dgrad channels", "dgrad stride2", "dgrad geometry"}
     assert (len(lines), route_sweep.digest(lines)) == (REASON_ROWS, REASON_SHA256)
+
+
+def test_launch_sweep_matches_the_recorded_geometry(route_sweep):
+    from mdm import _lib, ops
+    lines = route_sweep.launches(_lib, ops)
+    assert (len(lines), route_sweep.digest(lines)) == (LAUNCH_CASES, LAUNCH_SHA256)
+
+
+def test_a_route_is_named_exactly_where_a_launch_is_planned(route_sweep):
+    """mdm_gemm_route_of says "none" exactly where mdm_gemm_launch_of refuses (and the pair queries likewise): the refusals that
+    depend on the descriptor alone are part of the plan, not of the launchers."""
+    from mdm import _lib, ops
+    n = 0
+    for case in list(route_sweep.conv_cases(ops)) + list(route_sweep.plain_cases()):
+        for f in case[1:]:
+            assert (_lib.route_of(**dict(f)) == "none") == (_lib.launch_of(**dict(f)) is None), case[0]
+        if len(case) == 3:
+            route, planned = _lib.pair_route_of(dict(case[1]), dict(case[2])), _lib.pair_launch_of(dict(case[1]), dict(case[2]))
+            assert (route == "none") == (planned is None), case[0]
+            assert (route == "pair:two launches") == (planned is not None and len(planned) == 2), case[0]
+        n += 1
+    assert n == SWEEP_CASES
+
+
+# The fused 1x1 sites of the attention blocks on the 8x8 map, bf16, at the batches where the generic tile rule of the unfused routes
+# says 128 x 128 (M = batch x 64 pixels, N = C channels: unet6_config(32) and (64) at batch 256, unet6_config(128) at batch 100).
+# Before the geometry was planned from the route's own row these launched a quarter of the 64 x 64 tiles.
+BIG_FUSED_SITES = [("unet6_32", 256, 256, 1024), ("unet6_64", 256, 256, 1024), ("unet6_128", 100, 512, 800)]
+
+
+@pytest.mark.parametrize("preset,batch,chan,workgroups", BIG_FUSED_SITES, ids=[f"{p}-n{b}" for p, b, _, _ in BIG_FUSED_SITES])
+def test_fused_1x1_sites_launch_the_grid_of_the_64_tile(preset, batch, chan, workgroups):
+    """project_out with the next GroupNorm's forward fused (gnf) and the data gradient of project_in with the GroupNorm backward fused
+    (gnb): lin2<64,64>, one workgroup of 512 threads (conv_lin2's 4 x 2 waves) per 64 x 64 tile of the output."""
+    from mdm import _lib, ops
+    g = ops.ConvGeom(batch, 8, 8, chan, 0, chan, KH=1, KW=1, pad_t=0, pad_l=0, pad_b=0, pad_r=0)
+    gnf = ops.conv_fwd_fields(R.BF, g, 16, None, 16, 16, 16, gnf=dict(out=16, gamma=16, beta=16, stats=16, G=32, silu=1))
+    gnb = ops.conv_dgrad_t_fields(R.BF, g, 16, 16, 16, 0, gnb=dict(x=16, stats=16, gamma=16, beta=16, dgamma=16, dbeta=16, G=32, silu=1))
+    assert (batch * 64 // 128) * (chan // 128) >= 200
+    for f, lds in ((gnf, 4 * (64 + 64) * 128), (gnb, 16384 + 65536 + 4096 + 512)):
+        assert _lib.route_of(**f) == "lin2<64,64>"
+        assert _lib.launch_of(**f) == (workgroups, 1, 512, lds, 64, 64)
+        assert workgroups == (batch * 64 // 64) * (chan // 64)

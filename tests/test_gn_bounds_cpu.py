@@ -48,3 +48,23 @@ def test_fused_rows_reach_every_route_a_fused_descriptor_can_take(kind, rows):
     assert not missing, f"{kind}: routes of fused descriptors that no GPU row reaches: {sorted(missing)}"
     # the smallest batch of the sweep keeps every route
     assert all(row[2] == 4 for row in rows)
+
+
+@pytest.mark.parametrize("kind,rows", [("gnb", R.GNB_BIG_ROWS), ("gnf", R.GNF_BIG_ROWS)], ids=["gnb", "gnf"])
+def test_big_fused_rows_take_the_64_tile_and_its_grid(kind, rows):
+    """The fused 1x1 rows at M = 6400, N = 512, where an unfused convolution of the same shape takes 128 x 128 tiles: they qualify,
+    name lin2<64,64>, and the launch is planned on that route's own tile -- 100 x 8 workgroups."""
+    from mdm import _lib, ops
+    assert len(rows) == 2 and {row[1] for row in rows} == {4, 8}
+    for route, H, N, C, Co, k in rows:
+        assert route == "lin2<64,64>" and R.fused_route(kind, H, N, C, Co, k) == route, (kind, H, N)
+        g = R.fused_geom(H, N, C, Co, k)
+        if kind == "gnf":
+            plain = ops.conv_fwd_fields(1, g, 16, None, 16, 16, 16)
+            fused = ops.conv_fwd_fields(1, g, 16, None, 16, 16, 16, gnf=dict(out=16, gamma=16, beta=16, stats=16, G=R.FUSED_G, silu=1))
+        else:
+            plain = ops.conv_dgrad_t_fields(1, g, 16, 16, 16, 0)
+            fused = ops.conv_dgrad_t_fields(1, g, 16, 16, 16, 0, gnb=dict(x=16, stats=16, gamma=16, beta=16, dgamma=16, dbeta=16,
+                                                                          G=R.FUSED_G, silu=1))
+        assert _lib.route_of(**plain) == "lin2<128,128>" and _lib.launch_of(**plain)[:2] + _lib.launch_of(**plain)[4:] == (200, 1, 128, 128)
+        assert _lib.launch_of(**fused)[:2] + _lib.launch_of(**fused)[4:] == (800, 1, 64, 64)

@@ -22,8 +22,9 @@ import torch
 
 from _bounds import EPS_EXP, Buf, check_bound, gn_bwd_ref, gn_fwd_ref, gn_stats_in, rel_l2_bar, rne_bf16
 from _dropout_ref import ctl_words
-from _gn_rows import (BWD_ROWS, DROP_BASE, DT, EPS, FUSED_G, FWD_ROWS, GNB_ROWS, GNF_ROWS, KEY, OFFSET, R2, RATE, S128, TD, bwd_problem,
-                      fused_geom, fused_id, fused_route, fwd_problem, row_id, row_keep, rows_cover_every_instantiation)
+from _gn_rows import (BWD_ROWS, DROP_BASE, DT, EPS, FUSED_G, FWD_ROWS, GNB_BIG_ROWS, GNB_ROWS, GNF_BIG_ROWS, GNF_ROWS, KEY, OFFSET, R2, RATE,
+                      S128, TD, bwd_problem, fused_geom, fused_id, fused_route, fwd_problem, row_id, row_keep,
+                      rows_cover_every_instantiation)
 from _notes import note
 
 pytestmark = pytest.mark.gpu
@@ -265,7 +266,10 @@ def _run_gnb(row, T, variant):
     return B
 
 
-@pytest.mark.parametrize("row", GNB_ROWS, ids=[fused_id(r) for r in GNB_ROWS])
+GNB_ALL, GNF_ALL = GNB_ROWS + GNB_BIG_ROWS, GNF_ROWS + GNF_BIG_ROWS
+
+
+@pytest.mark.parametrize("row", GNB_ALL, ids=[fused_id(r) for r in GNB_ALL])
 def test_fused_backward_bounds(row):
     """dz = the data gradient (fp64 conv_dgrad_ref; the kernel's dz is off by at most (K + 8) 2^-23 mag, handed on as dy_err), then
     gn_bwd_ref of it: dx accumulated (acc0), with a residual-branch addend and the column sums (gnb_add, gnb_sum_img / _sum_all),
@@ -279,7 +283,7 @@ def test_fused_backward_bounds(row):
     dy = _q16(torch.randn(N, H, H, Co, generator=g))
     wt = _q16(torch.randn(taps, Co, C, generator=g) / (taps * Co) ** 0.5)                 # [tap][Cout][Cin]
     T = dict(x=x, dy=dy, wT=wt.transpose(1, 2).contiguous(), stats=gn_stats_in(x, FUSED_G, EPS), gamma=gamma, beta=beta,
-             silu=int(GNB_ROWS.index(row) % 3 != 2), prior=_q16(torch.randn(N, P, C, generator=g)),
+             silu=int(GNB_ALL.index(row) % 3 != 2), prior=_q16(torch.randn(N, P, C, generator=g)),
              addt=_q16(0.5 * torch.randn(N, P, C, generator=g)),
              pri=dict(dgamma=torch.randn(C, generator=g), dbeta=torch.randn(C, generator=g), sum_all=torch.randn(C, generator=g) + 2.0))
     dz, dzmag = conv_dgrad_ref(dy, wt, H, H, C, k, k, 1, (pd, pd, pd, pd))
@@ -322,7 +326,7 @@ def _run_gnf(row, T):
     return B
 
 
-@pytest.mark.parametrize("row", GNF_ROWS, ids=[fused_id(r) for r in GNF_ROWS])
+@pytest.mark.parametrize("row", GNF_ALL, ids=[fused_id(r) for r in GNF_ALL])
 def test_fused_forward_bounds(row):
     """y = conv + bias + time-embedding row + residual against fp64 (_bounds.check); the normalised output and the statistics as
     gn_fwd_ref(scheme="two_pass") of the y the kernel stored, read back: the GroupNorm's bound does not carry the convolution's."""
@@ -333,7 +337,7 @@ def test_fused_forward_bounds(row):
     g, gamma, beta = _fused_params(Co, 7 * C + Co + H + k)
     T = dict(x=_q16(torch.randn(N, H, H, C, generator=g)), wt=_q16(torch.randn(taps, Co, C, generator=g) / (taps * C) ** 0.5),
              bias=torch.randn(Co, generator=g), rv=torch.randn(N, Co, generator=g), resid=_q16(torch.randn(N, H, H, Co, generator=g)),
-             gamma=gamma, beta=beta, silu=int(GNF_ROWS.index(row) % 3 != 2))
+             gamma=gamma, beta=beta, silu=int(GNF_ALL.index(row) % 3 != 2))
     B = _run_gnf(row, T)
     _assert_guards(B, fused_id(row))
     acc, mag = conv_fwd_ref(T["x"], None, T["wt"], k, k, 1, (pd, pd, pd, pd), 0)

@@ -70,6 +70,7 @@ PARSER_REFUSALS = [      # header text, what the message must name
     ("int mdm_x(unsigned int n, void* stream);", ("cannot split", "unsigned int n", "mdm_x")),
     ("typedef struct mdm_s { float* a, b; } mdm_s;", ("one pointer per declaration", "mdm_s")),
     ("int mdm_x(int n, void* stream);\nstruct mdm_t;\n", ("cannot parse", "struct mdm_t")),
+    ("typedef struct mdm_s { int32_t a[4]; } mdm_s;", ("cannot split", "a[4]", "mdm_s")),      # an array is a pointer in a parameter only
 ]
 
 
@@ -124,7 +125,9 @@ def test_the_parsed_tables_are_the_types_the_wrappers_rely_on():
     assert _lib._PARAMS["mdm_add"] == ["dtype", "dst", "src", "n", "stream"]
     assert _lib._PROTOS["mdm_skinny_route_of"] == ([C.c_int32] * 5, C.c_char_p) and _lib._PROTOS["mdm_skinny_last_route"] == ([], C.c_char_p)
     assert _lib._PROTOS["mdm_skinny_route_names"] == ([C.c_void_p, C.c_int32], C.c_int32)
-    assert len(_lib._PROTOS) == 90 and len(_lib.EXPORTS) == 90
+    assert _lib._PROTOS["mdm_gemm_launch_of"] == ([C.POINTER(_lib.GemmDesc), C.c_void_p], C.c_int32)      # `int32_t out[6]`: a pointer
+    assert _lib._PROTOS["mdm_gemm_pair_launch_of"] == ([C.POINTER(_lib.GemmDesc)] * 2 + [C.c_void_p], C.c_int32)
+    assert len(_lib._PROTOS) == 92 and len(_lib.EXPORTS) == 92
 
 
 def test_call_binds_keywords_against_the_header_names():
