@@ -527,9 +527,12 @@ int mdm_sampler_update(const float* d_t, const float* d_next, float* x_t, float*
 /* ------------------------------------------------------------------------- *
  * Evaluation caller (the step after the sampler; tester.py:57-223, sampler.py:487-526): the similarity matrix of
  * generated images against data images is ONE fp32 contraction (mdm_gemm, layout 0) over unit-length rows.
- *   mdm_normalize01  y = (x - min) / (max - min) per image [N][E], NaN -> 0       (utils/datautils.py:211-222)
+ *   mdm_normalize01  y = (x - min) / (max - min) per image [N][E], NaN -> 0       (utils/datautils.py:211-222); min and max
+ *                    hand a NaN pixel on like torch's amin / amax: an image that holds one comes out all 0, as a constant image does
  *   mdm_unit_rows    y[r] = x[r] / max(||x[r]||, eps) over [R][D]                  (F.cosine_similarity's normalisation)
- *   mdm_col_argmax   per column of S[M][B]: largest value and the first row holding it (score.max(dim=0), tester.py:198)
+ *   mdm_col_argmax   per column of S[M][B]: largest value and the first row holding it (score.max(dim=0), tester.py:198), in
+ *                    torch's order: a NaN beats every number (the first NaN row), an all -inf column gives (-inf, 0); the index is
+ *                    below M always; val may be NULL
  * ------------------------------------------------------------------------- */
 int mdm_normalize01(const float* x, float* y, int N, int E, void* stream);
 int mdm_unit_rows(const float* x, float* y, int R, int D, float eps, void* stream);
@@ -560,6 +563,7 @@ int mdm_col_argmax(const float* S, int M, int B, float* val, int64_t* idx, void*
 int mdm_sqnorm(const float* g, int64_t n, float* out, void* stream);
 int mdm_optim_update(int kind, float* p, const float* g, float* buf0, float* buf1, float* ema, void* shadow_bf16,
                      int64_t n, const float* hp, const float* sqnorm, float max_norm, float gmul, void* stream);
+/* dst[i] = bf16(src[i]), round to nearest even, NaN stays NaN; n == 0 returns 0 without a launch (so does mdm_fill_f32) */
 int mdm_cast_bf16(const float* src, void* dst, int64_t n, void* stream);
 /* Transposed bf16 shadow of the conv filters for the data-gradient pass, from the bf16 shadow Pb the optimizer kernel writes:
  * for every 64x64 tile listed in `tiles` (device, int64 x5 per tile: element offset of one tap's [Cout][Cin] matrix, Cout,

@@ -8,20 +8,23 @@
 
 namespace mdm {
 
-// one workgroup per image: y = (x - min) / (max - min), NaN (constant image) -> 0
+// one workgroup per image: y = (x - min) / (max - min), NaN (constant image) -> 0.  fminf / fmaxf drop a NaN operand, amin / amax
+// of the reference hand it on: a NaN pixel is carried beside them and makes the range NaN, so the whole image comes out 0.
 __global__ __launch_bounds__(256) void normalize01_kernel(const float* x, float* y, int E) {
     const int img = blockIdx.x, t = threadIdx.x;
     const float* xi = x + (int64_t)img * E;
-    float lo = 3.0e38f, hi = -3.0e38f;
-    for (int i = t; i < E; i += 256) { const float v = xi[i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
+    float lo = __builtin_inff(), hi = -__builtin_inff(), bad = 0.f;
+    for (int i = t; i < E; i += 256) { const float v = xi[i]; lo = fminf(lo, v); hi = fmaxf(hi, v); if (v != v) bad = 1.f; }
     hi = wave_max(hi);
     lo = -wave_max(-lo);
-    __shared__ float s_lo[4], s_hi[4];
-    if ((t & 63) == 0) { s_lo[t >> 6] = lo; s_hi[t >> 6] = hi; }
+    bad = wave_max(bad);
+    __shared__ float s_lo[4], s_hi[4], s_bad[4];
+    if ((t & 63) == 0) { s_lo[t >> 6] = lo; s_hi[t >> 6] = hi; s_bad[t >> 6] = bad; }
     __syncthreads();
     lo = fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3]));
     hi = fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3]));
-    const float range = hi - lo;
+    bad = (s_bad[0] + s_bad[1]) + (s_bad[2] + s_bad[3]);
+    const float range = bad != 0.f ? __builtin_nanf("") : hi - lo;
     for (int i = t; i < E; i += 256) {
         const float v = (xi[i] - lo) / range;
         y[(int64_t)img * E + i] = (v != v) ? 0.f : v;
@@ -42,14 +45,22 @@ __global__ __launch_bounds__(256) void unit_rows_kernel(const float* x, float* y
     for (int i = t; i < D; i += 256) y[(int64_t)r * D + i] = xr[i] * inv;
 }
 
-// S[M][B] -> for every column b: the largest value and the FIRST row that holds it (torch.max(dim=0) tie rule)
+// torch.max(dim=0)'s order on (value, row): a NaN beats every number, among equals (two NaNs count as equal) the FIRST row wins
+__device__ __forceinline__ bool argmax_takes(float v, int i, float bv, int bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn != bn) return vn;
+    if (vn || v == bv) return i < bi;
+    return v > bv;
+}
+// S[M][B] -> for every column b: the largest value and the FIRST row that holds it (torch.max(dim=0) tie rule); a column with a NaN
+// gives (NaN, its first NaN row).  A lane starts from (-inf, past every row): any row of S takes it, so the index is always below M.
 __global__ __launch_bounds__(256) void col_argmax_kernel(const float* S, int M, int B, float* val, int64_t* idx) {
     const int b = blockIdx.x, t = threadIdx.x;
-    float best = -3.0e38f;
+    float best = -__builtin_inff();
     int bi = 0x7fffffff;
     for (int m = t; m < M; m += 256) {
         const float v = S[(int64_t)m * B + b];
-        if (v > best || (v == best && m < bi)) { best = v; bi = m; }
+        if (argmax_takes(v, m, best, bi)) { best = v; bi = m; }
     }
     __shared__ float sv[256];
     __shared__ int si[256];
@@ -59,7 +70,7 @@ __global__ __launch_bounds__(256) void col_argmax_kernel(const float* S, int M, 
         if (t < o) {
             const float v = sv[t + o];
             const int i = si[t + o];
-            if (v > sv[t] || (v == sv[t] && i < si[t])) { sv[t] = v; si[t] = i; }
+            if (argmax_takes(v, i, sv[t], si[t])) { sv[t] = v; si[t] = i; }
         }
         __syncthreads();
     }

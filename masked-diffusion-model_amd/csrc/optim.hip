@@ -314,6 +314,8 @@ extern "C" int mdm_split_shadow_t(const float* P, float* PsT, const int64_t* seg
     return launch_status("split_shadow_t");
 }
 extern "C" int mdm_cast_bf16(const float* src, void* dst, int64_t n, void* stream) {
+    MDM_REQUIRE(src && dst && n >= 0, "cast_bf16: bad arguments");
+    if (n == 0) return 0;
     hipLaunchKernelGGL(cast_bf16_kernel, dim3(ogrid(n)), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, n);
     return launch_status("cast_bf16");
 }
@@ -323,6 +325,8 @@ extern "C" int mdm_fill_segments_f32(float* base, const int64_t* segs, int nseg,
     return launch_status("fill_segments");
 }
 extern "C" int mdm_fill_f32(float* p, float v, int64_t n, void* stream) {
+    MDM_REQUIRE(p && n >= 0, "fill: bad arguments");
+    if (n == 0) return 0;
     hipLaunchKernelGGL(fill_kernel, dim3(ogrid(n)), dim3(256), 0, (hipStream_t)stream, p, v, n);
     return launch_status("fill");
 }

@@ -451,6 +451,8 @@ extern "C" int mdm_monitor_commit(const int64_t* loss_q40, int64_t* mon_q40, con
 extern "C" int mdm_sampler_x0(int dtype, const void* pred_nhwc, int Cp, const float* x_in, const float* s, int N, int C, int H,
                               int W, float* pred_nchw, float* shifted0, float* x0_hat, void* stream) {
     MDM_REQUIRE(pred_nhwc && x_in && x0_hat, "sampler_x0: bad arguments");
+    MDM_REQUIRE(dtype == MDM_F32 || dtype == MDM_BF16, "sampler_x0: bad dtype %d", dtype);
+    MDM_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && Cp >= C, "sampler_x0: bad shape (Cp >= C)");
     const int64_t total = (int64_t)N * C * H * W;
     if (dtype == MDM_BF16)
         hipLaunchKernelGGL((sampler_x0_kernel<bf16_t>), dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
@@ -480,7 +482,7 @@ extern "C" int mdm_sampler_step_params(const int32_t* timesteps, int T, int32_t*
 
 extern "C" int mdm_sampler_update(const float* d_t, const float* d_next, float* x_t, float* diff, int momentum, int64_t n,
                                   void* stream) {
-    MDM_REQUIRE(d_t && d_next && x_t, "sampler_update: bad arguments");
+    MDM_REQUIRE(d_t && d_next && x_t && n > 0, "sampler_update: bad arguments");
     hipLaunchKernelGGL(sampler_update_kernel, dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, d_t, d_next, x_t, diff, momentum, n);
     return launch_status("sampler_update");
 }

@@ -189,6 +189,65 @@ fp32, + prior, one rounding (as test_avgpool2's accumulate case).
 A CPU emulation in fp32 (tests/_temb_rows.py: four wave partials over k summed w0 + w1 + w2 + w3, slabs summed in order, silu and
 silu' in fp32, the embedding in fp32 numpy, colsum as 32 pixel-lane partials and their 32-term sum) stays inside these bounds on
 every row, and each planted fault leaves them (tests/test_bounds_cpu.py).
+
+The store kernels (csrc/optim.hip apart from optim_update_kernel), the loss and sampler kernels (the value side of csrc/sched.hip)
+and the evaluation kernels (csrc/eval.hip)
+-----------------------------------------------------------------------------------------------------------------------------------
+All fp32 arithmetic; u = 2^-24.  The library is built without any fast-math flag (csrc/Makefile: -O3 and nothing that relaxes
+floating point), so +, -, * are IEEE, sqrtf and / are correctly rounded, and the compiler contracts a product into an fma only where
+one expression holds a product AND a sum of it.  Three kernels sum; everything else is held BIT FOR BIT.
+
+mdm_sqnorm, ref = sum g^2 in fp64.  Every term is non-negative, so each rounding on the way from a term to the result is at most u of
+a partial sum that is itself at most ref: the error is (depth) u ref, whatever n is.  The depth, from sqnorm_kernel /
+sqnorm_final_kernel and the launcher (n4 = n / 4 float4, nb = min(1024, max(1, ceil(n4 / 256))) workgroups of 256):
+
+    T = ceil(n4 / (256 nb)) float4 per thread: 4 T chained fmaf (one rounding each, the square is not rounded)
+    <= 3 tail elements on thread 0 of workgroup 0, 6 shuffle adds, 2 adds over the four wave partials              (11)
+    second stage: ceil(nb / 256) <= 4 chained adds per lane, 6 shuffle adds, 2 adds                                (12)
+
+    |y - ref| <= (4 T + 32) 2^-24 ref              (depth 4 T + 23 as found; the other 9 u cover every second-order term)
+
+A row that is zero but for one 3.0 must give exactly 9.0: 9 + 0 is exact at every node.  That is the row that shows a MISSING
+element; among a million random terms one float4 is at the edge of the bound.
+
+mdm_loss_fwd_bwd.  r = ((x_in + pred) - s) - x0 is two or three IEEE additions of stored values (pred upcasts exactly), no product
+next to them: the same expression in numpy fp32 has the kernel's bits (`loss_residual32`).  dpred = 2.f * wn * r * inv_numel *
+gscale, left to right, inv_numel = 1.f / ((float)N * (float)C * (float)HW): products and one correctly rounded division, no sum, so
+nothing can contract -- bit for bit the numpy fp32 expression, rounded once (RNE) to a bf16 destination; the pad channels C .. Cp - 1
+are +0.  The loss word: ref = fp64 mean of w_n r32^2.  A term passes wn * r (1 rounding), the thread's chain of fmaf over its C T
+terms (T = ceil(N HW / (256 grid)) pixels per thread, grid = min(256, ceil(N HW / 256)) workgroups), 6 shuffle adds and 2 adds, the
+product with inv_numel (1) and inv_numel's own three roundings: C T + 13, all terms non-negative.  Each workgroup then rounds its
+partial once to Q23.40, half a unit = 2^-41, and the integer adds are exact:
+
+    |loss - ref| <= (C T + 16) 2^-24 ref + grid 2^-41;      the flag word is 0
+
+mdm_unit_rows, ref = x / max(||x||, eps) in fp64 with eps the fp32 value the call carries.  The sum of squares S has depth d =
+ceil(D / 256) + 8 (the lane's fmaf chain, 6 shuffle adds, 2 adds), non-negative terms: relative d u.  sqrtf halves that and rounds
+once (d / 2 + 1) u; max(., eps) is 1-Lipschitz (and exact), so the figure holds on either side of eps and across it; inv = 1.f / max
+is correctly rounded (+ u); y = x * inv (+ u):
+
+    |y - ref| <= (d / 2 + 4) 2^-24 |ref|           (d / 2 + 3 to first order; the fourth u covers the second-order terms, d <= 200)
+
+A zero row is exactly +0 (0 * (1 / eps)); a row with ||x|| < eps is x / eps under the same bound.
+
+Bit for bit, and why:
+    mdm_normalize01     (x - lo) / (hi - lo), then NaN -> 0: one subtraction, one correctly rounded division, and min / max, which do
+                        not round: torch fp32 nan_to_num((x - amin) / (amax - amin), nan=0) on the CPU.  A NaN pixel makes amin and
+                        amax NaN and the whole image 0; a constant image is 0 / 0 -> 0.
+    mdm_col_argmax      comparisons only: torch.max(dim=0), values and indices: the first row among equals, a NaN beats every number
+                        (the first NaN row), an all -inf column gives (-inf, 0); the index is below M always.
+    mdm_sampler_x0      sh0 = x_in + pred, x0_hat = sh0 - s: one addition each; pred_nchw moves bits.  Pad channels of pred are
+                        never read.
+    mdm_sampler_update  diff = d_next - d_t; x_t + diff (two additions, no product) or the bits of d_next.
+    mdm_cast_bf16       v_cvt_pk_bf16_f32, round to nearest even, NaN stays NaN: torch's .to(bfloat16).
+    mdm_transpose_shadow_bf16, mdm_split_shadow, mdm_split_shadow_t
+                        move bits / round to bf16 twice (hi = bf16(x), lo = bf16(x - hi): x - hi is exact in fp32): the layouts the
+                        kernel comments give, restated below (`transpose_want`, `split_want`, `split_t_want`).
+    the two fills       the fill value's bits (-0.0 stays -0.0).
+
+A CPU emulation in numpy fp32 (tests/_store_rows.py: the sqnorm tree with per-thread chains, waves and both stages in the kernel's
+order, the loss tree, unit_rows; fmaf(a, a, c) as the fp64 a a + c rounded to fp32) stays inside these bounds on every row, and each
+planted fault is rejected by at least one row (tests/test_store_rows_cpu.py).
 """
 import torch
 import torch.nn.functional as F
@@ -773,3 +832,127 @@ def colsum_ref(dY, prior_img=None, prior_bias=None):
         r, b = pi + s, b + 2.0 ** -24 * (pi.abs() + sa)
     pb = _f64(prior_bias) if prior_bias is not None else torch.zeros(C, dtype=torch.float64)
     return {"per_img": (r, b), "dbias": (pb + s.sum(0), (N * P + 8) * 2.0 ** -23 * (pb.abs() + sa.sum(0)))}
+
+
+# ------------------------------------------------------------------ store, loss, sampler and evaluation kernels (module docstring)
+def sqnorm_geom(n):
+    """the launch of mdm_sqnorm restated: (n4 float4 of the body, nb workgroups, T float4 per thread at most)"""
+    n4 = n // 4
+    nb = min(1024, max(1, -(-n4 // 256)))
+    return n4, nb, -(-n4 // (nb * 256))
+
+
+def sqnorm_ref(g):
+    """g [n] as stored -> (sum g^2 in fp64, bound): python floats"""
+    g = _f64(g).reshape(-1)
+    ref = float((g * g).sum())
+    return ref, (4 * sqnorm_geom(g.numel())[2] + 32) * 2.0 ** -24 * ref
+
+
+def loss_geom(N, HW):
+    """(grid, T): workgroups of the loss launch and the pixels one thread walks at most"""
+    npix = N * HW
+    grid = min(256, max(1, -(-npix // 256)))
+    return grid, -(-npix // (grid * 256))
+
+
+def loss_residual32(pred, x_in, s, x0, C):
+    """r = ((x_in + pred) - s) - x0 in fp32, in that order: pred NHWC [N][H][W][Cp] as stored, the rest NCHW fp32 -> [N][C][H][W] fp32.
+    Additions of stored values only: the kernel's bits."""
+    pv = pred.detach().cpu().float()[..., :C].permute(0, 3, 1, 2).contiguous()
+    r = x_in.detach().cpu().float() + pv
+    if s is not None:
+        r = r - s.detach().cpu().float()
+    return r - x0.detach().cpu().float()
+
+
+def loss_ref(r32, w):
+    """r32 [N][C][H][W] (loss_residual32), w [N] or None -> (fp64 mean of w_n r^2, bound): python floats"""
+    N, C, H, W = r32.shape
+    t = r32.double() ** 2
+    if w is not None:
+        t = t * _f64(w).reshape(N, 1, 1, 1)
+    ref = float(t.mean())
+    grid, T = loss_geom(N, H * W)
+    return ref, (C * T + 16) * 2.0 ** -24 * ref + grid * 2.0 ** -41
+
+
+def dpred_want(r32, w, Cp, gscale, dtype):
+    """2.f * wn * r * inv_numel * gscale left to right in numpy fp32, pad channels +0, one rounding to `dtype` -> NHWC [N][H][W][Cp]"""
+    import numpy as np
+    f32 = np.float32
+    N, C, H, W = r32.shape
+    inv_numel = f32(1.0) / (f32(N) * f32(C) * f32(H * W))
+    wn = (np.ones(N, f32) if w is None else w.detach().cpu().numpy().astype(f32)).reshape(N, 1, 1, 1)
+    g = f32(2.0) * wn * r32.numpy() * inv_numel * f32(gscale)
+    assert g.dtype == f32
+    out = torch.zeros(N, H, W, Cp, dtype=torch.float32)
+    out[..., :C] = torch.from_numpy(g).permute(0, 2, 3, 1)
+    return out.to(dtype)
+
+
+def unit_rows_ref(x, eps):
+    """x [R][D] as stored, eps as passed -> (x / max(||x||, fp32(eps)), bound) fp64"""
+    x = _f64(x)
+    D = x.shape[1]
+    e = float(torch.tensor(eps, dtype=torch.float32))
+    ref = x / x.norm(dim=1, keepdim=True).clamp_min(e)
+    d = -(-D // 256) + 8
+    return ref, (d / 2 + 4) * 2.0 ** -24 * ref.abs()
+
+
+def normalize01_want(x):
+    """torch fp32 on the CPU: nan_to_num((x - amin) / (amax - amin), nan=0) per image, x [N][E]"""
+    x = x.detach().cpu().float()
+    lo, hi = x.amin(1, keepdim=True), x.amax(1, keepdim=True)
+    return torch.nan_to_num((x - lo) / (hi - lo), nan=0.0)
+
+
+def col_argmax_want(S):
+    """torch.max(dim=0) of the stored S [M][B] -> (values, indices)"""
+    m = S.detach().cpu().float().max(dim=0)
+    return m.values, m.indices
+
+
+def sampler_x0_want(pred, x_in, s, C):
+    """-> (pred_nchw, shifted0, x0_hat) fp32 NCHW: pred NHWC [N][H][W][Cp] as stored"""
+    pv = pred.detach().cpu().float()[..., :C].permute(0, 3, 1, 2).contiguous()
+    sh0 = x_in.detach().cpu().float() + pv
+    return pv, sh0, (sh0 - s.detach().cpu().float() if s is not None else sh0)
+
+
+def sampler_update_want(d_t, d_next, x_t, momentum):
+    """-> (diff, new x_t)"""
+    diff = d_next - d_t
+    return diff, (x_t + diff if momentum else d_next.clone())
+
+
+def transpose_want(Pb, filters):
+    """Pb: int16 bits [n] (CPU); filters [(off, taps, Cout, Cin)] -> {off: bits [taps][Cin][Cout]}: PT[off + tap Cout Cin + c Cout + r]
+    = Pb[off + tap Cout Cin + r Cin + c]"""
+    return {off: Pb[off:off + t * co * ci].view(t, co, ci).transpose(1, 2).contiguous() for off, t, co, ci in filters}
+
+
+def _split_halves(x):
+    """x fp32 [..., 32 k] -> int16 bits of the same shape viewed as [..., 64 k] halves: per 32-element block, 32-bit word j (j < 16) =
+    (hi of element j, hi of element 16 + j), word 16 + j = the lo halves of the same pair; hi = bf16(x), lo = bf16(x - hi)"""
+    b = x.reshape(*x.shape[:-1], -1, 2, 16)                     # [.., block, half, j]
+    hi = b.to(torch.bfloat16)
+    lo = (b - hi.float()).to(torch.bfloat16)
+    pair = lambda h: h.view(torch.int16).transpose(-1, -2)      # [.., block, j, half]: element j low, element 16 + j high
+    return torch.stack((pair(hi), pair(lo)), -3).reshape(*x.shape[:-1], -1)
+
+
+def split_want(P, segs):
+    """P fp32 [n] (CPU), segs [(off, len)] -> {off: int16 bits [2 len]} of mdm_split_shadow's arrangement"""
+    return {off: _split_halves(P[off:off + ln]) for off, ln in segs}
+
+
+def split_t_want(P, filters):
+    """filters [(off, taps, Cout, Cin)] -> {off: int16 bits [2 taps Cin Cout]}: taps flipped, each tap transposed to [Cin][Cout], every
+    row of Cout in mdm_split_shadow's arrangement"""
+    out = {}
+    for off, t, co, ci in filters:
+        wt = P[off:off + t * co * ci].view(t, co, ci).flip(0).transpose(1, 2).contiguous()
+        out[off] = _split_halves(wt).reshape(-1)
+    return out

@@ -41,6 +41,11 @@ def test_similarity_matrix_at_benchmark_size():
     assert float((S - want).abs().max()) < 6e-6          # fp32 sums over 3072 elements in another order
     val, idx = E.col_argmax(S.cuda())
     wv, wi = want.max(dim=0)
+    # the kernel against torch.max(dim=0) of the matrix it was GIVEN: values and indices, bit for bit (first row among equals) ...
+    sv, si = S.max(dim=0)
+    assert torch.equal(idx.cpu(), si) and torch.equal(val.cpu().view(torch.int32), sv.view(torch.int32))
+    assert int(idx.min()) >= 0 and int(idx.max()) < 1000
+    # ... and against the host's matrix, whose entries differ from S by the summation order
     assert torch.equal(idx.cpu(), wi) or float((val.cpu() - wv).abs().max()) < 1e-6
 
 
