@@ -2,6 +2,8 @@
 
 include/mdm_hip.h is the only statement of the C ABI: the two descriptor structs, every prototype and the parameter
 names below are parsed from it at import.  To add an entry point, declare it in the header -- nothing else.
+include/mdm_vis.h is the presentation ABI of the same library (image grids, `mdm_vis_*`): parsed the same way into
+`VIS_PROTOS` / `VIS_EXPORTS`, bound by `load()` and served by `call` and `Recording` next to the core table.
 
 The product path has NO fallback: if the shared library or the header is missing, or a call
 returns non-zero, a RuntimeError is raised.
@@ -21,6 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # (MDM_LIB_PATH: load another BUILD of the same library -- A/B timing of two builds on one box; it selects a file, not a code path)
 LIB_PATH = os.environ.get("MDM_LIB_PATH") or os.path.join(_HERE, "libmdm_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "mdm_hip.h"))
+VIS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_vis.h")
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 _SCALARS = {"int": i32, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32}
@@ -70,12 +73,17 @@ def parse_header(text):
     return structs, protos
 
 
-if not os.path.exists(HEADER_PATH):
-    raise RuntimeError(
-        f"{HEADER_PATH} is missing: it is the only statement of libmdm_hip.so's C ABI and this binding is built from it at import "
-        "(include/ sits next to masked-diffusion-model_amd/).  There is no fallback.")
+for _path in (HEADER_PATH, VIS_HEADER_PATH):
+    if not os.path.exists(_path):
+        raise RuntimeError(
+            f"{_path} is missing: it is the only statement of libmdm_hip.so's C ABI and this binding is built from it at import "
+            "(include/ sits next to masked-diffusion-model_amd/).  There is no fallback.")
 with open(HEADER_PATH) as _f:
     _STRUCTS, _DECLS = parse_header(_f.read())
+with open(VIS_HEADER_PATH) as _f:
+    _VIS_STRUCTS, _VIS_DECLS = parse_header(_f.read())
+if _VIS_STRUCTS or set(_VIS_DECLS) & set(_DECLS) or not all(n.startswith("mdm_vis_") for n in _VIS_DECLS):
+    raise RuntimeError(f"{VIS_HEADER_PATH}: the presentation header declares `mdm_vis_*` functions only, none of them twice")
 
 _DESC_PTR = {}
 
@@ -102,6 +110,10 @@ _DESC_PTR.update({"mdm_gemm_desc*": C.POINTER(GemmDesc), "mdm_gn_desc*": C.POINT
 _PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _DECLS.items()}
 _PARAMS = {name: [n for n, _ in params] for name, (_, params) in _DECLS.items()}
 EXPORTS = list(_PROTOS)
+# the same two tables of include/mdm_vis.h, kept apart: the core tables are exactly what mdm_hip.h declares
+VIS_PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _VIS_DECLS.items()}
+VIS_PARAMS = {name: [n for n, _ in params] for name, (_, params) in _VIS_DECLS.items()}
+VIS_EXPORTS = list(VIS_PROTOS)
 
 _lib = None
 
@@ -116,7 +128,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C masked-diffusion-model_amd/csrc`).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in _PROTOS.items():
+    for name, (args, res) in (*_PROTOS.items(), *VIS_PROTOS.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
@@ -255,7 +267,7 @@ class GraphExec:
 
 @functools.lru_cache(maxsize=None)
 def _signature(name):
-    return inspect.Signature([inspect.Parameter(p, inspect.Parameter.POSITIONAL_OR_KEYWORD) for p in _PARAMS[name]])
+    return inspect.Signature([inspect.Parameter(p, inspect.Parameter.POSITIONAL_OR_KEYWORD) for p in (_PARAMS.get(name) or VIS_PARAMS[name])])
 
 
 def call(name, *args, **kw):

@@ -16,6 +16,7 @@ What is different from the reference loop (same arithmetic, same RNG order in re
 from __future__ import annotations
 
 import functools
+import os
 import types
 
 import numpy as np
@@ -129,6 +130,57 @@ class Sampler:
             g = gather_shards(h.to(x0.device).transpose(0, 1).contiguous(), n).transpose(0, 1)
             return g if h.is_cuda else g.cpu()
         return gather_shards(x0, n), [gather_hist(h) for h in hist]
+
+    # ---- image grids (mdm/visuals.py: one range launch + one grid launch each, built on the device) ---------
+    def _batch(self, sample):
+        """A batch as the grid kernels read it: float32 on the scheduler's device, images contiguous (a strided view stays a view)."""
+        x = sample.to(self.Scheduler.device, torch.float32)
+        ok = x.dim() == 4 and x[0].is_contiguous() and (x.shape[0] == 1 or x.stride(0) >= x[0].numel())
+        return x if ok else x.contiguous()
+
+    def _save_image_grid(self, sample, normalization="global", dir_save=None, file_sample=None):
+        """sampler.py:369-387: `nrow = ceil(sqrt(batch))`, normalize01_global ('global') / normalize01 ('image') / nothing (anything
+        else, as upstream), make_grid -> the fp32 grid [Cg, Hg, Wg] on the device; with both path parts also the PNG `save_image`
+        writes.  An empty batch returns None (upstream's ZeroDivisionError branch)."""
+        from . import visuals
+        if sample.shape[0] == 0:
+            return None
+        nrow = int(np.ceil(np.sqrt(sample.shape[0])))
+        norm = normalization if normalization in ("global", "image") else None
+        if dir_save is None or file_sample is None:
+            return visuals.make_grid(self._batch(sample), nrow, norm)
+        grid, u8 = visuals.make_grid(self._batch(sample), nrow, norm, out="both")
+        visuals.save_png(u8, os.path.join(dir_save, file_sample))
+        return grid
+
+    def _save_multi_index_image_grid(self, sample, nrow=None, normalization="global", option=None, time_major=False):
+        """sampler.py:390-417: one grid per sample over its time axis -> list of fp32 grids on the device.  `sample` is upstream's
+        [N, T', C, H, W], or with `time_major` a history of `sample()` as it lies in memory, [T+1, N, C, H, W]: sample n is then
+        read in place, its frames N C H W elements apart, and no transposed copy is made.  'skip_first' drops frame 0."""
+        from . import visuals
+        if normalization not in ("global", "image", None):
+            raise UnboundLocalError(f"sample_i undefined for normalization={normalization!r}")
+        frames = sample.to(self.Scheduler.device, torch.float32)
+        if not time_major:
+            frames = frames.transpose(0, 1)                         # a view: [T', N, C, H, W]
+        if option == "skip_first":
+            frames = frames[1:]
+        if nrow is None:
+            nrow = int(np.ceil(np.sqrt(sample.shape[0 if time_major else 1])))      # of T' BEFORE the skip, as upstream
+        return [visuals.make_grid(self._batch(frames[:, i]), nrow, normalization) for i in range(frames.shape[1])]
+
+    def _save_image_pair_grid(self, data1, data2, dir_save, file_save):
+        """sampler.py:474-484: the two batches interleaved (one device copy), normalize01 per image, `nrow = 2 ceil(sqrt(batch))`,
+        written as a PNG; -> the fp32 grid.  Upstream passes the result through `make_grid(normalize=True)` once more: a min-max
+        over the whole batch, which after normalize01 runs from 0 to 1 whenever at least one image is not constant -- (v - 0) / 1,
+        the identity bit for bit -- so that pass is not built (a batch of constant images is all 0 here and there)."""
+        from . import visuals
+        d1, d2 = self._batch(data1), self._batch(data2)
+        data = torch.stack((d1, d2), 1).reshape(2 * d1.shape[0], *d1.shape[1:])
+        nrow = int(np.ceil(np.sqrt(d1.shape[0]))) * 2
+        grid, u8 = visuals.make_grid(data, nrow, "image", out="both")
+        visuals.save_png(u8, os.path.join(dir_save, file_save))
+        return grid
 
     # ------------------------------------------------------------------------------
     def _predict(self, model, x_in_nchw, time, fused_nhwc):

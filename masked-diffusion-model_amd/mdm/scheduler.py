@@ -278,10 +278,14 @@ class Scheduler:
 
     def degrade_training(self, black_area_num, img, mean_option=None, mean_area=None):
         x_t, masks, mp, _ = self._degrade(black_area_num, img, mean_option, mean_area, rng_stream=1)
+        return (x_t, masks) + self.degradation_visuals(masks, mp)
+
+    @staticmethod
+    def degradation_visuals(masks, mp):
+        """(degradation_mask, mean_pixel) of scheduler.py:320-321 from the keep-mask [N, C, H, W] and the fill colour [N, C]:
+        the two tensors `degrade_training` returns for visualisation only."""
         mp4 = mp[:, :, None, None]
-        degrade_mask = (1 - masks) * mp4 + masks                         # scheduler.py:320 (visualisation)
-        mean_mask = torch.ones_like(x_t) * mp4                            # scheduler.py:321
-        return x_t, masks, degrade_mask, mean_mask
+        return (1 - masks) * mp4 + masks, torch.ones_like(masks) * mp4
 
     def degrade_independent_base_sampling(self, black_area_num_t, img, mean_option=None, mean_area=None, _stream=3):
         x_t, masks, mp, _ = self._degrade(black_area_num_t, img, mean_option, mean_area, rng_stream=_stream)

@@ -4,8 +4,17 @@
 :82-193, `_run_epoch` :196-215, `train` :218-273, `_save_ema_momentum_sample` :409-425);
 `BaseTrainer` mirrors trainer_masked.py (:31-82, :95-183, :186-208, :211-272), whose constructor is
 broken upstream (D2) -- the arithmetic is mean-shift with no shift, int timesteps and three return
-values.  Image grids / wandb / matplotlib output of the reference are out of scope:
-samples are saved as tensors.
+values.  wandb / matplotlib output of the reference is out of scope; samples are saved as tensors, and with
+`args.visuals` also as the PNG upstream writes.
+
+`args.visuals` turns on the reference's image surface (ms:58-59, 235-236, 263-264, 301-318, 423-425): `train()` calls
+`visualizer.reset()` at the top of every epoch and `visualizer.display_current_results(epoch, self.get_current_visuals(epoch))`
+in the save block, and `_save_ema_momentum_sample` sets the two EMA sample grids and writes `ema_sample_{epoch:05d}.png`.
+`get_current_visuals` is upstream's OrderedDict of fp32 CHW grids, built on the device (mdm/visuals.py: per grid one range launch
+and one grid launch, no host sync).  The visual tensors the step does not keep (`degradation_mask`, `mean_pixel`,
+`reconstructed_img`, `inverse_shift_reconstructed_img`, `mask`) are made when it is called, from the buffers the last step
+left; with `visuals` off `_run_batch` and `train()` issue exactly what they did before.  Under data parallelism the training
+grids are THIS rank's tensors (upstream draws the main process's too).
 
 `args.monitor` turns on the reference's per-step logging surface (ms:61-64, 175-179, 249-250, 321-334): `loss_names` is
 its five names, the five attributes hold the step's values after every `_run_batch`, `get_current_losses()` /
@@ -51,6 +60,10 @@ class Trainer:
             raise ValueError("args.defer_loss needs args.monitor: a deferred loss is read from the monitor ring")
         self.loss_names = list(MonitorRing.COLUMNS[:5]) if self.monitor else ["train_loss"]          # ms:61
         self.mean_names = ["ema_sample_mean"]                                                        # ms:64
+        self.visuals = bool(getattr(args, "visuals", False))
+        self.train_visual_names = ["input", "degraded_img", "degrade_binary_masks", "degradation_mask", "mean_pixel", "shift",
+                                   "shifted_degrade_img", "reconstructed_img", "inverse_shift_reconstructed_img", "mask"]   # ms:58
+        self.sample_visual_names = ["ema_sample_result_normalize_global", "ema_sample_result_normalize_local"]          # ms:59
         # what `accelerator.save_state(path)` / `load_state(path)` cover (main_train_masked.py:195-225 hooks)
         reg = getattr(accelerator, "register_for_checkpointing", None)
         if reg is not None:
@@ -152,6 +165,37 @@ class Trainer:
                 loss_batch.append(loss)
         return loss_batch
 
+    def _make_visual_tensors(self):
+        """The visual tensors of ms:58 that the step does not keep, from what the last step left: `mask` (ms:140),
+        `reconstructed_img` (ms:142) and `inverse_shift_reconstructed_img` (ms:145) are the three outputs of ONE mdm_sampler_x0
+        launch on the net's output, `step.x_in` and `step.s`; `degradation_mask` / `mean_pixel` are the expressions of
+        `Scheduler.degrade_training` (scheduler.py:320-321) on `step.mask` / `step.mean_pixel`.  With 'non_shift' (and in the
+        base trainer) `step.s` is never written and is the zero tensor upstream's shift is.  No host sync."""
+        from ._lib import call, ptr, stream
+        s, m = self.step, self.model
+        if not hasattr(self, "input"):
+            raise RuntimeError("get_current_visuals: no step has run yet")
+        self.degradation_mask, self.mean_pixel = Scheduler.degradation_visuals(s.mask, s.mean_pixel)
+        self.shift = s.s
+        self.mask, self.reconstructed_img, self.inverse_shift_reconstructed_img = (torch.empty_like(s.x0) for _ in range(3))
+        call("mdm_sampler_x0", dtype=m.dt, pred_nhwc=ptr(m.y_out.data), Cp=m.cout_p, x_in=ptr(s.x_in), s=ptr(s.s), N=m.N, C=m.cin,
+             H=m.H, W=m.W, pred_nchw=ptr(self.mask), shifted0=ptr(self.reconstructed_img),
+             x0_hat=ptr(self.inverse_shift_reconstructed_img), stream=stream())
+
+    def get_current_visuals(self, epoch):
+        """ms:301-318: for every name of `train_visual_names` its batch as a grid, normalised over the batch ('_normalize_global')
+        and per image ('_normalize_local'), then the `sample_visual_names` as `_save_ema_momentum_sample` left them -> OrderedDict
+        of fp32 [Cg, Hg, Wg] device tensors."""
+        self._make_visual_tensors()
+        ret = OrderedDict()
+        for name in self.train_visual_names:
+            img = getattr(self, name)
+            ret[name + "_normalize_global"] = self.Sampler._save_image_grid(img, normalization="global")
+            ret[name + "_normalize_local"] = self.Sampler._save_image_grid(img, normalization="image")
+        for name in self.sample_visual_names:
+            ret[name] = getattr(self, name)
+        return ret
+
     def get_current_losses(self):
         """ms:321-327."""
         return OrderedDict((name, float(getattr(self, name))) for name in self.loss_names if isinstance(name, str))
@@ -176,7 +220,10 @@ class Trainer:
         self.global_step = global_step
         loss_mean_epoch = []
         self.model.train()
+        show = self.visuals and visualizer is not None and self.accelerator.is_main_process
         for epoch in range(epoch_start, epoch_start + epoch_length):
+            if show:
+                visualizer.reset()                                                                   # ms:235-236
             loss = self._epoch_losses(self._run_epoch(epoch, epoch_length, resume_step, dirs, visualizer))
             if self.accelerator.is_main_process:
                 loss_mean_epoch.append(statistics.mean(loss))
@@ -190,6 +237,8 @@ class Trainer:
                 # files are still written by the main process alone.
                 if getattr(a, "use_ema", False) and getattr(a, "sampling", "momentum") == "momentum":
                     self._save_ema_momentum_sample(dirs, epoch)
+                if show:
+                    visualizer.display_current_results(epoch, self.get_current_visuals(epoch))       # ms:263-264
                 save_path = os.path.join(dirs.list_dir["checkpoint"], f"checkpoint-epoch-{epoch}")
                 self.accelerator.save_state(save_path)                                           # ms:267-268
         self.loss_mean_epoch = loss_mean_epoch
@@ -209,6 +258,10 @@ class Trainer:
         self.ema_sample_mean = sample_0.mean()                                   # ms:421
         if self.accelerator.is_main_process:
             torch.save(sample_0.cpu(), os.path.join(dirs.list_dir["ema_sample_img"], f"ema_sample_{epoch:05d}.pt"))
+        if self.visuals:                                                         # ms:423-425; the PNG is the global grid
+            png = (dirs.list_dir["ema_sample_img"], f"ema_sample_{epoch:05d}.png") if self.accelerator.is_main_process else (None, None)
+            self.ema_sample_result_normalize_global = self.Sampler._save_image_grid(sample_0, "global", *png)
+            self.ema_sample_result_normalize_local = self.Sampler._save_image_grid(sample_0, "image")
         return sample_0
 
 
@@ -218,6 +271,8 @@ class BaseTrainer(Trainer):
 
     def __init__(self, args, dataloader, dataset, model, ema_model, optimizer, lr_scheduler, accelerator):
         super().__init__(args, dataloader, dataset, [None] * 3, model, ema_model, optimizer, lr_scheduler, accelerator)
+        self.train_visual_names = ["input", "degraded_img", "degradation_mask", "mask", "mean_pixel", "degrade_binary_masks",
+                                   "reconstructed_img"]                                                              # base:58
 
     def _run_batch(self, batch, input, epoch, epoch_length, resume_step, dirs, visualizer):
         loss = self._step(input)
