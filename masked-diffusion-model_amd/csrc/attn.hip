@@ -21,6 +21,10 @@
 //
 // 256 threads = 4 waves, one per SIMD (the accumulators of the C = 256 backward need the whole register file);
 // wave w owns 16 of the tile's 64 queries (keys in the dK/dV kernel).  L must be a multiple of 16.
+//
+// L <= 64 (the 8x8 and 4x4 maps of the train step) is one key tile: the same two kernels run the *_tile1 bodies there -- every
+// global load issued at entry, one wait, one barrier, only the real rows staged, results stored as whole rows -- see "one tile"
+// below and DESIGN finding 63.  make EXTRA=-DMDM_STAMP compiles cycle stamps into these kernels (scripts/stamp_attn.py).
 #include "common.h"
 
 namespace mdm {
@@ -94,14 +98,438 @@ __device__ __forceinline__ void store4bf(bf16_t* p, const f32x4& v) {
 }
 constexpr float NEG_BIG = -1.0e30f;
 
+#ifdef MDM_STAMP
+// debug build only (make EXTRA=-DMDM_STAMP, scripts/stamp_attn.py): cycles per segment of attn_fwd_kernel and the two bodies of
+// attn_bwd_kernel, one 8-entry record per wave, plain stores.  Every mark drains vmcnt and lgkmcnt first, so a stamped kernel is
+// slower than the shipped one and a segment is "until its memory operations have come back"; an MFMA still in the pipe is billed
+// to the segment that first reads its result.
+constexpr int ASTAMP_RECS = 4096;
+__device__ unsigned long long g_astamp_buf[ASTAMP_RECS * 8];
+__device__ __forceinline__ unsigned long long astamp_now() {
+    unsigned long long t;
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    __builtin_amdgcn_sched_barrier(0);
+    return t;
+}
+enum { AS_LDS = 0, AS_P1, AS_SM, AS_P2, AS_ST };   // entry (or the previous tile's end) -> operands in LDS | first product | softmax / dS | second product | stores
+struct AStamp {
+    unsigned long long t0, tp, seg[5];
+    __device__ __forceinline__ void begin() { t0 = tp = astamp_now(); seg[0] = seg[1] = seg[2] = seg[3] = seg[4] = 0; }
+    __device__ __forceinline__ void mark(int i) { const unsigned long long x = astamp_now(); seg[i] += x - tp; tp = x; }
+    // kind: 1 forward, 2 dQ, 3 dK/dV
+    __device__ __forceinline__ void store(int kind) const {
+        const int widx = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        if ((threadIdx.x & 63) == 0 && widx < ASTAMP_RECS) {
+            unsigned long long* r = g_astamp_buf + widx * 8;
+            r[0] = t0; r[1] = seg[0]; r[2] = seg[1]; r[3] = seg[2]; r[4] = seg[3]; r[5] = seg[4]; r[6] = tp; r[7] = kind;
+        }
+    }
+};
+#define MDM_TA(...) __VA_ARGS__
+#else
+#define MDM_TA(...)
+#endif
+
+// ------------------------------------------------------------------------------------------------ one tile: L <= 64
+// The U-Net's small maps (8x8, 4x4: L = 64, 16) are ONE key tile, and a launch is a few dozen workgroups on 256 CUs: nothing hides a
+// workgroup's latencies, so the kernels' time is the chain of their memory round trips (DESIGN finding 63).  The *_tile1 bodies
+// below are the L <= 64 case of attn_fwd_kernel / attn_bwd_kernel with ONE exposed round trip: every global load of the workgroup
+// is issued at entry (the rows to stage into uint4 registers, the wave's own fragments, lse), then one wait, the LDS writes and one
+// barrier.  Only the L real rows are loaded and staged; NB = L / 16 is uniform, so a 16-row block beyond L is skipped as a whole
+// (its scores / probabilities are the zeros the multi-tile code computes for masked rows, its half of a transposed fragment is
+// zeros instead of an LDS read, a k-step with no valid row is not multiplied) and a wave whose 16 rows are beyond L leaves
+// after the barrier.  FULL: L == 64, no block test anywhere.  Arithmetic, orientation and tile layout are those of the
+// multi-tile bodies at one tile: the forward drops the online-softmax carry (m = max, l = sum: the carry multiplied zeros by
+// alpha), the products add the same terms in the same order.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));      // (a register array of these is promoted where one of HIP's uint4 is not)
+template <int D>            // rows [0, L) x D of src (row pitch ld) -> registers; chunk idx = t + 256 i of the tile, 16 bytes each
+__device__ __forceinline__ void rows_load(u32x4 (&r)[D / 32], const bf16_t* src, int ld, int L, int t, bool full) {
+    constexpr int CPR = D / 8;
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+        const int idx = t + 256 * i, row = idx / CPR, c = idx - row * CPR;
+        // (a wave's chunks of one i lie in one 16-row block and L % 16 == 0: the test is wave-uniform)
+        if (full || __builtin_amdgcn_readfirstlane(row) < L) {
+            asm volatile("");      // (keeps the branch: a speculated load would fetch the rows beyond L)
+            r[i] = *reinterpret_cast<const u32x4*>(src + (int64_t)row * ld + c * 8);
+        }
+    }
+}
+template <int D>
+__device__ __forceinline__ void rows_store(char* lds, const u32x4 (&r)[D / 32], int L, int t, bool full) {
+    constexpr int CPR = D / 8;
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+        const int idx = t + 256 * i, row = idx / CPR, c = idx - row * CPR;
+        if (full || __builtin_amdgcn_readfirstlane(row) < L) *reinterpret_cast<u32x4*>(lds + tile_off<D>(row, c)) = r[i];
+    }
+}
+__device__ __forceinline__ float8 bf8_floats(const u32x4& r) {          // eight bf16 of one 16-byte chunk
+    float8 o;
+    o.lo = make_float4(__uint_as_float(r[0] << 16), __uint_as_float(r[0] & 0xffff0000u), __uint_as_float(r[1] << 16), __uint_as_float(r[1] & 0xffff0000u));
+    o.hi = make_float4(__uint_as_float(r[2] << 16), __uint_as_float(r[2] & 0xffff0000u), __uint_as_float(r[3] << 16), __uint_as_float(r[3] & 0xffff0000u));
+    return o;
+}
+// frag_tr at L <= 64, for a k-step whose rows 32 s .. 32 s + 15 are real: the rows 32 s + 16 .. 32 s + 31 may lie beyond L (hi_ok
+// false, uniform), where nobody wrote the LDS.  That half is zeros: read from the real rows again and dropped by a select -- no
+// branch, so the reads of the next fragment still overlap this one's MFMA
+template <int D>
+__device__ __forceinline__ bf16x8 frag_tr_nb(const char* tile, int s, int d0, int lane, bool hi_ok) {
+    const int i = lane & 15, g = lane >> 4;
+    const int q = i >> 2, p = i & 3;
+    const int r0 = 32 * s + 4 * g + q, r1 = hi_ok ? r0 + 16 : r0;
+    const int chunk = (d0 >> 3) + (p >> 1), sub = (p & 1) * 8;
+    const char* p0 = tile + tile_off<D>(r0, chunk) + sub;
+    const char* p1 = tile + tile_off<D>(r1, chunk) + sub;
+    bf4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf4_t __attribute__((address_space(3)))*)(p0));
+    bf4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((bf4_t __attribute__((address_space(3)))*)(p1));
+    const bf16x4 l4 = *reinterpret_cast<bf16x4*>(&lo), h4 = hi_ok ? *reinterpret_cast<bf16x4*>(&hi) : (bf16x4){0, 0, 0, 0};
+    bf16x8 f;
+    f[0] = l4[0]; f[1] = l4[1]; f[2] = l4[2]; f[3] = l4[3];
+    f[4] = h4[0]; f[5] = h4[1]; f[6] = h4[2]; f[7] = h4[3];
+    return f;
+}
+
+// A wave's 16 x D result block (lane & 15 = row, registers = columns 16 db + 4 g + r) -> 16 global rows of pitch ld.  Stored from
+// the accumulator layout, an instruction writes 32-byte pieces of 16 different rows (the stamps of the multi-tile kernels at
+// (32, 64, 256): 5 700 cycles until the forward's stores are acknowledged, 8 400 for dK / dV -- as much as staging the operands).
+// Through a patch of LDS that only this wave touches (tile layout, no barrier: a wave's LDS operations complete in order) every
+// instruction stores whole rows: four times fewer, four times wider.  dst and ld * 2 must be multiples of 16 bytes.
+template <int D>
+__device__ __forceinline__ void rows16_out(char* patch, bf16_t* dst, int ld, const f32x4 (&acc)[D / 16], int lane) {
+    constexpr int CPR = D / 8;
+    const int i = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int db = 0; db < D / 16; ++db) {
+        uint2 r;
+        r.x = (uint32_t)f2bf(acc[db][0]) | ((uint32_t)f2bf(acc[db][1]) << 16);
+        r.y = (uint32_t)f2bf(acc[db][2]) | ((uint32_t)f2bf(acc[db][3]) << 16);
+        *reinterpret_cast<uint2*>(patch + tile_off<D>(i, 2 * db + (g >> 1)) + (g & 1) * 8) = r;
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < D / 32; ++j) {
+        const int idx = lane + 64 * j, row = idx / CPR, c = idx - row * CPR;
+        const uint4 v = *reinterpret_cast<const uint4*>(patch + tile_off<D>(row, c));
+        *reinterpret_cast<uint4*>(dst + (int64_t)row * ld + c * 8) = v;
+    }
+}
+constexpr int attn_patch_bytes(int D) { return 16 * 2 * D; }     // per wave and result
+// Workgroups per image at L <= 64.  false: one, wave w owns the 16-row block w.  true: one per 16-row block (grid.x = L / 16): all four
+// waves stage the whole other side, wave 0 multiplies, the others leave after the barrier.  A CU's L1 keeps only so many misses in
+// flight, so a workgroup's staging time grows with its bytes; splitting cuts the bytes per CU (backward: 160 KB -> 88 / 112 KB at
+// C = 256) and uses 256 CUs instead of 64, for more L2 traffic in all.  Chosen by the train step, not by the isolated launch
+// (finding 63): the backward gains from it, the forward (96 -> 72 KB) lost.
+constexpr bool T1_SPLIT_FWD = false, T1_SPLIT_BWD = true;
+
+template <int D, bool FULL>
+__device__ __forceinline__ void attn_fwd_tile1(char* lds, const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
+                                               int L, float scale) {
+    constexpr int KS = D / 32, DB = D / 16;
+    char* Kt = lds;
+    char* Vt = lds + 64 * 2 * D;
+    MDM_TA(AStamp st; st.begin();)
+    const int t = threadIdx.x, lane = t & 63, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int NB = FULL ? 4 : L >> 4;                                     // valid 16-row blocks
+    const int rb = T1_SPLIT_FWD ? (int)blockIdx.x : wave;                    // this wave's 16-row block
+    const bool active = T1_SPLIT_FWD ? wave == 0 : (FULL || wave < NB);
+    const int n = blockIdx.y, ld = 3 * D;
+    const bf16_t* base = qkv + (int64_t)n * L * ld;
+    const int qrow = rb * 16 + (lane & 15);
+    u32x4 kr[D / 32], vr[D / 32];
+    bf16x8 Qf[KS];
+    rows_load<D>(kr, base + D, ld, L, t, FULL);
+    rows_load<D>(vr, base + 2 * D, ld, L, t, FULL);
+    if (active) {
+        asm volatile("");
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) Qf[ks] = *reinterpret_cast<const bf16x8*>(base + (int64_t)qrow * ld + ks * 32 + 8 * g);
+    }
+    asm volatile("" ::: "memory");          // every load above is issued before the first wait (else a guarded load and its store merge into one block)
+    rows_store<D>(Kt, kr, L, t, FULL);
+    rows_store<D>(Vt, vr, L, t, FULL);
+    __syncthreads();
+    MDM_TA(st.mark(AS_LDS);)
+    if (!active) {
+        MDM_TA(st.store(1);)
+        return;
+    }
+    f32x4 s[4];
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+        s[jb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (FULL || jb < NB) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+                s[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Kt, 16 * jb, ks, lane), Qf[ks], s[jb], 0, 0, 0);
+        }
+    }
+    MDM_TA(st.mark(AS_P1);)
+    float tmax = NEG_BIG;
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+#pragma clang fp contract(off)             // the product is rounded, as the multi-tile body's select makes it: not fused into s * scale - m below
+            s[jb][r] = (FULL || jb < NB) ? s[jb][r] * scale : NEG_BIG;
+            tmax = fmaxf(tmax, s[jb][r]);
+        }
+    const float m = fmaxf(NEG_BIG, group_max(tmax));
+    float lsum = 0.f;
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float p = (FULL || jb < NB) ? __expf(s[jb][r] - m) : 0.f;      // (a masked score gave __expf(-1e30 - m) = 0)
+            s[jb][r] = p;
+            lsum += p;
+        }
+    lsum = group_sum(lsum);
+    const bf16x8 pf0 = pack_pair(s[0], s[1]), pf1 = pack_pair(s[2], s[3]);
+    MDM_TA(st.mark(AS_SM);)
+    f32x4 O[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db) {
+        O[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        O[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Vt, 0, 16 * db, lane, FULL || NB > 1), pf0, O[db], 0, 0, 0);
+        if (FULL) O[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Vt, 1, 16 * db, lane, true), pf1, O[db], 0, 0, 0);
+    }
+    if (!FULL && NB > 2) {                            // keys 32 .. 63: one branch around the whole k-step, none inside it
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+            O[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Vt, 1, 16 * db, lane, NB > 3), pf1, O[db], 0, 0, 0);
+    }
+    MDM_TA(st.mark(AS_P2);)
+    const float inv = 1.f / lsum;
+#pragma unroll
+    for (int db = 0; db < DB; ++db) { O[db][0] *= inv; O[db][1] *= inv; O[db][2] *= inv; O[db][3] *= inv; }
+    rows16_out<D>(lds + 2 * 64 * 2 * D + wave * attn_patch_bytes(D), o + ((int64_t)n * L + rb * 16) * D, D, O, lane);
+    if (g == 0) lse[(int64_t)n * L + qrow] = m + __logf(lsum);
+    MDM_TA(st.mark(AS_ST); st.store(1);)
+}
+
+template <int D, bool FULL>
+__device__ __forceinline__ void attn_bwd_dq_tile1(char* lds, const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
+                                                  const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
+                                                  float* __restrict__ delta, bf16_t* __restrict__ dqkv, int L, float scale) {
+    constexpr int KS = D / 32, DB = D / 16;
+    char* Kt = lds;
+    char* Vt = lds + 64 * 2 * D;
+    MDM_TA(AStamp st; st.begin();)
+    const int t = threadIdx.x, lane = t & 63, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int NB = FULL ? 4 : L >> 4;
+    const int rb = T1_SPLIT_BWD ? (int)blockIdx.x : wave;                    // this wave's 16-row block
+    const bool active = T1_SPLIT_BWD ? wave == 0 : (FULL || wave < NB);
+    const int n = blockIdx.y, ld = 3 * D;
+    const bf16_t* base = qkv + (int64_t)n * L * ld;
+    const int qrow = rb * 16 + (lane & 15);
+    u32x4 kr[D / 32], vr[D / 32];
+    bf16x8 Qf[KS], dOf[KS], Of[KS];
+    float ls = 0.f;
+    rows_load<D>(kr, base + D, ld, L, t, FULL);
+    rows_load<D>(vr, base + 2 * D, ld, L, t, FULL);
+    if (active) {
+        asm volatile("");
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            Qf[ks] = *reinterpret_cast<const bf16x8*>(base + (int64_t)qrow * ld + ks * 32 + 8 * g);
+            dOf[ks] = *reinterpret_cast<const bf16x8*>(d_o + ((int64_t)n * L + qrow) * D + ks * 32 + 8 * g);
+            Of[ks] = *reinterpret_cast<const bf16x8*>(o + ((int64_t)n * L + qrow) * D + ks * 32 + 8 * g);
+        }
+        ls = lse[(int64_t)n * L + qrow];
+    }
+    asm volatile("" ::: "memory");          // every load above is issued before the first wait (else a guarded load and its store merge into one block)
+    rows_store<D>(Kt, kr, L, t, FULL);
+    rows_store<D>(Vt, vr, L, t, FULL);
+    __syncthreads();
+    MDM_TA(st.mark(AS_LDS);)
+    if (!active) {
+        MDM_TA(st.store(2);)
+        return;
+    }
+    float dl = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dl = fmaf(bf2f((bf16_t)dOf[ks][e]), bf2f((bf16_t)Of[ks][e]), dl);
+    dl = group_sum(dl);                               // delta[q] = sum_d dO[q][d] O[q][d]
+    if (g == 0) delta[(int64_t)n * L + qrow] = dl;
+    f32x4 s[4], dp[4];
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+        s[jb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dp[jb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (FULL || jb < NB) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                s[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Kt, 16 * jb, ks, lane), Qf[ks], s[jb], 0, 0, 0);
+                dp[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Vt, 16 * jb, ks, lane), dOf[ks], dp[jb], 0, 0, 0);
+            }
+        }
+    }
+    MDM_TA(st.mark(AS_P1);)
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float p = (FULL || jb < NB) ? __expf(s[jb][r] * scale - ls) : 0.f;
+            s[jb][r] = p * (dp[jb][r] - dl) * scale;                   // dS
+        }
+    const bf16x8 f0 = pack_pair(s[0], s[1]), f1 = pack_pair(s[2], s[3]);
+    MDM_TA(st.mark(AS_SM);)
+    f32x4 dQ[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db) {
+        dQ[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dQ[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Kt, 0, 16 * db, lane, FULL || NB > 1), f0, dQ[db], 0, 0, 0);
+        if (FULL) dQ[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Kt, 1, 16 * db, lane, true), f1, dQ[db], 0, 0, 0);
+    }
+    if (!FULL && NB > 2) {
+#pragma unroll
+        for (int db = 0; db < DB; ++db)
+            dQ[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Kt, 1, 16 * db, lane, NB > 3), f1, dQ[db], 0, 0, 0);
+    }
+    MDM_TA(st.mark(AS_P2);)
+    rows16_out<D>(lds + 2 * 64 * 2 * D + wave * attn_patch_bytes(D), dqkv + ((int64_t)n * L + rb * 16) * ld, ld, dQ, lane);
+    MDM_TA(st.mark(AS_ST); st.store(2);)
+}
+
+// dK / dV at one tile.  delta comes from the dO chunks this thread stages and the O chunks at the same places (O never enters LDS):
+// 8 products per chunk, then a shuffle tree over the D / 8 lanes that hold a row.  That is another summation order than the
+// 4-threads-per-query loop of attn_bwd_dkv_body, so dK (through dS) can differ from it in the last bit; dV does not use delta.
+template <int D, bool FULL>
+__device__ __forceinline__ void attn_bwd_dkv_tile1(char* lds, const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ o,
+                                                   const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
+                                                   bf16_t* __restrict__ dqkv, int L, float scale) {
+    constexpr int KS = D / 32, DB = D / 16, CPR = D / 8;
+    char* Qt = lds;
+    char* Gt = lds + 64 * 2 * D;           // dO tile
+    float* del_n = reinterpret_cast<float*>(lds + 4 * 64 * 2 * D);       // (behind the two result patches of every wave)
+    MDM_TA(AStamp st; st.begin();)
+    const int t = threadIdx.x, lane = t & 63, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int NB = FULL ? 4 : L >> 4;
+    const int rb = T1_SPLIT_BWD ? (int)blockIdx.x : wave;                    // this wave's 16-row block
+    const bool active = T1_SPLIT_BWD ? wave == 0 : (FULL || wave < NB);
+    const int n = blockIdx.y, ld = 3 * D;
+    const bf16_t* base = qkv + (int64_t)n * L * ld;
+    const int krow = rb * 16 + (lane & 15);
+    u32x4 qr[D / 32], gr[D / 32], orr[D / 32];
+    bf16x8 Kf[KS], Vf[KS];
+    f32x4 l4[4];
+    rows_load<D>(qr, base, ld, L, t, FULL);
+    rows_load<D>(gr, d_o + (int64_t)n * L * D, D, L, t, FULL);
+    rows_load<D>(orr, o + (int64_t)n * L * D, D, L, t, FULL);
+    if (active) {
+        asm volatile("");
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            Kf[ks] = *reinterpret_cast<const bf16x8*>(base + (int64_t)krow * ld + D + ks * 32 + 8 * g);
+            Vf[ks] = *reinterpret_cast<const bf16x8*>(base + (int64_t)krow * ld + 2 * D + ks * 32 + 8 * g);
+        }
+        const float* lse_n = lse + (int64_t)n * L;
+#pragma unroll
+        for (int qb = 0; qb < 4; ++qb) {              // queries 16 qb + 4 g + r; a block beyond L: a clamped address, the values are not used
+            const int qa = 16 * qb + 4 * g;
+            l4[qb] = *reinterpret_cast<const f32x4*>(lse_n + (FULL || qa < L ? qa : L - 4));
+        }
+    }
+    asm volatile("" ::: "memory");          // every load above is issued before the first wait (else a guarded load and its store merge into one block)
+    rows_store<D>(Qt, qr, L, t, FULL);
+    rows_store<D>(Gt, gr, L, t, FULL);
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+        const int idx = t + 256 * i, row = idx / CPR, c = idx - row * CPR;
+        if (FULL || __builtin_amdgcn_readfirstlane(row) < L) {
+            const float8 a = bf8_floats(orr[i]), b = bf8_floats(gr[i]);
+            float sum = a.lo.x * b.lo.x;
+            sum = fmaf(a.lo.y, b.lo.y, sum); sum = fmaf(a.lo.z, b.lo.z, sum); sum = fmaf(a.lo.w, b.lo.w, sum);
+            sum = fmaf(a.hi.x, b.hi.x, sum); sum = fmaf(a.hi.y, b.hi.y, sum); sum = fmaf(a.hi.z, b.hi.z, sum); sum = fmaf(a.hi.w, b.hi.w, sum);
+#pragma unroll
+            for (int w = 1; w < CPR; w <<= 1) sum += __shfl_xor(sum, w, 64);
+            if (c == 0) del_n[row] = sum;
+        }
+    }
+    __syncthreads();
+    MDM_TA(st.mark(AS_LDS);)
+    if (!active) {
+        MDM_TA(st.store(3);)
+        return;
+    }
+    f32x4 s[4], dp[4];
+#pragma unroll
+    for (int qb = 0; qb < 4; ++qb) {
+        s[qb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dp[qb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (FULL || qb < NB) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                s[qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Qt, 16 * qb, ks, lane), Kf[ks], s[qb], 0, 0, 0);
+                dp[qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Gt, 16 * qb, ks, lane), Vf[ks], dp[qb], 0, 0, 0);
+            }
+        }
+    }
+    MDM_TA(st.mark(AS_P1);)
+    // lane: key (lane & 15), queries 16 qb + 4 g + r
+#pragma unroll
+    for (int qb = 0; qb < 4; ++qb) {
+        if (FULL || qb < NB) {
+            const f32x4 d4 = *reinterpret_cast<const f32x4*>(del_n + 16 * qb + 4 * g);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float p = __expf(s[qb][r] * scale - l4[qb][r]);
+                s[qb][r] = p;                                            // P
+                dp[qb][r] = p * (dp[qb][r] - d4[r]) * scale;             // dS
+            }
+        }                                                                // (else: P = dS = 0, as they stand)
+    }
+    const bf16x8 p0 = pack_pair(s[0], s[1]), p1 = pack_pair(s[2], s[3]);
+    const bf16x8 e0 = pack_pair(dp[0], dp[1]), e1 = pack_pair(dp[2], dp[3]);
+    MDM_TA(st.mark(AS_SM);)
+    f32x4 dK[DB], dV[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db) {
+        dK[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dV[db] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        dV[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Gt, 0, 16 * db, lane, FULL || NB > 1), p0, dV[db], 0, 0, 0);
+        if (FULL) dV[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Gt, 1, 16 * db, lane, true), p1, dV[db], 0, 0, 0);
+        dK[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Qt, 0, 16 * db, lane, FULL || NB > 1), e0, dK[db], 0, 0, 0);
+        if (FULL) dK[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Qt, 1, 16 * db, lane, true), e1, dK[db], 0, 0, 0);
+    }
+    if (!FULL && NB > 2) {
+#pragma unroll
+        for (int db = 0; db < DB; ++db) {
+            dV[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Gt, 1, 16 * db, lane, NB > 3), p1, dV[db], 0, 0, 0);
+            dK[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr_nb<D>(Qt, 1, 16 * db, lane, NB > 3), e1, dK[db], 0, 0, 0);
+        }
+    }
+    MDM_TA(st.mark(AS_P2);)
+    char* patch = lds + 2 * 64 * 2 * D + wave * 2 * attn_patch_bytes(D);
+    bf16_t* row = dqkv + ((int64_t)n * L + rb * 16) * ld;
+    rows16_out<D>(patch, row + D, ld, dK, lane);
+    rows16_out<D>(patch + attn_patch_bytes(D), row + 2 * D, ld, dV, lane);
+    MDM_TA(st.mark(AS_ST); st.store(3);)
+}
+// dynamic LDS of the one-tile launches: two operand tiles, a result patch per wave (dK / dV: two), delta of 64 queries
+constexpr int attn_tile1_lds(int D, bool bwd) { return (bwd ? 4 : 3) * 64 * 2 * D + (bwd ? 4 * 64 : 0); }
+
 // ------------------------------------------------------------------------------------------------ forward
 template <int D>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o, float* __restrict__ lse,
                                                        int L, float scale) {
     constexpr int KS = D / 32, DB = D / 16;
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (L <= 64) {                                                         // one key tile, one workgroup per image
+        if (L == 64) attn_fwd_tile1<D, true>(lds, qkv, o, lse, L, scale);
+        else attn_fwd_tile1<D, false>(lds, qkv, o, lse, L, scale);
+        return;
+    }
     char* Kt = lds;
     char* Vt = lds + 64 * 2 * D;
+    MDM_TA(AStamp st; st.begin();)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, g = lane >> 4;
     const int n = blockIdx.y, q0 = blockIdx.x * 64 + wave * 16;
     const int ld = 3 * D;
@@ -121,6 +549,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
         load_tile<D>(Kt, base + D, k0, L, ld, t);
         load_tile<D>(Vt, base + 2 * D, k0, L, ld, t);
         __syncthreads();
+        MDM_TA(st.mark(AS_LDS);)
         f32x4 s[4];
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) {
@@ -129,6 +558,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
             for (int ks = 0; ks < KS; ++ks)
                 s[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Kt, 16 * jb, ks, lane), Qf[ks], s[jb], 0, 0, 0);
         }
+        MDM_TA(st.mark(AS_P1);)
         float tmax = NEG_BIG;
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb)
@@ -155,11 +585,13 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
 #pragma unroll
         for (int db = 0; db < DB; ++db) { O[db][0] *= alpha; O[db][1] *= alpha; O[db][2] *= alpha; O[db][3] *= alpha; }
         const bf16x8 pf0 = pack_pair(s[0], s[1]), pf1 = pack_pair(s[2], s[3]);
+        MDM_TA(st.mark(AS_SM);)
 #pragma unroll
         for (int db = 0; db < DB; ++db) {
             O[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(Vt, 0, 16 * db, lane), pf0, O[db], 0, 0, 0);
             O[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(Vt, 1, 16 * db, lane), pf1, O[db], 0, 0, 0);
         }
+        MDM_TA(st.mark(AS_P2);)
     }
     if (q_ok) {
         const float inv = 1.f / lsum;
@@ -172,6 +604,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const bf16_t* __restrict_
         }
         if (g == 0) lse[(int64_t)n * L + qrow] = m + __logf(lsum);
     }
+    MDM_TA(st.mark(AS_ST); st.store(1);)
 }
 
 
@@ -326,6 +759,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* lds, const bf16_t* __rest
     constexpr int KS = D / 32, DB = D / 16;
     char* Kt = lds;
     char* Vt = lds + 64 * 2 * D;
+    MDM_TA(AStamp st; st.begin();)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, g = lane >> 4;
     const int n = blockIdx.y, q0 = blockIdx.x * 64 + wave * 16;
     const int ld = 3 * D;
@@ -354,6 +788,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* lds, const bf16_t* __rest
         load_tile<D>(Kt, base + D, k0, L, ld, t);
         load_tile<D>(Vt, base + 2 * D, k0, L, ld, t);
         __syncthreads();
+        MDM_TA(st.mark(AS_LDS);)
         f32x4 s[4], dp[4];
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb) {
@@ -365,6 +800,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* lds, const bf16_t* __rest
                 dp[jb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Vt, 16 * jb, ks, lane), dOf[ks], dp[jb], 0, 0, 0);
             }
         }
+        MDM_TA(st.mark(AS_P1);)
 #pragma unroll
         for (int jb = 0; jb < 4; ++jb)
 #pragma unroll
@@ -374,17 +810,20 @@ __device__ __forceinline__ void attn_bwd_dq_body(char* lds, const bf16_t* __rest
                 s[jb][r] = p * (dp[jb][r] - dl) * scale;                   // dS
             }
         const bf16x8 f0 = pack_pair(s[0], s[1]), f1 = pack_pair(s[2], s[3]);
+        MDM_TA(st.mark(AS_SM);)
 #pragma unroll
         for (int db = 0; db < DB; ++db) {
             dQ[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(Kt, 0, 16 * db, lane), f0, dQ[db], 0, 0, 0);
             dQ[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(Kt, 1, 16 * db, lane), f1, dQ[db], 0, 0, 0);
         }
+        MDM_TA(st.mark(AS_P2);)
     }
     if (q_ok) {
         bf16_t* row = dqkv + ((int64_t)n * L + qrow) * ld;
 #pragma unroll
         for (int db = 0; db < DB; ++db) store4bf(row + 16 * db + 4 * g, dQ[db]);
     }
+    MDM_TA(st.mark(AS_ST); st.store(2);)
 }
 
 // ------------------------------------------------------------------------------------------------ backward: dK, dV
@@ -397,6 +836,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* lds, const bf16_t* __res
     constexpr int KS = D / 32, DB = D / 16;
     char* Qt = lds;
     char* Gt = lds + 64 * 2 * D;           // dO tile
+    MDM_TA(AStamp st; st.begin();)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, g = lane >> 4;
     const int n = blockIdx.y, kk0 = blockIdx.x * 64 + wave * 16;
     const int ld = 3 * D;
@@ -436,6 +876,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* lds, const bf16_t* __res
         load_tile<D>(Qt, base, q0, L, ld, t);
         load_tile<D>(Gt, d_o + (int64_t)n * L * D, q0, L, D, t);
         __syncthreads();
+        MDM_TA(st.mark(AS_LDS);)
         f32x4 s[4], dp[4];
 #pragma unroll
         for (int qb = 0; qb < 4; ++qb) {
@@ -447,6 +888,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* lds, const bf16_t* __res
                 dp[qb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(Gt, 16 * qb, ks, lane), Vf[ks], dp[qb], 0, 0, 0);
             }
         }
+        MDM_TA(st.mark(AS_P1);)
         // lane: key (lane & 15), queries q0 + 16 qb + 4 g + r
 #pragma unroll
         for (int qb = 0; qb < 4; ++qb) {
@@ -464,6 +906,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* lds, const bf16_t* __res
         }
         const bf16x8 p0 = pack_pair(s[0], s[1]), p1 = pack_pair(s[2], s[3]);
         const bf16x8 e0 = pack_pair(dp[0], dp[1]), e1 = pack_pair(dp[2], dp[3]);
+        MDM_TA(st.mark(AS_SM);)
 #pragma unroll
         for (int db = 0; db < DB; ++db) {
             dV[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(Gt, 0, 16 * db, lane), p0, dV[db], 0, 0, 0);
@@ -471,6 +914,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* lds, const bf16_t* __res
             dK[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(Qt, 0, 16 * db, lane), e0, dK[db], 0, 0, 0);
             dK[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(Qt, 1, 16 * db, lane), e1, dK[db], 0, 0, 0);
         }
+        MDM_TA(st.mark(AS_P2);)
     }
     if (k_ok) {
         bf16_t* row = dqkv + ((int64_t)n * L + krow) * ld;
@@ -480,6 +924,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(char* lds, const bf16_t* __res
             store4bf(row + 2 * D + 16 * db + 4 * g, dV[db]);
         }
     }
+    MDM_TA(st.mark(AS_ST); st.store(3);)
 }
 
 
@@ -725,6 +1170,16 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const bf16_t* __restrict_
                                                        const bf16_t* __restrict__ d_o, const float* __restrict__ lse,
                                                        float* __restrict__ delta, bf16_t* __restrict__ dqkv, int L, float scale) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (L <= 64) {
+        if (blockIdx.z == 0) {
+            if (L == 64) attn_bwd_dq_tile1<D, true>(lds, qkv, o, d_o, lse, delta, dqkv, L, scale);
+            else attn_bwd_dq_tile1<D, false>(lds, qkv, o, d_o, lse, delta, dqkv, L, scale);
+        } else {
+            if (L == 64) attn_bwd_dkv_tile1<D, true>(lds, qkv, o, d_o, lse, dqkv, L, scale);
+            else attn_bwd_dkv_tile1<D, false>(lds, qkv, o, d_o, lse, dqkv, L, scale);
+        }
+        return;
+    }
     if (blockIdx.z == 0) attn_bwd_dq_body<D>(lds, qkv, o, d_o, lse, delta, dqkv, L, scale);
     else attn_bwd_dkv_body<D>(lds, qkv, o, d_o, lse, dqkv, L, scale);
 }
@@ -756,14 +1211,17 @@ template <int D>
 static int attn_launch(int kernel, const bf16_t* qkv, bf16_t* o, const bf16_t* d_o, float* lse, float* delta, bf16_t* dqkv,
                        int N, int L, float scale, hipStream_t s) {
     constexpr int bytes = 2 * 64 * 2 * D;
+    constexpr int fwd1 = attn_tile1_lds(D, false), bwd1 = attn_tile1_lds(D, true);       // L <= 64: the one-tile bodies
+    constexpr int bwd_max = bytes + 4 * ATTN_BWD_MAX_L > bwd1 ? bytes + 4 * ATTN_BWD_MAX_L : bwd1;
+    static_assert(fwd1 <= 160 * 1024 && bwd_max <= 160 * 1024, "attention: LDS of a CU");
     static bool configured = false;
     if (!configured) {
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          bytes + 4 * ATTN_BWD_MAX_L));
+        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, fwd1));
+        MDM_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, bwd_max));
         configured = true;
     }
-    dim3 grid((unsigned)cdiv(L, 64), (unsigned)N);
+    const bool split = L <= 64 && (kernel == AK_FWD ? T1_SPLIT_FWD : T1_SPLIT_BWD);      // one workgroup per 16-row block
+    dim3 grid((unsigned)(split ? L / 16 : cdiv(L, 64)), (unsigned)N);
     if constexpr (D >= 64) {
         constexpr int dma_bytes = (D <= 128 ? 3 : 2) * 2 * 64 * 2 * D;
         if (kernel == AK_FWD_DMA) {
@@ -788,9 +1246,9 @@ static int attn_launch(int kernel, const bf16_t* qkv, bf16_t* o, const bf16_t* d
         }
     }
     if (kernel == AK_FWD) {
-        hipLaunchKernelGGL((attn_fwd_kernel<D>), grid, dim3(256), bytes, s, qkv, o, lse, L, scale);
+        hipLaunchKernelGGL((attn_fwd_kernel<D>), grid, dim3(256), L <= 64 ? fwd1 : bytes, s, qkv, o, lse, L, scale);
     } else if (kernel == AK_BWD) {
-        hipLaunchKernelGGL((attn_bwd_kernel<D>), dim3(grid.x, grid.y, 2), dim3(256), bytes + 4 * L, s, qkv, (const bf16_t*)o, d_o,
+        hipLaunchKernelGGL((attn_bwd_kernel<D>), dim3(grid.x, grid.y, 2), dim3(256), L <= 64 ? bwd1 : bytes + 4 * L, s, qkv, (const bf16_t*)o, d_o,
                            (const float*)lse, delta, dqkv, L, scale);
     } else {
         set_error("attention: no kernel %d at head width %d", kernel, D);
@@ -1069,6 +1527,17 @@ extern "C" int mdm_attn_f32_small_fwd(const float* qkv, float* o, float* S, int 
 #undef MDM_ATTN_F32
     return launch_status("attn_f32_small_fwd");
 }
+
+#ifdef MDM_STAMP
+extern "C" int mdm_debug_stamps_attn(unsigned long long* out, int reset) {      // out: 4096 * 8 entries
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mdm::g_astamp_buf), ASTAMP_RECS * 8 * 8) != hipSuccess) return -1;
+    if (reset) {
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(mdm::g_astamp_buf)) != hipSuccess || hipMemset(p, 0, ASTAMP_RECS * 8 * 8) != hipSuccess) return -1;
+    }
+    return 0;
+}
+#endif
 
 extern "C" int mdm_attn_supported(int dtype, int L, int C) { return attn_route(0, dtype, L, C) >= 0 ? 1 : 0; }
 extern "C" const char* mdm_attn_route_of(int which, int dtype, int L, int C) { return attn_route_name(attn_route(which, dtype, L, C)); }
