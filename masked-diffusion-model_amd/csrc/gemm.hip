@@ -2315,7 +2315,7 @@ __global__ __launch_bounds__(64 * NW) void wgrad_lin_kernel(mdm_gemm_desc d, int
 // Work item = (tile, range of slabs [k0, k1)): the host cuts the (tile, slab) space of a whole group into one contiguous
 // share per CU (plan_wgrad_group), so a tile that is cut writes its partial sums to a `slot` ([9][128][64] fp32) and
 // tile_parts_reduce_kernel adds the slots; an uncut tile goes straight to the gradient.
-// Requires: 3x3, stride 1, pad 1, OW in {8, 16, 32}, OH a power of two, OH OW >= 64, bf16; M a multiple of 128 or one partly filled
+// Requires: 3x3, stride 1, pad 1, OW in {8, 16, 32, 64}, OH a power of two, OH OW >= 64, bf16; M a multiple of 128 or one partly filled
 // tile (M < 128, 8 | M), N a multiple of 64 or one partly filled tile: the two 8-channel ends of the U-Net ride along on zero operands.
 // ----------------------------------------------------------------------------
 constexpr int TAPS_BM = 128, TAPS_BN = 64, TAPS_SLOT_FLOATS = 9 * TAPS_BM * TAPS_BN;

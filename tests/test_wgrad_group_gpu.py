@@ -14,13 +14,14 @@ TILE_BITS, K_BITS, GK_TAPS = 12, 16, 3
 # N, H, C0, C1, Cout, stride, ups, kernel, splitk, accumulate
 GROUP_A = [(4, 8, 64, 0, 64, 1, 0, 3, 1, 0), (2, 16, 64, 0, 128, 1, 0, 1, 1, 0), (8, 16, 128, 0, 128, 1, 0, 3, 4, 1)]
 GROUP_B = [(4, 8, 64, 64, 128, 1, 0, 3, 1, 0), (2, 32, 64, 0, 256, 1, 0, 3, 1, 0), (4, 16, 8, 0, 128, 1, 0, 3, 1, 0)]
-# the 16 shapes of test_kernels_gpu.test_grouped_weight_gradients_match_self_contained_ones, once: at 256 CUs some tiles are cut
+# the 16 shapes of test_kernels_gpu.test_grouped_weight_gradients_match_self_contained_ones, once: at Q_CUT queues some tiles are cut
 # (partial slots + tile_parts_reduce_kernel), which the three short layers of GROUP_B are not
 GROUP_D = [s + (3, 0, 0) for s in
            [(8, 8, 64, 0, 64, 1, 0), (8, 8, 64, 0, 128, 1, 0), (4, 16, 64, 64, 64, 1, 0), (4, 32, 128, 0, 128, 1, 0), (8, 16, 64, 0, 64, 2, 0),
             (4, 8, 64, 0, 64, 1, 1), (16, 4, 256, 0, 256, 1, 0), (4, 8, 64, 64, 128, 1, 0), (4, 16, 64, 64, 128, 1, 0),
             (2, 16, 128, 0, 128, 1, 1), (4, 4, 64, 0, 128, 1, 1), (2, 32, 64, 0, 256, 1, 0), (1, 64, 64, 64, 128, 1, 0),
             (2, 64, 128, 0, 128, 1, 0), (4, 16, 8, 0, 128, 1, 0), (4, 16, 128, 0, 8, 1, 0)]]
+Q_CUT = 32          # queues of "d_merged_cut_tiles": GROUP_D then has cut tiles (26 parts in slots) on any device of >= 32 CUs
 CASES = {"a_per_tap": (GROUP_A, None, None, 0), "b_merged": (GROUP_B, 0, None, 1), "c_merged_reserve32": (GROUP_B, 0, 32, 1),
          "d_merged_cut_tiles": (GROUP_D, 0, None, 1)}
 
@@ -83,6 +84,9 @@ def test_group_table_and_gradients(name, monkeypatch):
     from mdm import _lib
     members, min_share, reserve, want_form = CASES[name]
     dev = torch.device("cuda:0")
+    if name == "d_merged_cut_tiles":        # the persistent launch is planned for Q_CUT queues whatever the device's CU count
+        assert torch.cuda.get_device_properties(dev).multi_processor_count >= Q_CUT
+        reserve = torch.cuda.get_device_properties(dev).multi_processor_count - Q_CUT
     for var, val in (("MDM_TAPS_MIN_SHARE", min_share), ("MDM_WGRAD_RESERVE_CUS", reserve)):
         if val is None:
             monkeypatch.delenv(var, raising=False)
@@ -95,8 +99,8 @@ def test_group_table_and_gradients(name, monkeypatch):
     grp = _lib.WgradGroup(fields, dev)
     assert grp.table.numel() == need
     assert decode(grp.table, len(fields), len(rows), form, n_cu) == rows
-    if name == "d_merged_cut_tiles" and n_cu == 256:
-        assert any(r[7] > 0 for r in rows)
+    if name == "d_merged_cut_tiles":
+        assert n_cu == Q_CUT and any(r[7] > 0 for r in rows)
     runs = []
     for _ in range(2):
         for gw, gb, _, _, _ in outs:
