@@ -4,6 +4,7 @@ include/mdm_hip.h is the only statement of the C ABI: the two descriptor structs
 names below are parsed from it at import.  To add an entry point, declare it in the header -- nothing else.
 include/mdm_vis.h is the presentation ABI of the same library (image grids, `mdm_vis_*`): parsed the same way into
 `VIS_PROTOS` / `VIS_EXPORTS`, bound by `load()` and served by `call` and `Recording` next to the core table.
+include/mdm_data.h is the data ABI (the device-resident data set, `mdm_data_*`): `DATA_PROTOS` / `DATA_EXPORTS`, the same way.
 
 The product path has NO fallback: if the shared library or the header is missing, or a call
 returns non-zero, a RuntimeError is raised.
@@ -24,6 +25,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MDM_LIB_PATH") or os.path.join(_HERE, "libmdm_hip.so")
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "mdm_hip.h"))
 VIS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_vis.h")
+DATA_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_data.h")
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 _SCALARS = {"int": i32, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32}
@@ -73,7 +75,7 @@ def parse_header(text):
     return structs, protos
 
 
-for _path in (HEADER_PATH, VIS_HEADER_PATH):
+for _path in (HEADER_PATH, VIS_HEADER_PATH, DATA_HEADER_PATH):
     if not os.path.exists(_path):
         raise RuntimeError(
             f"{_path} is missing: it is the only statement of libmdm_hip.so's C ABI and this binding is built from it at import "
@@ -84,6 +86,10 @@ with open(VIS_HEADER_PATH) as _f:
     _VIS_STRUCTS, _VIS_DECLS = parse_header(_f.read())
 if _VIS_STRUCTS or set(_VIS_DECLS) & set(_DECLS) or not all(n.startswith("mdm_vis_") for n in _VIS_DECLS):
     raise RuntimeError(f"{VIS_HEADER_PATH}: the presentation header declares `mdm_vis_*` functions only, none of them twice")
+with open(DATA_HEADER_PATH) as _f:
+    _DATA_STRUCTS, _DATA_DECLS = parse_header(_f.read())
+if _DATA_STRUCTS or set(_DATA_DECLS) & (set(_DECLS) | set(_VIS_DECLS)) or not all(n.startswith("mdm_data_") for n in _DATA_DECLS):
+    raise RuntimeError(f"{DATA_HEADER_PATH}: the data header declares `mdm_data_*` functions only, none of them twice")
 
 _DESC_PTR = {}
 
@@ -114,6 +120,10 @@ EXPORTS = list(_PROTOS)
 VIS_PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _VIS_DECLS.items()}
 VIS_PARAMS = {name: [n for n, _ in params] for name, (_, params) in _VIS_DECLS.items()}
 VIS_EXPORTS = list(VIS_PROTOS)
+# ... and of include/mdm_data.h
+DATA_PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _DATA_DECLS.items()}
+DATA_PARAMS = {name: [n for n, _ in params] for name, (_, params) in _DATA_DECLS.items()}
+DATA_EXPORTS = list(DATA_PROTOS)
 
 _lib = None
 
@@ -128,7 +138,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C masked-diffusion-model_amd/csrc`).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in (*_PROTOS.items(), *VIS_PROTOS.items()):
+    for name, (args, res) in (*_PROTOS.items(), *VIS_PROTOS.items(), *DATA_PROTOS.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
@@ -267,7 +277,7 @@ class GraphExec:
 
 @functools.lru_cache(maxsize=None)
 def _signature(name):
-    return inspect.Signature([inspect.Parameter(p, inspect.Parameter.POSITIONAL_OR_KEYWORD) for p in (_PARAMS.get(name) or VIS_PARAMS[name])])
+    return inspect.Signature([inspect.Parameter(p, inspect.Parameter.POSITIONAL_OR_KEYWORD) for p in (_PARAMS.get(name) or VIS_PARAMS.get(name) or DATA_PARAMS[name])])
 
 
 def call(name, *args, **kw):

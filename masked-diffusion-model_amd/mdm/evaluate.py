@@ -114,13 +114,14 @@ def data_mean_histogram(dataset, args):
     dataset_hist)` takes for `sample_latent_shape='data'`.  Host arithmetic like upstream (once per run)."""
     if args.sample_latent_shape.lower() != "data":
         return [None, None, None]
-    data = _dataset_tensor(dataset).to("cpu", torch.float32)
-    if args.mean_area == "channel-wise":
-        means = data.mean(dim=[2, 3])
-    elif args.mean_area == "image-wise":
-        means = data.mean(dim=[1, 2, 3]).unsqueeze(-1)
-    else:
+    if args.mean_area not in ("channel-wise", "image-wise"):
         raise UnboundLocalError("mean_area")
+    from .data import DeviceDataset
+    if isinstance(dataset, DeviceDataset):         # the means are taken where the data is (mdm_data_means); only [M, d] comes back
+        means = dataset.means(per_channel=args.mean_area == "channel-wise").cpu()
+    else:
+        data = _dataset_tensor(dataset).to("cpu", torch.float32)
+        means = data.mean(dim=[2, 3]) if args.mean_area == "channel-wise" else data.mean(dim=[1, 2, 3]).unsqueeze(-1)
     hist, edges = torch.histogramdd(means, bins=args.sample_num, density=True)
     shape = hist.shape
     hist = torch.ravel(hist)

@@ -423,9 +423,12 @@ class Accelerator:
     is_local_main_process = is_main_process
 
     def prepare(self, *objs):
+        from .data import DeviceLoader
         from .unet import UNet
         for o in objs:                      # main_train_masked.py:299-307: model, optimizer, dataloader, lr_scheduler
-            if isinstance(o, UNet):
+            if isinstance(o, DeviceLoader):          # this rank's batches of the common order; every other loader is returned as it is
+                o.rank, o.world = self.process_index, self.num_processes
+            elif isinstance(o, UNet):
                 self._ckpt["model"] = o
             elif isinstance(o, _FlatOptimizer):      # AdamW | Adam | SGD
                 self._ckpt["optimizer"] = o

@@ -32,6 +32,7 @@ from collections import OrderedDict
 
 import torch
 
+from .data import DeviceLoader
 from .dist import GradComm
 from .sampler import Sampler
 from .scheduler import Scheduler
@@ -54,6 +55,10 @@ class Trainer:
         ema = ema_model if getattr(args, "use_ema", False) else None
         self.step = TrainStep(model, self.Scheduler, args, optimizer, ema, mean_shift=self.mean_shift, comm=comm,
                               grad_accum=getattr(accelerator, "gradient_accumulation_steps", 1))
+        if isinstance(dataloader, DeviceLoader):       # the gather writes the batch where the step reads it: `_step` passes x0=None
+            if dataloader.batch_size != model.N:
+                raise ValueError(f"DeviceLoader batch_size {dataloader.batch_size} is not the model's batch {model.N}")
+            dataloader.bind(self.step.x0)
         self.monitor = self.step.mon is not None
         self.defer_loss = bool(getattr(args, "defer_loss", False))
         if self.defer_loss and not self.monitor:
@@ -87,7 +92,8 @@ class Trainer:
             if self.Scheduler.rng_mode == "replay":
                 loss = self.step.run_replay(x0, self.timesteps_used_epoch, sync=sync)
             else:
-                loss = self.step.run_device(x0, self.timesteps_used_epoch, sync=sync)
+                # (a bound DeviceLoader yields `step.x0` itself: the batch is already there)
+                loss = self.step.run_device(None if x0 is self.step.x0 else x0, self.timesteps_used_epoch, sync=sync)
             if sync:
                 for _ in range(1 if getattr(acc, "split_batches", False) else max(1, getattr(acc, "num_processes", 1))):
                     self.lr_scheduler.step()
