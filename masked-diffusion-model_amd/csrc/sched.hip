@@ -9,7 +9,8 @@
 namespace mdm {
 
 // Philox stream ids (philox_at, common.h) so the draws of one step never overlap
-// (id 0: timesteps, 1: training mask, 2: shift, 3/4: sampler masks t / t-1; 5: the dropout masks of norm.hip, on the U-Net's own state)
+// (id 0: timesteps, 1: training mask, 2: shift, 3/4: sampler masks t / t-1; 5: the dropout masks of norm.hip, on the U-Net's own state;
+//  6: the batch-shared row mask of interp.hip, new with the interpolation sampler)
 
 __global__ void draw_timesteps_kernel(const uint64_t* rng, const int32_t* used, int n_used, const double* table,
                                       const float* wtab, int N, float* t_out, double* amount_out, float* weight_out,

@@ -5,6 +5,7 @@ names below are parsed from it at import.  To add an entry point, declare it in 
 include/mdm_vis.h is the presentation ABI of the same library (image grids, `mdm_vis_*`): parsed the same way into
 `VIS_PROTOS` / `VIS_EXPORTS`, bound by `load()` and served by `call` and `Recording` next to the core table.
 include/mdm_data.h is the data ABI (the device-resident data set, `mdm_data_*`): `DATA_PROTOS` / `DATA_EXPORTS`, the same way.
+include/mdm_interp.h is the interpolation-sampler ABI (`mdm_interp_*`): `INTERP_PROTOS` / `INTERP_EXPORTS`, the same way.
 
 The product path has NO fallback: if the shared library or the header is missing, or a call
 returns non-zero, a RuntimeError is raised.
@@ -26,6 +27,7 @@ LIB_PATH = os.environ.get("MDM_LIB_PATH") or os.path.join(_HERE, "libmdm_hip.so"
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "include", "mdm_hip.h"))
 VIS_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_vis.h")
 DATA_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_data.h")
+INTERP_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_interp.h")
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 _SCALARS = {"int": i32, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32}
@@ -75,21 +77,26 @@ def parse_header(text):
     return structs, protos
 
 
-for _path in (HEADER_PATH, VIS_HEADER_PATH, DATA_HEADER_PATH):
-    if not os.path.exists(_path):
-        raise RuntimeError(
-            f"{_path} is missing: it is the only statement of libmdm_hip.so's C ABI and this binding is built from it at import "
-            "(include/ sits next to masked-diffusion-model_amd/).  There is no fallback.")
-with open(HEADER_PATH) as _f:
-    _STRUCTS, _DECLS = parse_header(_f.read())
-with open(VIS_HEADER_PATH) as _f:
-    _VIS_STRUCTS, _VIS_DECLS = parse_header(_f.read())
-if _VIS_STRUCTS or set(_VIS_DECLS) & set(_DECLS) or not all(n.startswith("mdm_vis_") for n in _VIS_DECLS):
-    raise RuntimeError(f"{VIS_HEADER_PATH}: the presentation header declares `mdm_vis_*` functions only, none of them twice")
-with open(DATA_HEADER_PATH) as _f:
-    _DATA_STRUCTS, _DATA_DECLS = parse_header(_f.read())
-if _DATA_STRUCTS or set(_DATA_DECLS) & (set(_DECLS) | set(_VIS_DECLS)) or not all(n.startswith("mdm_data_") for n in _DATA_DECLS):
-    raise RuntimeError(f"{DATA_HEADER_PATH}: the data header declares `mdm_data_*` functions only, none of them twice")
+def _read_headers(core, extra):
+    """Parse the core header, then every `(path, prefix)` of `extra`: such a header declares functions named `prefix*` only -- no
+    struct, no name that a header before it declares.  -> (core structs, core prototypes, [prototypes of each extra header])."""
+    parsed = []
+    for path, prefix in ((core, None), *extra):
+        if not os.path.exists(path):
+            raise RuntimeError(
+                f"{path} is missing: it is the only statement of libmdm_hip.so's C ABI and this binding is built from it at import "
+                "(include/ sits next to masked-diffusion-model_amd/).  There is no fallback.")
+        with open(path) as f:
+            structs, decls = parse_header(f.read())
+        seen = set().union(*(d for _, d in parsed))
+        if prefix is not None and (structs or set(decls) & seen or not all(n.startswith(prefix) for n in decls)):
+            raise RuntimeError(f"{path}: this header declares `{prefix}*` functions only, none of them twice")
+        parsed.append((structs, decls))
+    return parsed[0][0], parsed[0][1], [d for _, d in parsed[1:]]
+
+
+_STRUCTS, _DECLS, (_VIS_DECLS, _DATA_DECLS, _INTERP_DECLS) = _read_headers(
+    HEADER_PATH, ((VIS_HEADER_PATH, "mdm_vis_"), (DATA_HEADER_PATH, "mdm_data_"), (INTERP_HEADER_PATH, "mdm_interp_")))
 
 _DESC_PTR = {}
 
@@ -112,18 +119,21 @@ class GnDesc(C.Structure):
 
 
 _DESC_PTR.update({"mdm_gemm_desc*": C.POINTER(GemmDesc), "mdm_gn_desc*": C.POINTER(GnDesc)})
-# every function the header declares: {name: (argtypes, restype)} and {name: parameter names}
-_PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _DECLS.items()}
-_PARAMS = {name: [n for n, _ in params] for name, (_, params) in _DECLS.items()}
-EXPORTS = list(_PROTOS)
-# the same two tables of include/mdm_vis.h, kept apart: the core tables are exactly what mdm_hip.h declares
-VIS_PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _VIS_DECLS.items()}
-VIS_PARAMS = {name: [n for n, _ in params] for name, (_, params) in _VIS_DECLS.items()}
-VIS_EXPORTS = list(VIS_PROTOS)
-# ... and of include/mdm_data.h
-DATA_PROTOS = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in _DATA_DECLS.items()}
-DATA_PARAMS = {name: [n for n, _ in params] for name, (_, params) in _DATA_DECLS.items()}
-DATA_EXPORTS = list(DATA_PROTOS)
+def _tables(decls):
+    """{name: (argtypes, restype)}, {name: parameter names} and the names, in the header's order."""
+    protos = {name: ([_ctype(t) for _, t in params], _ctype(rtype, ret=True)) for name, (rtype, params) in decls.items()}
+    return protos, {name: [n for n, _ in params] for name, (_, params) in decls.items()}, list(protos)
+
+
+# every function the core header declares ...
+_PROTOS, _PARAMS, EXPORTS = _tables(_DECLS)
+# ... and the same three tables of include/mdm_vis.h, mdm_data.h and mdm_interp.h, kept apart: the core tables are exactly what
+# mdm_hip.h declares
+VIS_PROTOS, VIS_PARAMS, VIS_EXPORTS = _tables(_VIS_DECLS)
+DATA_PROTOS, DATA_PARAMS, DATA_EXPORTS = _tables(_DATA_DECLS)
+INTERP_PROTOS, INTERP_PARAMS, INTERP_EXPORTS = _tables(_INTERP_DECLS)
+_ALL_PROTOS = {**_PROTOS, **VIS_PROTOS, **DATA_PROTOS, **INTERP_PROTOS}
+_ALL_PARAMS = {**_PARAMS, **VIS_PARAMS, **DATA_PARAMS, **INTERP_PARAMS}
 
 _lib = None
 
@@ -138,7 +148,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C masked-diffusion-model_amd/csrc`).  There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (args, res) in (*_PROTOS.items(), *VIS_PROTOS.items(), *DATA_PROTOS.items()):
+    for name, (args, res) in _ALL_PROTOS.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res
@@ -277,7 +287,7 @@ class GraphExec:
 
 @functools.lru_cache(maxsize=None)
 def _signature(name):
-    return inspect.Signature([inspect.Parameter(p, inspect.Parameter.POSITIONAL_OR_KEYWORD) for p in (_PARAMS.get(name) or VIS_PARAMS.get(name) or DATA_PARAMS[name])])
+    return inspect.Signature([inspect.Parameter(p, inspect.Parameter.POSITIONAL_OR_KEYWORD) for p in _ALL_PARAMS[name]])
 
 
 def call(name, *args, **kw):

@@ -1,6 +1,8 @@
 """Reverse (cold-diffusion) sampler on the GPU -- same surface as the reference `Sampler`.
 
-Mirrors reference code/sampler.py: `_get_latent_initial` (:46-83), `sample` (:102-106) and
+Mirrors reference code/sampler.py: `_get_latent_initial` (:46-83), `sample` (:102-106),
+`_get_latent_initial_interpolation` (:86-99) with `_sample_interpolation` (:264-366, public here as
+`sample_interpolation`: nothing calls it upstream) and
 `_sample_mean_shift_momentum` (:109-261) for the options that run upstream at HEAD
 (`sampling_mask_dependency` in {independent, dependent_prev, dependent_t -- the last for
 'thresholding' with mean_option 'degraded_area' or "0", scheduler.py:480-549}, `momentum_adaptive`
@@ -27,6 +29,8 @@ from ._lib import call, ptr, stream
 
 HISTORY_NAMES = ["sample_t", "shift", "shifted", "mask", "shifted_result", "sample_0",
                  "degraded_mask", "degraded_mask_next", "degraded_t", "difference", "degraded_next_t"]
+# the ten lists of the interpolation sampler (sampler.py:366): one mask per step, shared by the batch
+INTERP_HISTORY_NAMES = [k for k in HISTORY_NAMES if k != "degraded_mask_next"]
 
 
 def shard_bounds(n, rank, world):
@@ -130,6 +134,151 @@ class Sampler:
             g = gather_shards(h.to(x0.device).transpose(0, 1).contiguous(), n).transpose(0, 1)
             return g if h.is_cuda else g.cpu()
         return gather_shards(x0, n), [gather_hist(h) for h in hist]
+
+    # ---- latent interpolation (sampler.py:86-99, 264-366) ------------------------------------------------------
+    def _get_latent_initial_interpolation(self, interpolation_shift):
+        """sampler.py:86-99 -> (latent [N, C, H, W], grid [N, 1, 1, 1]) on the host: a ramp of constant start colours whose ends
+        leave room for the shift -- linspace(-1, 1 - shift) for a positive shift, linspace(-1 - shift, 1) for a negative one."""
+        a = self.args
+        if interpolation_shift > 0:
+            grid = torch.linspace(-1, 1 - interpolation_shift, a.sample_num)
+        elif interpolation_shift < 0:
+            grid = torch.linspace(-1 - interpolation_shift, 1, a.sample_num)
+        else:
+            grid = torch.linspace(-1, 1, a.sample_num)
+        grid = grid[:, None, None, None]
+        return torch.zeros(a.sample_num, a.out_channel, a.data_size, a.data_size) + grid, grid
+
+    def sample_interpolation(self, model, timesteps_used_epoch, interpolation_shift):
+        """The latent-interpolation sampler (upstream's `_sample_interpolation`, which nothing calls there): -> (sample_0, mu,
+        history lists in INTERP_HISTORY_NAMES order).  With a process group every rank runs its rows of the ramp (`model` built
+        for `local_sample_num()`), the ramp and the host draws are made for the full batch on every rank, and the shards are
+        all-gathered once at the end: every rank returns what one process computes; `mu` is the full grid."""
+        rank, world = self._shard()
+        if world == 1:
+            return self._sample_interpolation(model, timesteps_used_epoch, interpolation_shift)
+        n = self.args.sample_num
+        lo, hi = shard_bounds(n, rank, world)
+        if hi == lo:
+            raise ValueError(f"sample_num={n} < world size {world}: a rank would sample nothing")
+        x0, mu, hist = self._sample_interpolation(model, timesteps_used_epoch, interpolation_shift, rows=(lo, hi))
+        def gather_hist(h):             # [T+1, n_local, C, H, W], on the host when args.sample_history is True
+            g = gather_shards(h.to(x0.device).transpose(0, 1).contiguous(), n).transpose(0, 1)
+            return g if h.is_cuda else g.cpu()
+        return gather_shards(x0, n), mu, [gather_hist(h) for h in hist]
+
+    def _emit_interp_step(self, b, more, params, forward):
+        """One reverse step of the interpolation loop (sampler.py:297-361) over the fixed buffers `b`, launched or recorded: the
+        clamped shift, the forward, x0 reconstruction and -- with `more`, every step but the last -- the fill through the mask of
+        the step before, the new batch-shared row mask, the fill through it and the momentum write.  `params()` fills b.time /
+        ratio / amt_next and bumps the Philox offset, `forward()` runs the net on b.x_in -> (pred NHWC, Cp, dtype), `b.draw_row()`
+        is the row's random input in the scheduler's RNG mode."""
+        a, S = self.args, self.Scheduler
+        n, c, h, w = b.x_t.shape
+        params()
+        S.emit_shift_interp(b.x_t, b.mu, b.ratio, b.shift, b.s, b.x_in, nhwc=b.nhwc)                                     # :302-303
+        pred, cp, pdt = forward()                                                                                      # :305
+        call("mdm_sampler_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), N=n, C=c, H=h, W=w,
+             pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0), x0_hat=ptr(b.x0_hat), stream=stream())              # :306-307
+        if not more:
+            return
+        S.emit_degrade(b.x0_hat, b.d_t, b.mp, rng_stream=0, mean_option=a.mean_option, mean_area=a.mean_area, mask_in=b.m_next)   # :321
+        mo, ma = S._interp_fill(a.mean_option)
+        S.emit_row_mask(b.amt_next, b.m_next, u_row=b.draw_row())                                                      # :323
+        S.emit_degrade(b.x0_hat, b.d_next, b.mp, rng_stream=0, mean_option=mo, mean_area=ma, mask_in=b.m_next)
+        call("mdm_interp_update", d_t=ptr(b.d_t), d_next=ptr(b.d_next), x_t=ptr(b.x_t), diff=ptr(b.diff),
+             update=int(a.momentum_adaptive == "base_momentum"), n=b.x_t.numel(), stream=stream())                     # :326-333
+
+    def _sample_interpolation_graph(self, model, timesteps, b):
+        """The host-driven loop of `_sample_interpolation` (history off, device RNG) with ONE hipGraph per reverse step, like
+        `_sample_graph`: a body graph replayed T - 1 times and a last graph (shift, forward, x0) once; the per-step scalars come
+        from `mdm_sampler_step_params`."""
+        S = self.Scheduler
+        dev, T, n = S.device, len(timesteps), b.x_t.shape[0]
+        amount_tab = (S.pixels_dev if b.indexing else S.ratio_dev).to(dev, torch.float64).contiguous()
+        ratio_tab = S.ratio_dev.to(dev, torch.float64).contiguous()
+        ts_dev = torch.as_tensor([int(t) for t in timesteps], dtype=torch.int32, device=dev)
+        ctr = torch.zeros(1, dtype=torch.int32, device=dev)
+        amt_t = torch.empty(n, dtype=torch.float64, device=dev)       # the amount at t: the entry point writes it, this loop reads t - 1 only
+
+        def params():
+            call("mdm_sampler_step_params", timesteps=ptr(ts_dev), T=T, step_ctr=ptr(ctr), ratio_tab=ptr(ratio_tab),
+                 amount_tab=ptr(amount_tab), n=n, time_out=ptr(b.time), ratio_out=ptr(b.ratio), amt_t=ptr(amt_t),
+                 amt_next=ptr(b.amt_next), rng=ptr(S.dev_rng.dev), stream=stream())
+
+        def forward():
+            _lib._recording.extend(model.forward_plan)
+            return model.y_out.data, model.cout_p, model.dt
+
+        graphs = []
+        for more in ((True, False) if T > 1 else (False,)):
+            with _lib.Recording() as rec:
+                self._emit_interp_step(b, more, params, forward)
+            graphs.append(_lib.GraphExec(rec))
+        for _ in range(T - 1):
+            graphs[0].launch()
+        graphs[-1].launch()
+        self._graph_keep = ((b, ts_dev, ctr, amount_tab, ratio_tab, amt_t), graphs)
+        return b.x0_hat
+
+    def _sample_interpolation(self, model, timesteps, interpolation_shift, rows=None):
+        """sampler.py:264-366.  `rows = (lo, hi)`: compute rows [lo, hi) of the batch only (a shard of `sample_interpolation`):
+        the ramp and every host draw are made for the full batch and sliced, `model` is built for hi - lo samples, the returned
+        `mu` stays the full grid."""
+        from .unet import UNet
+        a, S = self.args, self.Scheduler
+        dev, T = S.device, len(timesteps)
+        n_full, c, hw = a.sample_num, a.out_channel, a.data_size
+        lo, hi = rows if rows is not None else (0, n_full)
+        n = hi - lo
+        mode = a.momentum_adaptive
+        if mode in ("momentum", "boosting"):     # :341, 352 read `momentum` before anything binds it
+            raise UnboundLocalError(f"momentum_adaptive={mode!r} does not run upstream (D4)")
+        hist_mode = getattr(a, "sample_history", True)
+        fused = isinstance(model, UNet)
+        if fused and getattr(a, "sampler_uniform_t", True):
+            model = model.with_uniform_t()      # every reverse step passes ONE timestep for the whole batch (sampler.py:298-305)
+        if fused:
+            assert (model.N, model.H, model.W) == (n, hw, hw), "UNet plan was built for another batch/extent"
+        latent, mu = self._get_latent_initial_interpolation(interpolation_shift)
+        x_t = latent[lo:hi].to(dev, torch.float32).contiguous()
+        if S.rng_mode == "replay" and a.sampling_mask_dependency == "dependent":
+            for _ in range(n_full):             # :295: drawn for every sample of the batch, never read
+                torch.randperm(hw * hw)
+        graph = (fused and not hist_mode and S.rng_mode == "device" and model.use_graph and getattr(a, "sampler_graph", True)
+                 and self.step_hook is None)
+        img = lambda on=True: torch.empty_like(x_t) if on else None
+        b = types.SimpleNamespace(
+            x_t=x_t, mu=mu[lo:hi].reshape(n).to(dev, torch.float32).contiguous(), shift=float(interpolation_shift),
+            indexing=a.select_degrade_pixel == "indexing", nhwc=(model.dt, model.x_in.data, model.cin_p) if fused else None,
+            time=model.t_in if graph else torch.empty(n, device=dev), ratio=torch.empty(n, dtype=torch.float64, device=dev),
+            amt_next=torch.empty(n, dtype=torch.float64, device=dev), s=img(), x_in=img(), pred_nchw=img(hist_mode),
+            shifted0=img(hist_mode), x0_hat=img(), d_t=img(), d_next=img(), m_next=torch.zeros_like(x_t),
+            mp=torch.empty(n, c, device=dev), diff=img())
+        b.draw_row = (lambda: S.host_uniform_row(hw * hw)) if S.rng_mode == "replay" else (lambda: None)
+        if graph:
+            return self._sample_interpolation_graph(model, timesteps, b), mu, []
+        hist = {k: torch.zeros(T + 1, n, c, hw, hw, device=dev) for k in INTERP_HISTORY_NAMES} if hist_mode else None
+
+        def params(i):                          # what mdm_sampler_step_params does for the graph loop
+            S.dev_rng.advance()
+            b.time.fill_(float(timesteps[i]))
+            torch.index_select(S.ratio_dev, 0, b.time.int() - 1, out=b.ratio)
+            if i > 0:
+                b.amt_next.copy_(S.get_black_area_num_pixels_time(b.time - 1))          # :317-319
+        for i in range(T - 1, -1, -1):
+            slot = T - i
+            if self.step_hook is not None:
+                self.step_hook(i, slot, x_t)
+            self._emit_interp_step(b, i > 0, functools.partial(params, i), lambda: self._predict(model, b.x_in, b.time, fused))
+            if hist_mode:
+                hist["shift"][slot].copy_(b.s); hist["shifted"][slot].copy_(b.x_in); hist["mask"][slot].copy_(b.pred_nchw)
+                hist["shifted_result"][slot].copy_(b.shifted0); hist["sample_0"][slot].copy_(b.x0_hat)
+                if i > 0:                       # :357-361: sample_t is the UPDATED x_t, degraded_mask the row mask just drawn
+                    hist["degraded_next_t"][slot].copy_(b.d_next); hist["degraded_t"][slot].copy_(b.d_t)
+                    hist["difference"][slot].copy_(b.diff); hist["sample_t"][slot].copy_(x_t)
+                    hist["degraded_mask"][slot].copy_(b.m_next)
+        return b.x0_hat, mu, [hist[k] if hist_mode == "device" else hist[k].cpu() for k in INTERP_HISTORY_NAMES] if hist_mode else []
 
     # ---- image grids (mdm/visuals.py: one range launch + one grid launch each, built on the device) ---------
     def _batch(self, sample):

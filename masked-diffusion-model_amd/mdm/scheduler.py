@@ -356,6 +356,65 @@ class Scheduler:
         s, _ = self.shift_and_perturb(timesteps, zero)
         return s.to(getattr(self.args, "weight_dtype", torch.float32))
 
+    # ---- latent interpolation (scheduler.py:552-569, 735-754) ---------------------------
+    def emit_shift_interp(self, x_t, mu, ratio, interpolation_shift, s, x_in, *, nhwc=None):
+        """The one place that launches (or records) mdm_interp_shift over the caller's contiguous device tensors: per sample
+        s = clamp(float32(shift * ratio), -mu - ratio, -mu + ratio) in the reference's arithmetic (`mu` [N] fp32, `ratio` [N]
+        fp64), x_in = x_t + s, optionally x_in once more as NHWC into `nhwc = (dtype, tensor, Cp)`.  `s` / `x_in` may be None.
+        Nothing is drawn, allocated, converted or read back."""
+        N, C, H, W = x_t.shape
+        dt, nh, Cp = nhwc if nhwc is not None else (0, None, 0)
+        call("mdm_interp_shift", x_t=ptr(x_t), mu=ptr(mu), ratio=ptr(ratio), shift=float(interpolation_shift), N=N, C=C, H=H, W=W,
+             s=ptr(s), x_in=ptr(x_in), dtype=dt, x_in_nhwc=ptr(nh), Cp=Cp, stream=stream())
+
+    def host_uniform_row(self, HW):
+        """The ONE row of uniforms degrade_interpolation_sampling draws for the whole batch (scheduler.py:553) -> [HW] on the
+        device.  The same on every shard of a batch: all ranks are seeded alike and the row does not depend on the batch."""
+        return torch.empty(1, HW, dtype=torch.float32).uniform_(0.0, 1.0).reshape(HW).to(self.device)
+
+    def emit_row_mask(self, amount, mask, *, u_row=None):
+        """The one place that launches (or records) mdm_interp_row_mask: mask[n, c, p] = float64(u[p]) > amount[n] into the
+        caller's `mask` [N, C, H, W] (`amount` [N] fp64).  `u_row` [HW]: the replayed host draw; None: the kernel draws the row
+        (Philox stream 6, the key without its rank half -- the shards of one batch draw the same row)."""
+        N, C, HW = mask.shape[0], mask.shape[1], mask[0, 0].numel()
+        call("mdm_interp_row_mask", amount=ptr(amount), u_row=ptr(u_row), rng=ptr(self.dev_rng.dev), N=N, C=C, HW=HW,
+             mask=ptr(mask), stream=stream())
+
+    @staticmethod
+    def _interp_fill(mean_option):
+        """(mean_option, mean_area) of the masked fill degrade_interpolation_sampling makes (scheduler.py:559-563): float(mean_option)
+        when that works, for ANY string the image-wise mean of the degraded area -- the option's name and mean_area are not looked
+        at -- and for None the TypeError float() raises."""
+        try:
+            return float(mean_option), "image-wise"
+        except ValueError:
+            return "degraded_area", "image-wise"
+
+    def get_schedule_shift_time_interpolation(self, timesteps, mu, interpolation_shift):
+        """scheduler.py:735-754 -> [N, 1, 1, 1] in weight_dtype: the constant shift scaled by the ratio of each timestep and
+        clamped to [-mu - ratio, -mu + ratio] per sample."""
+        idx = (timesteps.int() - 1).to(self.device)
+        N = idx.numel()
+        ratio = torch.index_select(self.ratio_dev, 0, idx).contiguous()
+        mu = torch.as_tensor(mu).to(self.device, torch.float32).reshape(N).contiguous()
+        s = torch.empty(N, 1, 1, 1, device=self.device)
+        self.emit_shift_interp(torch.zeros_like(s), mu, ratio, interpolation_shift, s, None)
+        return s.to(getattr(self.args, "weight_dtype", torch.float32))
+
+    def degrade_interpolation_sampling(self, black_area_num_t, img, mean_option=None, mean_area=None):
+        """scheduler.py:552-569: ONE uniform row for the whole batch, thresholded at each sample's amount -> (degraded, mask,
+        fill * ones).  Pixel counts ('indexing') are compared like ratios, as upstream does: every count is >= 1 > u, so that
+        mask is all zero."""
+        img = img.to(self.device, torch.float32).contiguous()
+        N, C, H, W = img.shape
+        amount = torch.as_tensor(black_area_num_t).to(self.device, torch.float64).reshape(N).contiguous()
+        u_row = self.host_uniform_row(H * W) if self.rng_mode == "replay" else None
+        mo, ma = self._interp_fill(mean_option)
+        mask, x_t, mp = torch.empty_like(img), torch.empty_like(img), torch.empty(N, C, device=self.device)
+        self.emit_row_mask(amount, mask, u_row=u_row)
+        self.emit_degrade(img, x_t, mp, rng_stream=0, mean_option=mo, mean_area=ma, mask_in=mask)
+        return x_t, mask, mp[:, :, None, None] * torch.ones_like(x_t)
+
     def perturb_shift(self, data, shift):
         return data + shift.to(data.device)
 
