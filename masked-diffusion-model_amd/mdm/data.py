@@ -77,6 +77,20 @@ class DeviceDataset:
             label[i] = float(item[1])
         return cls(data, label, random, device=device, **kw)
 
+    @classmethod
+    def from_folder(cls, root, size, *, num_data=None, num_timesteps=1, device=None, **kw):
+        """An `ImageFolder(root)` of image files under upstream's transform (`Resize(size)`, `CenterCrop(size)`, `ToTensor()`,
+        `Normalize([0.5], [0.5])`), materialised as `MyDataset.__init__` does: see mdm/ingest.py.  The files are decoded on host
+        threads and resized and cropped on the device, byte for byte as PIL does; labels are the sorted class folders' indices;
+        `num_data` keeps the first items and decodes only those."""
+        from . import ingest
+        samples = ingest.image_folder(root)[2]
+        if num_data is not None:
+            if not 0 < int(num_data) <= len(samples):
+                raise ValueError(f"DeviceDataset.from_folder: num_data = {num_data} of {len(samples)} items")
+            samples = samples[:int(num_data)]
+        return ingest.dataset_from_samples(samples, size, num_timesteps=num_timesteps, device=device, **kw)
+
     def __len__(self):
         return self.M
 
