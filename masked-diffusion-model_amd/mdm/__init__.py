@@ -3,7 +3,7 @@
 Host side (Python on PyTorch-ROCm for device memory / streams / torch.distributed)
 over libmdm_hip.so (hand-written HIP kernels for gfx950, C ABI in include/mdm_hip.h, image grids in
 include/mdm_vis.h, the device-resident data set in include/mdm_data.h, image-folder ingest in
-include/mdm_ingest.h).
+include/mdm_ingest.h, nearest-neighbour search in include/mdm_neighbor.h).
 Keeps the reference's call surface: Scheduler(args), Sampler(dataset, args, Scheduler,
 dataset_hist).sample(model, timesteps), Trainer(...).train(...), model(x, t).sample.
 """
@@ -14,6 +14,7 @@ from . import visuals  # noqa: F401
 from ._lib import BF16, F32  # noqa: F401
 from .data import DeviceDataset, DeviceLoader  # noqa: F401
 from .dist import GradComm  # noqa: F401
+from .evaluate import NeighborBank, get_nearest_neighbor, get_nearest_neighbor_idx, get_similar_neighbor  # noqa: F401
 from .ingest import get_dataset, image_folder, resize_crop_plan  # noqa: F401
 from .optim import EMA, SGD, Accelerator, Adam, AdamW, get_lr_scheduler, get_optimizer  # noqa: F401
 from .sampler import Sampler  # noqa: F401

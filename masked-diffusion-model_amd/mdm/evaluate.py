@@ -9,9 +9,14 @@ The reference compares images one pair at a time in Python loops (B x M cosine s
 and host sync).  Here every comparison of a batch is ONE fp32 contraction on the GPU -- unit-length rows (mdm_unit_rows)
 times unit-length rows (mdm_gemm, exact-fp32 MFMA) -- and the greedy keep/drop decisions, which depend on the order of the
 images, walk the resulting matrix on the host in the reference's order.  Image grids / plots are out of scope.
+
+`NeighborBank` serves every nearest-neighbour call (include/mdm_neighbor.h): the data set's unit-length feature rows -- 32 x 32 after
+normalize01 for `Sampler.get_nearest_neighbor`, full resolution for `Tester` -- are built by `mdm_nn_rows` straight from the
+`DeviceDataset` storage, uint8 or fp32 as stored, and searched chunk by chunk by `mdm_nn_col_argmax`.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -73,19 +78,223 @@ def _dataset_tensor(dataset):
     return torch.stack([dataset[i][0] for i in range(len(dataset))])
 
 
+def nn_plan(n_in, n_out, antialias):
+    """(first [n_out] int32, count [n_out] int32, weight [n_out][taps] float32, taps): the one-axis tap table of
+    `F.interpolate(mode="bilinear", align_corners=False, antialias=antialias)` as `mdm_nn_plan` states it (host arrays)."""
+    lib = _lib.load()
+    taps = lib.mdm_nn_plan(int(n_in), int(n_out), int(bool(antialias)), None, None, None, 0)
+    if taps < 1:
+        _lib.check(taps, "mdm_nn_plan")
+    first, count = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    weight = np.zeros((n_out, taps), np.float32)
+    got = lib.mdm_nn_plan(int(n_in), int(n_out), int(bool(antialias)), first.ctypes.data, count.ctypes.data, weight.ctypes.data, taps)
+    if got != taps:
+        _lib.check(-1, "mdm_nn_plan")
+    return first, count, weight, taps
+
+
+def neighbor_flip_rows(M, B):
+    """The draws of upstream's `RandomHorizontalFlip()` over a `DataLoader(dataset, batch_size=B, shuffle=False)` pass
+    (sampler.py:491-492, 504): the transform sees each batch as ONE tensor, so it is one `torch.rand(1) < 0.5` from the default host
+    generator per batch, in data order.  -> uint8 [M] on the host: 1 on the rows of the batches that flip."""
+    rows = torch.zeros(int(M), dtype=torch.uint8)
+    for i in range(0, int(M), int(B)):
+        if bool(torch.rand(1) < 0.5):
+            rows[i:i + int(B)] = 1
+    return rows
+
+
+def _as_device_dataset(dataset):
+    """`dataset` as a `DeviceDataset` on the GPU; a tensor or a map-style set is uploaded once (no draw from a host generator)."""
+    from .data import DeviceDataset
+    if isinstance(dataset, DeviceDataset):
+        if dataset.data.device.type != "cuda":
+            raise TypeError(f"NeighborBank: the data set is on {dataset.data.device}, the kernels of mdm_neighbor.h need it on a GPU")
+        return dataset
+    data = _dataset_tensor(dataset)
+    if data.dtype != torch.uint8:
+        data = data.to(torch.float32)
+    return DeviceDataset(data, random=torch.zeros(data.shape[0], 1), device=_dev())
+
+
+class NeighborBank:
+    """The unit-length feature rows of a data set, and every nearest-neighbour query against them.
+
+    `dataset`: a `DeviceDataset`, a tensor [M, C, H, W] or a map-style set (the last two are uploaded once).  A row is the image
+    `normalize01`-ed (`normalize`), resized to `size` x `size` by the tap tables of `F.interpolate(mode="bilinear", antialias=...)`
+    -- torchvision's tensor `Resize` -- or kept at full resolution (`size=None`, `Tester`'s comparison), and divided by its norm:
+    one `mdm_nn_rows` launch per `chunk` images, reading the storage as it is (uint8 through the data set's table).  The rows stay
+    for later queries when M x row_ld x 4 <= `cache_bytes`; otherwise every query rebuilds them chunk by chunk and one chunk of rows
+    is all that is ever live.  Source images go through the same kernel (kind 0, not normalised, as upstream leaves them); a
+    similarity is `ops.matmul` per chunk, the search `mdm_nn_col_argmax` with carry."""
+
+    EPS = 1e-8            # torch.nn.functional.cosine_similarity's
+
+    def __init__(self, dataset, size=32, antialias=True, normalize=True, chunk=4096, cache_bytes=1 << 30):
+        self.dataset = d = _as_device_dataset(dataset)
+        self.size, self.antialias, self.normalize = (None if size is None else int(size)), bool(antialias), bool(normalize)
+        if self.size is not None and self.size < 1:
+            raise ValueError(f"NeighborBank: size={size}")
+        self.chunk = max(1, min(int(chunk), d.M))
+        self.D = d.C * (self.size ** 2 if self.size else d.H * d.W)
+        self.row_ld = (self.D + 3) // 4 * 4
+        self._tables = {}
+        self.cached = d.M * self.row_ld * 4 <= int(cache_bytes)
+        self.rows = None
+        if self.cached:
+            self.rows = torch.empty(d.M, self.row_ld, dtype=torch.float32, device=d.device)
+            for first in range(0, d.M, self.chunk):
+                self._data_rows(first, min(self.chunk, d.M - first), self.rows[first:])
+        else:
+            self._chunk_rows = torch.empty(self.chunk, self.row_ld, dtype=torch.float32, device=d.device)
+
+    def _axis(self, n_in):
+        """the device copy of the tap table n_in -> size: (first, count, weight, taps)"""
+        if n_in not in self._tables:
+            first, count, weight, taps = nn_plan(n_in, self.size, self.antialias)
+            dev = self.dataset.device
+            self._tables[n_in] = (torch.from_numpy(first).to(dev), torch.from_numpy(count).to(dev), torch.from_numpy(weight).to(dev), taps)
+        return self._tables[n_in]
+
+    def _launch(self, src, kind, img_stride, M, C, H, W, lut, first, R, normalize, flip, out):
+        S = self.size or 0
+        (hf, hc, hw, ht), (vf, vc, vw, vt) = (self._axis(W), self._axis(H)) if S else ((None, None, None, 0),) * 2
+        call("mdm_nn_rows", src=ptr(src), kind=kind, img_stride=img_stride, M=M, C=C, H=H, W=W, lut=ptr(lut), first=int(first), R=int(R),
+             normalize=int(normalize), flip=int(flip), S=S, hfirst=ptr(hf), hcount=ptr(hc), hweight=ptr(hw), htaps=ht,
+             vfirst=ptr(vf), vcount=ptr(vc), vweight=ptr(vw), vtaps=vt, eps=self.EPS, rows=ptr(out), row_ld=self.row_ld, stream=stream())
+
+    def _data_rows(self, first, R, out):
+        d = self.dataset
+        self._launch(d.data, d.kind, d.img_stride, d.M, d.C, d.H, d.W, d.lut, first, R, self.normalize, False, out)
+
+    def _chunks(self):
+        """(first, R, rows of the images [first, first + R)) over the set: slices of the kept rows, or the one chunk buffer rebuilt"""
+        d = self.dataset
+        for first in range(0, d.M, self.chunk):
+            R = min(self.chunk, d.M - first)
+            if self.cached:
+                yield first, R, self.rows[first:first + R]
+            else:
+                self._data_rows(first, R, self._chunk_rows)
+                yield first, R, self._chunk_rows
+
+    def source_rows(self, source, flip=False):
+        """-> (rows [Bp][row_ld] with Bp = B padded to a multiple of 4 by zero rows, B): the unit rows of the source images, as
+        they are (upstream does not normalise the source), mirrored along W with `flip`"""
+        d = self.dataset
+        src = source.to(d.device, torch.float32).contiguous()
+        if src.dim() != 4 or src.shape[1] != d.C or (not self.size and tuple(src.shape[2:]) != (d.H, d.W)):
+            raise ValueError(f"NeighborBank: source {tuple(source.shape)} does not match the data set's images {(d.C, d.H, d.W)}")
+        B, C, H, W = (int(v) for v in src.shape)
+        out = torch.zeros((B + 3) // 4 * 4, self.row_ld, dtype=torch.float32, device=d.device)
+        self._launch(src, 0, C * H * W, B, C, H, W, None, 0, B, False, flip, out)
+        return out, B
+
+    def similarity(self, source, flip=False):
+        """S [M][B], S[m][b] = cos(row of data image m, row of source[b]) (`_compute_similarity`, sampler.py:521-526); `flip`: against
+        the mirrored source -- the similarity with the mirrored data up to rounding, the tables being symmetric"""
+        d = self.dataset
+        b, B = self.source_rows(source, flip)
+        Bp = b.shape[0]
+        S = torch.empty(d.M, Bp, dtype=torch.float32, device=d.device)
+        for first, R, rows in self._chunks():
+            ops.matmul(F32, 0, R, Bp, self.row_ld, rows, self.row_ld, b, self.row_ld, S[first:], Bp)
+        return S[:, :B]
+
+    def nearest_idx(self, source, augment_rows=None, with_val=False):
+        """int64 [B] on the device: the data image with the largest similarity to each source image, `score.max(dim=0)` of
+        sampler.py:512.  `augment_rows` (uint8 [M], see `neighbor_flip_rows`): the rows whose score is the larger of the similarity
+        and the similarity with the mirrored image (sampler.py:503-508)."""
+        d = self.dataset
+        b, B = self.source_rows(source)
+        Bp = b.shape[0]
+        aug = b_aug = S_aug = None
+        if augment_rows is not None:
+            aug = torch.as_tensor(augment_rows).to(torch.uint8).reshape(-1).to(d.device)
+            if aug.numel() != d.M:
+                raise ValueError(f"NeighborBank: augment_rows has {aug.numel()} entries for {d.M} images")
+            b_aug = self.source_rows(source, flip=True)[0]
+            S_aug = torch.empty(self.chunk, Bp, dtype=torch.float32, device=d.device)
+        S = torch.empty(self.chunk, Bp, dtype=torch.float32, device=d.device)
+        val = torch.empty(B, dtype=torch.float32, device=d.device)
+        idx = torch.empty(B, dtype=torch.int64, device=d.device)
+        for first, R, rows in self._chunks():
+            ops.matmul(F32, 0, R, Bp, self.row_ld, rows, self.row_ld, b, self.row_ld, S, Bp)
+            if aug is not None:
+                ops.matmul(F32, 0, R, Bp, self.row_ld, rows, self.row_ld, b_aug, self.row_ld, S_aug, Bp)
+            call("mdm_nn_col_argmax", S=ptr(S), S_aug=ptr(S_aug), row_aug=None if aug is None else aug.data_ptr() + first, M=R, B=B,
+                 ld=Bp, row0=first, carry=int(first > 0), val=ptr(val), idx=ptr(idx), stream=stream())
+        return (val, idx) if with_val else idx
+
+    def nearest(self, source, augment_rows=None):
+        """fp32 [B, C, H, W] on the device: the stored (un-normalised) nearest data images, one `mdm_data_gather`"""
+        d = self.dataset
+        idx = self.nearest_idx(source, augment_rows)
+        out = torch.empty(idx.numel(), d.C, d.H, d.W, dtype=torch.float32, device=d.device)
+        d.gather(idx, 0, idx.numel(), out)
+        return out
+
+
+def _full_bank(dataset):
+    """the full-resolution bank of a `DeviceDataset` on a GPU, made once and kept on the data set object; None for anything else"""
+    from .data import DeviceDataset
+    if not isinstance(dataset, DeviceDataset) or dataset.data.device.type != "cuda":
+        return None
+    bank = getattr(dataset, "_nn_bank_full", None)
+    if bank is None:
+        bank = dataset._nn_bank_full = NeighborBank(dataset, size=None)
+    return bank
+
+
 def get_nearest_neighbor_idx(source, dataset):
     """Index of the data image with the largest cosine similarity to each source image; data images are
-    normalize01-ed first (tester.py:186-201)."""
+    normalize01-ed first (tester.py:186-201).  A `DeviceDataset` on a GPU is searched through its full-resolution `NeighborBank`,
+    made once and kept on the data set: nothing of the set is copied per call."""
+    bank = _full_bank(dataset)
+    if bank is not None:
+        return bank.nearest_idx(source)
     data = normalize01(_dataset_tensor(dataset))
     return col_argmax(cosine_similarity_matrix(source, data))[1]
 
 
 def get_nearest_neighbor(source, dataset):
-    """The nearest data image (un-normalised, as stored) for every source image (sampler.py:487-518, augment=False;
-    the reference resizes both sides to 32x32 first -- a no-op at data_size 32, the benchmark shape)."""
+    """The nearest data image (un-normalised, as stored) for every source image, compared at full resolution as
+    `get_nearest_neighbor_idx` compares.  (Upstream's `Sampler.get_nearest_neighbor`, which compares 32 x 32 resizes, is
+    `mdm.Sampler.get_nearest_neighbor`.)"""
+    bank = _full_bank(dataset)
+    if bank is not None:
+        return bank.nearest(source).to(source.device)
     data = _dataset_tensor(dataset)
     idx = get_nearest_neighbor_idx(source, data)
     return data.to(source.device)[idx.to(source.device)]
+
+
+def get_similar_neighbor(generated, img_set, idx, th=COSINE_TH):
+    """tester.py:209-223: generated image i joins `img_set[idx[i]]` -- the list of its nearest data image -- unless a member of that
+    list, an image added earlier in this call included, is more similar to it than `th`.  One similarity matrix per call (the
+    members of the touched lists and the generated images against the generated images), then a host walk in upstream's order."""
+    n = len(generated)
+    if n == 0:
+        return img_set
+    idx = [int(i) for i in idx]
+    members, stored = {}, []
+    for k in sorted(set(idx)):
+        members[k] = list(range(len(stored), len(stored) + img_set[k].shape[0]))
+        stored.extend(img_set[k][j] for j in range(img_set[k].shape[0]))
+    base = len(stored)
+    gen = generated.cpu()
+    target = torch.cat((torch.stack(stored).to(gen.dtype), gen), dim=0) if stored else gen
+    S = cosine_similarity_matrix(generated, target).cpu()                # [base + n][n]
+    added = {k: [] for k in members}
+    for i in range(n):
+        k = idx[i]
+        if not any(bool(S[m, i] > th) for m in members[k]):
+            members[k].append(base + i)
+            added[k].append(i)
+    for k, rows in added.items():
+        if rows:
+            img_set[k] = torch.cat((img_set[k], gen[rows]), dim=0)
+    return img_set
 
 
 def remove_duplicates_in_batches(current_batch, th=COSINE_TH):
@@ -149,6 +358,8 @@ class Tester:
         total = torch.empty(0, a.out_channel, a.data_size, a.data_size)
         self.num_total_unique_images = []
         self.nearest_idx = []
+        n_sets = len(self.dataset) if self.dataset is not None else a.data_subset_num
+        self.img_set = [torch.empty(0, a.out_channel, a.data_size, a.data_size) for _ in range(n_sets)]          # tester.py:83
         for _ in range(max_rounds):
             if len(total) >= a.data_subset_num:
                 break
@@ -164,6 +375,7 @@ class Tester:
             self.num_total_unique_images.append(total.shape[0])
             if uniq.shape[0] and self.dataset is not None:
                 self.nearest_idx.append(get_nearest_neighbor_idx(uniq, self.dataset).cpu())
+                self.img_set = get_similar_neighbor(uniq.cpu(), self.img_set, self.nearest_idx[-1], self.cosine_similarity_th)   # :119-120
         self.model.train()
         self.total_unique_images = total
         return total

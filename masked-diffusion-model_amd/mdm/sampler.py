@@ -332,6 +332,28 @@ class Sampler:
         return grid
 
     # ------------------------------------------------------------------------------
+    def get_nearest_neighbor(self, source, augment=False, metric="cosine"):
+        """sampler.py:487-518: for every source image the data image with the largest cosine similarity, both sides resized to
+        32 x 32 (`transforms.Resize([32, 32])`), the data `normalize01`-ed first and the source as it is; `augment`: the score is the
+        larger of the similarity and the similarity with the data batch under `RandomHorizontalFlip()` -- the transform sees a batch of
+        `source.shape[0]` images as one tensor, so one `torch.rand(1) < 0.5` from the default host generator per batch, in data
+        order.  -> `zeros_like(source)` filled with `dataset[idx][0]`.
+
+        Served by an `evaluate.NeighborBank` made once per Sampler (include/mdm_neighbor.h): the data set's 32 x 32 unit rows are
+        built on the device from the storage as it is.  `nn_antialias` (an attribute of the Sampler or of args, default True) is the
+        `antialias` of the resize: True is what torchvision >= 0.17 does on tensors, False what older releases did after a warning."""
+        from . import evaluate
+        if metric.lower() != "cosine":
+            raise UnboundLocalError("score")              # upstream leaves `score` unset for any other metric
+        antialias = bool(getattr(self, "nn_antialias", getattr(self.args, "nn_antialias", True)))
+        bank = getattr(self, "_nn_bank", None)
+        if bank is None or bank.antialias != antialias:
+            bank = self._nn_bank = evaluate.NeighborBank(self.dataset, size=32, antialias=antialias)
+        rows = evaluate.neighbor_flip_rows(len(bank.dataset), source.shape[0]) if augment else None
+        nearest = torch.zeros_like(source)
+        nearest.copy_(bank.nearest(source, rows))
+        return nearest
+
     def _predict(self, model, x_in_nchw, time, fused_nhwc):
         """-> (pred as NHWC tensor, Cp, dtype) ready for mdm_sampler_x0."""
         from .unet import UNet
