@@ -10,13 +10,15 @@ dataset_hist).sample(model, timesteps), Trainer(...).train(...), model(x, t).sam
 from . import _lib  # noqa: F401
 from . import evaluate  # noqa: F401
 from . import ingest  # noqa: F401
+from . import rawsets  # noqa: F401
 from . import visuals  # noqa: F401
 from ._lib import BF16, F32  # noqa: F401
 from .data import DeviceDataset, DeviceLoader  # noqa: F401
 from .dist import GradComm  # noqa: F401
 from .evaluate import NeighborBank, get_nearest_neighbor, get_nearest_neighbor_idx, get_similar_neighbor  # noqa: F401
-from .ingest import get_dataset, image_folder, resize_crop_plan  # noqa: F401
+from .ingest import get_dataset, image_folder, ingest_block, resize_crop_plan  # noqa: F401
 from .optim import EMA, SGD, Accelerator, Adam, AdamW, get_lr_scheduler, get_optimizer  # noqa: F401
+from .rawsets import cifar10_arrays, flowers102_samples, mnist_arrays, read_idx  # noqa: F401
 from .sampler import Sampler  # noqa: F401
 from .scheduler import Scheduler  # noqa: F401
 from .train_step import MonitorRing  # noqa: F401

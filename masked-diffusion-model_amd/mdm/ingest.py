@@ -9,9 +9,16 @@ fixed point, a uint8 rounding between the horizontal and the vertical pass), kee
 into the tensor that becomes `DeviceDataset.data`.  `ToTensor` + `Normalize` stay the 256-entry table of `mdm.data.normalize_lut()`,
 so `ds[i]` and every gathered batch hold upstream's values bit for bit.
 
-What is not built: the four data sets upstream downloads (mnist, cifar10, flowers102, lsun -- `get_dataset` names them and says
-so), and `use_augment`: upstream's `MyDataset` never passes it on to `get_dataset` (mydataset.py:245), and its own
-`self.transform(sample)` (:275-276) names an undefined variable and raises NameError.  `DeviceLoader(hflip=p)` is the flip there is.
+mnist, cifar10 and flowers102 -- the sets upstream builds with torchvision's `download=True`, which reads the files under `root` when
+they are already there -- are read from those local files by mdm/rawsets.py and come through the same kernel: MNIST and CIFAR-10 are
+one block of same-shape images each, and `ingest_block` stages such a block a chunk at a time (one host copy, one asynchronous
+copy and one launch per chunk) where `ingest_arrays` would copy 60 000 arrays one by one; Flowers102 is a list of JPEG files and
+takes the folder path.  MNIST gives a one-channel data set (PIL mode L, as torchvision hands it to the transform).
+
+What is not built: any fetching (files that are not there are an error that says where they were looked for), torchvision's md5
+check, lsun (it needs lmdb; `get_dataset` names it and says so), and `use_augment`: upstream's `MyDataset` never passes it on to
+`get_dataset` (mydataset.py:245), and its own `self.transform(sample)` (:275-276) names an undefined variable and raises NameError.
+`DeviceLoader(hflip=p)` is the flip there is.
 
 There is no fallback: without a GPU nothing is resized, and the call says so.
 """
@@ -24,7 +31,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, rawsets
 from ._lib import call, ptr, stream
 from .data import DeviceDataset
 
@@ -169,6 +176,23 @@ class _Chunks:
         self.view[self.count * nbytes:(self.count + 1) * nbytes] = arr.reshape(-1)
         self.count += 1
 
+    def add_block(self, block):
+        """`block`: uint8 [K][h][w][C] -> its images in chunks of at most `chunk_bytes` (one image at the least): one host copy
+        into the pinned buffer, then `flush`, per chunk"""
+        K, h, w, C = block.shape
+        if C != self.C:
+            raise ValueError(f"mdm.ingest: the block has {C} channels, the data set {self.C}")
+        self.flush()
+        if self.done + K > self.data.shape[0]:
+            raise ValueError(f"mdm.ingest: more than the {self.data.shape[0]} images announced")
+        nbytes = h * w * C
+        per = max(1, self.chunk_bytes // nbytes)
+        for lo in range(0, K, per):
+            n = min(per, K - lo)
+            self.cap, self.shape, self.count = self._buffers(n * nbytes), (h, w, C), n
+            np.copyto(self.host[self.cur].numpy()[:n * nbytes].reshape(n, h, w, C), block[lo:lo + n])
+            self.flush()
+
     def flush(self):
         if self.shape is None:
             return
@@ -202,6 +226,22 @@ def ingest_arrays(arrays, size, *, C=3, device=None, chunk_bytes=CHUNK_BYTES):
     return chunks.finish()
 
 
+def ingest_block(block, size, *, device=None, chunk_bytes=CHUNK_BYTES):
+    """A block of same-shape decoded images (uint8 [K, h, w], or [K, h, w, C] with C 1 or 3; any strides) -> uint8 device tensor
+    [K, C, size, size], the bytes `ingest_arrays` gives for the same images.  The block is cut into chunks of at most
+    `chunk_bytes`; each is ONE host copy into the pinned buffer (the two buffers take turns), one asynchronous copy and one
+    `mdm_ingest_resize_crop` launch.  At `size == h == w` the plans are the identity tables and the kernel writes the source
+    bytes, planar."""
+    block = np.asarray(block)
+    if block.ndim == 3:
+        block = block[:, :, :, None]
+    if block.dtype != np.uint8 or block.ndim != 4 or block.shape[3] not in (1, 3) or 0 in block.shape:
+        raise ValueError(f"mdm.ingest: a block is a non-empty uint8 [K][h][w] or [K][h][w][C] with C 1 or 3, got {block.dtype} {block.shape}")
+    chunks = _Chunks(block.shape[0], block.shape[3], int(size), _device(device), chunk_bytes)
+    chunks.add_block(block)
+    return chunks.finish()
+
+
 def ingest_files(paths, size, *, device=None, chunk_bytes=CHUNK_BYTES, loader=pil_loader, threads=None):
     """Image files -> uint8 device tensor [M, 3, size, size], in the order of `paths`.  `loader(path)` runs on a pool of
     `decode_threads()` host threads, at most four files per thread ahead of the one being staged, so the decoded images held at
@@ -229,6 +269,13 @@ def _device(device):
     return torch.device(device)
 
 
+def _need_gpu(device):
+    device = _device(device)
+    if device.type != "cuda":
+        raise TypeError(f"mdm.ingest: the images are resized by the kernel of mdm_ingest.h, which needs a GPU, not {device}")
+    return device
+
+
 def dataset_from_samples(samples, size, *, num_timesteps=1, device=None, chunk_bytes=CHUNK_BYTES, **kw):
     """`(path, label)` pairs -> DeviceDataset, as `MyDataset.__init__` materialises them (mydataset.py:246-265): `random` is
     drawn first from the default host generator, then every item is read once -- reading draws nothing, there or here.  The
@@ -236,9 +283,7 @@ def dataset_from_samples(samples, size, *, num_timesteps=1, device=None, chunk_b
     samples = list(samples)
     if not samples:
         raise ValueError("mdm.ingest: the data set is empty")
-    device = _device(device)
-    if device.type != "cuda":
-        raise TypeError(f"mdm.ingest: the images are resized by the kernel of mdm_ingest.h, which needs a GPU, not {device}")
+    device = _need_gpu(device)
     random = torch.FloatTensor(len(samples), int(num_timesteps)).uniform_(-1.0, 1.0)
     data = ingest_files([p for p, _ in samples], size, device=device, chunk_bytes=chunk_bytes)
     return DeviceDataset(data, torch.tensor([float(l) for _, l in samples]), random, device=device, **kw)
@@ -248,8 +293,9 @@ def folder_roots(path, name, split):
     """The ImageFolder roots upstream's `get_dataset` reads for `(name, split)`, in its order of concatenation"""
     key = str(name).lower()
     if key in DOWNLOADS:
-        raise ValueError(f"get_dataset: '{name}' is one of the data sets upstream downloads ({', '.join(DOWNLOADS)}); downloads are "
-                         "not built -- decode it yourself and give the tensor to DeviceDataset")
+        raise ValueError(f"get_dataset: '{name}' is one of the data sets upstream downloads ({', '.join(DOWNLOADS)}), not an image "
+                         "folder; downloads are not built -- get_dataset reads the local files of mnist, cifar10 and flowers102 "
+                         "(mdm/rawsets.py); lsun needs lmdb: decode it yourself and give the tensor to DeviceDataset")
     if key not in FOLDER_SETS:
         raise ValueError(f"get_dataset: unknown data set '{name}'; the folder-backed ones are {', '.join(FOLDER_SETS)}")
     if split not in FOLDER_SETS[key]:
@@ -257,18 +303,44 @@ def folder_roots(path, name, split):
     return [os.path.join(path, key, sub) if sub else os.path.join(path, key) for sub in FOLDER_SETS[key][split]]
 
 
+def _first(items, data_subset, num_data):
+    """`Subset(dataset, range(0, num_data))` of upstream's MyDataset: the number of leading items that are kept"""
+    if not data_subset:
+        return len(items)
+    if not 0 < int(num_data) <= len(items):
+        raise ValueError(f"get_dataset: num_data = {num_data} of {len(items)} items")
+    return int(num_data)
+
+
+def dataset_from_block(images, labels, size, *, num_timesteps=1, device=None, chunk_bytes=CHUNK_BYTES, **kw):
+    """A block of same-shape decoded images (see `ingest_block`) and their labels -> DeviceDataset, as `MyDataset.__init__`
+    materialises them: refused without a GPU before anything is drawn, then `random` from the default host generator, then the
+    images.  The channel count is the block's: 1 for [M, h, w]."""
+    device = _need_gpu(device)
+    random = torch.FloatTensor(len(images), int(num_timesteps)).uniform_(-1.0, 1.0)
+    data = ingest_block(images, size, device=device, chunk_bytes=chunk_bytes)
+    return DeviceDataset(data, torch.as_tensor(np.asarray(labels, dtype=np.float32)), random, device=device, **kw)
+
+
 def get_dataset(path, name, size, split, data_subset=False, num_data=0, *, num_timesteps=1, device=None, **kw):
-    """Upstream's `MyDataset(path, name, size, split, data_subset, num_data, num_timesteps=...)` for its folder-backed data sets,
-    as a DeviceDataset: the directory layout, the `split` words ('all' concatenates in upstream's order) and the labels
-    (celeba_hq female 0 / male 1, afhqv2 cat 0 / dog 1 / wild 2: the sorted class folders of every root) are upstream's.
-    `data_subset` keeps the first `num_data` items (`Subset(dataset, range(0, num_data))`); only those are decoded.
-    mnist, cifar10, flowers102 and lsun are downloads and raise.  `use_augment` is not a parameter: upstream's MyDataset never
-    passes it on to its get_dataset, and its own flip branch raises NameError."""
-    samples = []
-    for root in folder_roots(path, name, split):
-        samples += image_folder(root)[2]
-    if data_subset:
-        if not 0 < int(num_data) <= len(samples):
-            raise ValueError(f"get_dataset: num_data = {num_data} of {len(samples)} items")
-        samples = samples[:int(num_data)]
+    """Upstream's `MyDataset(path, name, size, split, data_subset, num_data, num_timesteps=...)` as a DeviceDataset: the directory
+    layout, the `split` words ('all' concatenates in upstream's order) and the labels are upstream's.
+    celeba_hq, afhqv2, metfaces, stanfordcars: image folders (celeba_hq female 0 / male 1, afhqv2 cat 0 / dog 1 / wild 2: the
+    sorted class folders of every root).  mnist (one channel), cifar10, flowers102: torchvision's local files (mdm/rawsets.py);
+    when they are not under `path` the call says where it looked -- upstream would download them there, and downloads are not
+    built.  lsun raises.  `data_subset` keeps the first `num_data` items (`Subset(dataset, range(0, num_data))`); only those are
+    staged or decoded.  `use_augment` is not a parameter: upstream's MyDataset never passes it on to its get_dataset, and its own
+    flip branch raises NameError."""
+    key = str(name).lower()
+    if key in ("mnist", "cifar10"):
+        images, labels = (rawsets.mnist_arrays if key == "mnist" else rawsets.cifar10_arrays)(path, split)
+        n = _first(images, data_subset, num_data)
+        return dataset_from_block(images[:n], labels[:n], size, num_timesteps=num_timesteps, device=device, **kw)
+    if key == "flowers102":
+        samples = rawsets.flowers102_samples(path, split)
+    else:
+        samples = []
+        for root in folder_roots(path, name, split):
+            samples += image_folder(root)[2]
+    samples = samples[:_first(samples, data_subset, num_data)]
     return dataset_from_samples(samples, size, num_timesteps=num_timesteps, device=device, **kw)
