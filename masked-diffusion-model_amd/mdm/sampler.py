@@ -6,7 +6,8 @@ Mirrors reference code/sampler.py: `_get_latent_initial` (:46-83), `sample` (:10
 `_sample_mean_shift_momentum` (:109-261) for the options that run upstream at HEAD
 (`sampling_mask_dependency` in {independent, dependent_prev, dependent_t -- the last for
 'thresholding' with mean_option 'degraded_area' or "0", scheduler.py:480-549}, `momentum_adaptive`
-in {base_sampling, base_momentum}).
+in {base_sampling, base_momentum}).  `sample_inpaint` has no upstream counterpart: the same
+loop with every prediction projected onto the given pixels (include/mdm_inpaint.h).
 
 What is different from the reference loop (same arithmetic, same RNG order in replay mode):
   * the whole state stays on the GPU; nothing is copied to the host inside the loop.  The
@@ -53,6 +54,52 @@ def gather_shards(local, n, group=None):
     parts = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(parts, pad, group=group)
     return torch.cat([p[:k] for p, k in zip(parts, sizes)], 0)
+
+
+def inpaint_start_index(ratio_list, timesteps, unknown_fraction):
+    """Where a 'matched' inpainting run begins: the first j with ratio_list[timesteps[j] - 1] >= unknown_fraction (the schedule at
+    that timestep hides at least as much as the hole does), len(timesteps) - 1 if no used timestep reaches it.  The reverse loop
+    then walks timesteps[:j + 1] from its end.  Pure host arithmetic in fp64."""
+    frac = float(unknown_fraction)
+    for j, t in enumerate(timesteps):
+        if float(ratio_list[int(t) - 1]) >= frac:
+            return j
+    return len(timesteps) - 1
+
+
+def inpaint_keep(kind, N, H, W, **kw):
+    """A keep mask [N, 1, H, W] fp32 on the host, 1 = given, 0 = not given.  kind "box": the rectangle `top, left, height, width`
+    is not given; "half": the `side` ('left', 'right', 'top', 'bottom') half is not given; "random": each pixel is not given with
+    probability `p`, drawn as torch.rand(N, 1, H, W, generator=generator) < p."""
+    keep = torch.ones(N, 1, H, W)
+    def take(*names):
+        extra = set(kw) - set(names)
+        if extra or len(kw) != len(names):
+            raise TypeError(f"inpaint_keep({kind!r}): takes {', '.join(names)}, got {', '.join(sorted(kw)) or 'nothing'}")
+        return [kw[k] for k in names]
+    if kind == "box":
+        top, left, height, width = take("top", "left", "height", "width")
+        if not (0 <= top and 0 <= left and height >= 0 and width >= 0 and top + height <= H and left + width <= W):
+            raise ValueError(f"inpaint_keep('box'): {(top, left, height, width)} does not lie inside {H} x {W}")
+        keep[:, :, top:top + height, left:left + width] = 0
+    elif kind == "half":
+        side, = take("side")
+        if side not in ("left", "right", "top", "bottom"):
+            raise ValueError(f"inpaint_keep('half'): side={side!r}: one of 'left', 'right', 'top', 'bottom'")
+        if side in ("left", "right"):
+            keep[..., :W // 2] = 0
+            if side == "right":
+                keep = keep.flip(-1)
+        else:
+            keep[:, :, :H // 2] = 0
+            if side == "bottom":
+                keep = keep.flip(-2)
+    elif kind == "random":
+        p, generator = take("p", "generator")
+        keep[torch.rand(N, 1, H, W, generator=generator) < p] = 0
+    else:
+        raise ValueError(f"inpaint_keep: kind={kind!r}: one of 'box', 'half', 'random'")
+    return keep.contiguous()
 
 
 class Sampler:
@@ -134,6 +181,90 @@ class Sampler:
             g = gather_shards(h.to(x0.device).transpose(0, 1).contiguous(), n).transpose(0, 1)
             return g if h.is_cuda else g.cpu()
         return gather_shards(x0, n), [gather_hist(h) for h in hist]
+
+    # ---- inpainting (no upstream counterpart; include/mdm_inpaint.h, DESIGN.md finding 70) ----------------------
+    def sample_inpaint(self, model, timesteps_used_epoch, known, keep, start="latent"):
+        """Complete partly given images: -> (sample_0, history lists) like `sample`.  `known` [sample_num, C, H, W] fp32 on the
+        device, in the data range; `keep` [sample_num, 1 or C, H, W] fp32 on the device, a pixel is GIVEN where keep != 0.
+
+        Every reverse step runs as `sample` runs it, then its prediction is projected onto the data -- x0_hat = keep != 0 ? known :
+        x0_hat, a select -- and the degrades, fill means, mask dependencies and momentum modes go on from the projected x0_hat.
+        Given pixels are hidden and revealed by the schedule like any others and come out bit-equal to `known`.  `start`:
+          "latent"      `_get_latent_initial`, the host draws of `sample`;
+          "known_mean"  a constant image per sample, the mean of its given values (per channel for mean_area 'channel-wise'); an
+                        image with nothing given takes its row of the "latent" draw, which is made either way;
+          "matched"     keep ? known : mean, and the loop begins at the first used timestep whose ratio reaches the largest
+                        unknown fraction of the batch (`inpaint_start_index`; one host read before the loop).  Fewer steps for
+                        small holes; what that does to image quality has NOT been measured.
+        With a process group every rank gets the full `known` / `keep`, runs its rows (`model` built for `local_sample_num()`) and
+        the shards are all-gathered at the end; the start index of "matched" comes from the full batch on every rank."""
+        rank, world = self._shard()
+        if world == 1:
+            return self._sample_inpaint(model, timesteps_used_epoch, known, keep, start)
+        n = self.args.sample_num
+        lo, hi = shard_bounds(n, rank, world)
+        if hi == lo:
+            raise ValueError(f"sample_num={n} < world size {world}: a rank would sample nothing")
+        x0, hist = self._sample_inpaint(model, timesteps_used_epoch, known, keep, start, rows=(lo, hi))
+        def gather_hist(h):             # [T+1, n_local, C, H, W], on the host when args.sample_history is True
+            g = gather_shards(h.to(x0.device).transpose(0, 1).contiguous(), n).transpose(0, 1)
+            return g if h.is_cuda else g.cpu()
+        return gather_shards(x0, n), [gather_hist(h) for h in hist]
+
+    def _check_inpaint_args(self, known, keep, start):
+        a, dev = self.args, self.Scheduler.device
+        if start not in ("latent", "known_mean", "matched"):
+            raise ValueError(f"start={start!r}: one of 'latent', 'known_mean', 'matched'")
+        want = (a.sample_num, a.out_channel, a.data_size, a.data_size)
+        for name, t in (("known", known), ("keep", keep)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}: a torch.Tensor is needed, not {type(t).__name__}")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name}: dtype {t.dtype}, float32 is needed")
+            if t.device != dev:
+                raise ValueError(f"{name}: on {t.device}, the sampler runs on {dev}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name}: not contiguous")
+        if tuple(known.shape) != want:
+            raise ValueError(f"known: shape {tuple(known.shape)}, (sample_num, C, H, W) = {want} is needed")
+        if keep.dim() != 4 or (keep.shape[0], *keep.shape[2:]) != (want[0], *want[2:]) or keep.shape[1] not in (1, want[1]):
+            raise ValueError(f"keep: shape {tuple(keep.shape)}, {(want[0], 1, *want[2:])} or {want} is needed")
+
+    def _sample_inpaint(self, model, timesteps, known, keep, start="latent", rows=None):
+        """`sample_inpaint` on rows [lo, hi) of the batch (`rows`; all of it by default): `known` / `keep` and every host draw are
+        the full batch's, `model` is built for hi - lo samples."""
+        import argparse
+        self._check_inpaint_args(known, keep, start)
+        full, S = self.args, self.Scheduler
+        n, c, hw = full.sample_num, full.out_channel, full.data_size
+        lo, hi = rows if rows is not None else (0, n)
+        steps = list(timesteps)
+        latent = self._get_latent_initial(model)                      # the full draw in every start: the host generator moves as in `sample`
+        x_t = latent[lo:hi]
+        if start != "latent":
+            fallback = latent[:, :, 0, 0].to(S.device, torch.float32).contiguous()
+            x_start = torch.empty_like(known) if start == "matched" else None
+            mu = torch.empty(n, c, device=S.device) if start == "known_mean" else None
+            unknown = torch.empty(n, dtype=torch.int32, device=S.device) if start == "matched" else None
+            call("mdm_inpaint_start", known=ptr(known), keep=ptr(keep), keep_C=keep.shape[1], fallback=ptr(fallback),
+                 per_channel=int(full.mean_area == "channel-wise"), N=n, C=c, HW=hw * hw, x_start=ptr(x_start), mu=ptr(mu),
+                 unknown=ptr(unknown), stream=stream())
+            if start == "matched":      # the ONE host read: the largest hole of the FULL batch, so every shard walks the same steps
+                j = inpaint_start_index(S.ratio_list, steps, int(unknown.max()) / float(hw * hw))
+                steps, x_t = steps[:j + 1], x_start[lo:hi]
+            else:
+                x_t = mu[lo:hi, :, None, None].expand(hi - lo, c, hw, hw)
+        inpaint = (known[lo:hi], keep[lo:hi])                         # leading-dimension slices: contiguous views
+        if rows is None:
+            return self._sample_mean_shift_momentum(model, steps, latent=x_t, inpaint=inpaint, hist_steps=len(timesteps))
+        try:
+            self.args = argparse.Namespace(**vars(full))
+            self.args.sample_num = hi - lo
+            S.replay_rows = (lo, hi, n)                               # every later host draw: full batch, sliced (replay mode)
+            return self._sample_mean_shift_momentum(model, steps, latent=x_t, inpaint=inpaint, hist_steps=len(timesteps))
+        finally:
+            self.args = full
+            S.replay_rows = None
 
     # ---- latent interpolation (sampler.py:86-99, 264-366) ------------------------------------------------------
     def _get_latent_initial_interpolation(self, interpolation_shift):
@@ -381,8 +512,13 @@ class Sampler:
         params()
         S.emit_shift(b.x_t, b.s, b.x_in, kind=b.kind, ratio=b.ratio if b.kind != 0 else None, z=b.draw_z(), nhwc=b.nhwc)  # :142-143
         pred, cp, pdt = forward()                                                                                      # :145
-        call("mdm_sampler_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), N=n, C=c, H=h, W=w,
-             pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0), x0_hat=ptr(b.x0_hat), stream=stream())              # :146-152
+        if getattr(b, "known", None) is not None:       # inpainting: the same reconstruction, then the given pixels put back
+            call("mdm_inpaint_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), known=ptr(b.known),
+                 keep=ptr(b.keep), keep_C=b.keep.shape[1], N=n, C=c, H=h, W=w, pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0),
+                 x0_hat=ptr(b.x0_hat), stream=stream())
+        else:
+            call("mdm_sampler_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), N=n, C=c, H=h, W=w,
+                 pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0), x0_hat=ptr(b.x0_hat), stream=stream())          # :146-152
         degrade = functools.partial(S.emit_degrade, b.x0_hat, mean_pixel=b.mp, mean_option=a.mean_option, mean_area=a.mean_area)
         if dep == "independent":                                                                                       # :175-181
             degrade(b.d_t, rng_stream=3, mask_out=b.m_t, **mask_src(b.amt_t, b.mi_t))
@@ -443,7 +579,10 @@ class Sampler:
             return dict(amount=amount, u=S.host_uniforms(b.x_t))
         return (lambda: S.host_shift_z(S._host_full(b.ratio.cpu(), n), n, c, h, w) if b.kind != 0 else None), mask_src
 
-    def _sample_mean_shift_momentum(self, model, timesteps, latent=None):
+    def _sample_mean_shift_momentum(self, model, timesteps, latent=None, inpaint=None, hist_steps=None):
+        """sampler.py:109-261.  `inpaint = (known, keep)`: the rows of this run on the device; every step then projects its
+        prediction onto them (`sample_inpaint`).  `hist_steps`: the history lists get that many slots + 1 (a 'matched' run walks
+        fewer steps than the list it was given has; the slots behind them stay zero)."""
         from .unet import UNet
         a, S = self.args, self.Scheduler
         dev, T = S.device, len(timesteps)
@@ -475,10 +614,13 @@ class Sampler:
             s=img(), x_in=img(), pred_nchw=img(hist_mode), shifted0=img(hist_mode), x0_hat=img(), d_t=img(), d_next=img(), m_t=img(),
             m_next=torch.zeros_like(x_t), mi_t=img(indexing and S.rng_mode == "device"), mi_next=img(indexing and S.rng_mode == "device"),
             mp=torch.empty(n, c, device=dev), diff=torch.zeros_like(x_t))
+        if inpaint is not None:
+            b.known, b.keep = inpaint
         b.draw_z, b.mask_src = self._draws(b)
         if graph:
             return self._sample_graph(model, timesteps, b), []
-        hist = {k: torch.zeros(T + 1, n, c, hw, hw, device=dev) for k in HISTORY_NAMES} if hist_mode else None
+        slots = (T if hist_steps is None else hist_steps) + 1
+        hist = {k: torch.zeros(slots, n, c, hw, hw, device=dev) for k in HISTORY_NAMES} if hist_mode else None
 
         def params(i):                          # what mdm_sampler_step_params does for the graph loop
             S.dev_rng.advance()
