@@ -5,7 +5,8 @@
  * presentation ABI, include/mdm_data.h of the data ABI and include/mdm_interp.h of the interpolation sampler; what is declared here
  * is bound next to them (mdm/_lib.py: INGEST_PROTOS / INGEST_EXPORTS).  Same conventions: every function returns 0 or non-zero with
  * the text in mdm_last_error, a refused call launches nothing, the stream is the last parameter, nothing here allocates or
- * synchronises.  mdm_ingest_plan is host code with HOST pointers and no stream; mdm_ingest_resize_crop takes DEVICE pointers.
+ * synchronises.  mdm_ingest_plan and mdm_ingest_launch_of are host code with HOST pointers and no stream; mdm_ingest_resize_crop
+ * takes DEVICE pointers.
  *
  * Replaces the transform of upstream's get_dataset (utils/mydataset.py:77-83: Resize(size), CenterCrop(size), ToTensor(),
  * Normalize([0.5], [0.5]) on the PIL image an ImageFolder opens) as MyDataset.__init__ runs it over the whole set (:245-265).
@@ -57,6 +58,19 @@ int mdm_ingest_resize_crop(const uint8_t* src, int64_t src_stride, int K, int h,
                            const int32_t* hbounds, const int32_t* hcoeffs, int ksh,
                            const int32_t* vbounds, const int32_t* vcoeffs, int ksv,
                            uint8_t* dst, int64_t dst_stride, int64_t M, int64_t first, int S, void* stream);
+
+/* The launch mdm_ingest_resize_crop would make for a source row of w pixels of C channels, S kept columns and a horizontal table of
+ * ksh taps, without making it.  Host only: no stream, no device, nothing is launched.  It is the launcher's own statement of its
+ * geometry (the launcher asks the same function), so a test that wants a given kernel instantiation or row tile asks here.
+ *   out[0]  TR: the output rows of one workgroup, min(S, 8) shrunk until two row buffers (w C + 16 bytes, rounded up to 16, each),
+ *           TR S C int32 accumulators and 2 TR vertical bounds fit the 64 KiB of LDS of a workgroup
+ *   out[1]  1 when the horizontal table (S (2 + ksh) int32) fits behind them and is copied into LDS, 0 when the kernel reads it
+ *           from global memory -- the two instantiations of the kernel
+ *   out[2]  the dynamic LDS of a workgroup in bytes, the table included when it is in LDS (<= 65536)
+ *   out[3]  the workgroups per image, ceil(S / TR); the last one has S - (out[3] - 1) TR rows
+ * Refused: out NULL; C outside {1, 3}; w or S <= 0; ksh < 1; and what does not fit at TR = 1, exactly where and in the words with
+ * which mdm_ingest_resize_crop refuses it. */
+int mdm_ingest_launch_of(int w, int C, int S, int ksh, int32_t out[4]);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,48 @@ extern "C" int mdm_ingest_plan(int in_size, int out_size, int first, int count, 
     return ks;
 }
 
+// The launch geometry of mdm_ingest_resize_crop, stated once: the launcher takes every number of its launch from here and
+// mdm_ingest_launch_of reports the same numbers.  Pure host arithmetic on w, C, S and ksh (the callers have checked them): the row
+// tile shrinks from min(S, 8) until two row buffers, its accumulators and its vertical bounds fit the LDS of a workgroup; the
+// horizontal table joins them there when it still fits and stays in global memory when it does not.
+struct IngestGeometry {
+    int tr;             // output rows per workgroup
+    bool table_lds;     // the horizontal table is copied into LDS (ingest_resize_crop_kernel<true>)
+    int64_t row_bytes;  // one LDS row buffer: w C + 16, rounded up to 16
+    int64_t lds;        // dynamic LDS of a workgroup, bytes
+    int64_t tiles;      // workgroups per image
+};
+static int ingest_geometry(int w, int C, int S, int ksh, IngestGeometry& g) {
+    const int64_t row_bytes = (((int64_t)w * C + 16) + 15) & ~(int64_t)15;
+    const int64_t NJ = (int64_t)S * C;
+    // LDS of a workgroup with TR output rows: two row buffers, TR NJ accumulators, 2 TR vertical bounds (+ the horizontal table)
+    auto lds_of = [&](int tr) { return 2 * row_bytes + 4 * (tr * NJ + 2 * tr); };
+    int tr = S < INGEST_MAX_TR ? S : INGEST_MAX_TR;
+    while (tr > 1 && lds_of(tr) > INGEST_LDS) --tr;
+    MDM_REQUIRE(lds_of(tr) <= INGEST_LDS,
+                "ingest_resize_crop: two rows of w C = %lld bytes and S C = %lld accumulators need %lld bytes of LDS, past %lld",
+                (long long)w * C, (long long)NJ, (long long)lds_of(tr), (long long)INGEST_LDS);
+    const int64_t table = 4 * (2 * (int64_t)S + (int64_t)S * ksh);
+    g.tr = tr;
+    g.row_bytes = row_bytes;
+    g.table_lds = lds_of(tr) + table <= INGEST_LDS;
+    g.lds = lds_of(tr) + (g.table_lds ? table : 0);
+    g.tiles = (S + tr - 1) / tr;
+    return 0;
+}
+
+extern "C" int mdm_ingest_launch_of(int w, int C, int S, int ksh, int32_t out[4]) {
+    MDM_REQUIRE(out, "ingest_launch_of: out is NULL");
+    MDM_REQUIRE(C == 1 || C == 3, "ingest_launch_of: C = %d is not 1 or 3", C);
+    MDM_REQUIRE(w > 0, "ingest_launch_of: w must be positive (%d)", w);
+    MDM_REQUIRE(S > 0, "ingest_launch_of: S must be positive (%d)", S);
+    MDM_REQUIRE(ksh >= 1, "ingest_launch_of: ksh = %d is below 1", ksh);
+    IngestGeometry g;
+    if (int rc = ingest_geometry(w, C, S, ksh, g)) return rc;
+    out[0] = g.tr; out[1] = g.table_lds ? 1 : 0; out[2] = (int32_t)g.lds; out[3] = (int32_t)g.tiles;
+    return 0;
+}
+
 extern "C" int mdm_ingest_resize_crop(const uint8_t* src, int64_t src_stride, int K, int h, int w, int C,
                                       const int32_t* hbounds, const int32_t* hcoeffs, int ksh,
                                       const int32_t* vbounds, const int32_t* vcoeffs, int ksv,
@@ -186,26 +228,16 @@ extern "C" int mdm_ingest_resize_crop(const uint8_t* src, int64_t src_stride, in
     MDM_REQUIRE(first >= 0, "ingest_resize_crop: first %lld is negative", (long long)first);
     MDM_REQUIRE(first <= M - K, "ingest_resize_crop: first + K = %lld is past M = %lld", (long long)(first + K), (long long)M);
 
+    IngestGeometry g;
+    if (int rc = ingest_geometry(w, C, S, ksh, g)) return rc;
     IngestArgs a;
     a.src = src; a.hbounds = hbounds; a.hcoeffs = hcoeffs; a.vbounds = vbounds; a.vcoeffs = vcoeffs; a.dst = dst;
     a.src_stride = src_stride; a.dst_stride = dst_stride; a.first = first;
     a.h = h; a.w = w; a.C = C; a.S = S; a.ksh = ksh; a.ksv = ksv;
-    const int64_t row_bytes = (((int64_t)w * C + 16) + 15) & ~(int64_t)15;
-    const int64_t NJ = (int64_t)S * C;
-    // LDS of a workgroup with TR output rows: two row buffers, TR NJ accumulators, 2 TR vertical bounds (+ the horizontal table)
-    auto lds_of = [&](int tr) { return 2 * row_bytes + 4 * (tr * NJ + 2 * tr); };
-    int tr = S < INGEST_MAX_TR ? S : INGEST_MAX_TR;
-    while (tr > 1 && lds_of(tr) > INGEST_LDS) --tr;
-    MDM_REQUIRE(lds_of(tr) <= INGEST_LDS,
-                "ingest_resize_crop: two rows of w C = %lld bytes and S C = %lld accumulators need %lld bytes of LDS, past %lld",
-                (long long)w * C, (long long)NJ, (long long)lds_of(tr), (long long)INGEST_LDS);
-    const int64_t table = 4 * (2 * (int64_t)S + (int64_t)S * ksh);
-    a.TR = tr; a.row_bytes = (int)row_bytes;
-    const bool table_lds = lds_of(tr) + table <= INGEST_LDS;
-    const int64_t lds = lds_of(tr) + (table_lds ? table : 0);
-    const int64_t blocks = (int64_t)K * ((S + tr - 1) / tr);
+    a.TR = g.tr; a.row_bytes = (int)g.row_bytes;
+    const int64_t blocks = (int64_t)K * g.tiles;
     MDM_REQUIRE(blocks <= INT32_MAX, "ingest_resize_crop: K = %d images of S = %d rows are too many workgroups for one launch", K, S);
-    if (table_lds) hipLaunchKernelGGL(ingest_resize_crop_kernel<true>, dim3((unsigned)blocks), dim3(INGEST_THREADS), (size_t)lds, (hipStream_t)stream, a);
-    else hipLaunchKernelGGL(ingest_resize_crop_kernel<false>, dim3((unsigned)blocks), dim3(INGEST_THREADS), (size_t)lds, (hipStream_t)stream, a);
+    if (g.table_lds) hipLaunchKernelGGL(ingest_resize_crop_kernel<true>, dim3((unsigned)blocks), dim3(INGEST_THREADS), (size_t)g.lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(ingest_resize_crop_kernel<false>, dim3((unsigned)blocks), dim3(INGEST_THREADS), (size_t)g.lds, (hipStream_t)stream, a);
     return launch_status("ingest_resize_crop");
 }

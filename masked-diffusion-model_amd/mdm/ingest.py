@@ -125,6 +125,17 @@ def device_plans(h, w, size, device):
     return _device_axis_plan(w, ow, left, size, torch.device(device)) + _device_axis_plan(h, oh, top, size, torch.device(device))
 
 
+def launch_of(w, C, size, ksh):
+    """The launch `mdm_ingest_resize_crop` would make, without making it (`mdm_ingest_launch_of`, host arithmetic) -> (rows of a
+    workgroup's tile, whether the horizontal table is in LDS, LDS bytes of a workgroup, workgroups per image); None for what
+    the launcher refuses -- `mdm_last_error` then says why."""
+    import ctypes
+    out = (ctypes.c_int32 * 4)()
+    if _lib.load().mdm_ingest_launch_of(int(w), int(C), int(size), int(ksh), out) != 0:
+        return None
+    return out[0], bool(out[1]), out[2], out[3]
+
+
 def resize_crop(src, K, h, w, C, plans, dst, first, size, src_stride=None):
     """One `mdm_ingest_resize_crop` launch on the current stream: K images [h][w][C] at `src` (uint8 device tensor, image k at
     byte k src_stride) -> images first .. first + K - 1 of `dst` ([M, C, size, size] uint8, contiguous, on the device)."""

@@ -4,7 +4,10 @@ with the uint8 rounding between them, and torchvision's `Resize(size)` + `Center
 it against tests/golden/ingest.npz and against the installed PIL; the GPU tests then check the kernel against all three.
 
 CASES is the list the golden file, the CPU tests and the GPU tests share: name -> (h, w, C, size, fill); fill None = seeded bytes.
+GEOMETRY_CASES (below it) are the shapes that reach the other launch geometries of the kernel; tests/test_ingest_geometry_gpu.py
+runs them.
 """
+import functools
 import math
 import zlib
 
@@ -35,9 +38,40 @@ EXPECTED_PLANS = {
 }
 
 
+# The launch geometries of mdm_ingest_resize_crop that no entry of CASES selects (every one of those is TR = min(S, 8) with the
+# horizontal table in LDS and at most 192 (channel, column) pairs): same format, same seeded source.  They are NOT in
+# tests/golden/ingest.npz -- some outputs are over a megabyte; their references are the restatement and, where the resized image is
+# small enough to build (pil_allowed), the installed PIL.  GEOMETRY_EXPECTED is what each is there for, as mdm_ingest_launch_of must
+# report it: (TR, horizontal table in LDS, workgroups per image); tests/test_ingest_cpu.py asks the query, nothing restates the rule.
+GEOMETRY_CASES = {
+    "preset128": (150, 131, 3, 128, None),          # NJ = 384: a second trip of the lane loops, 16 row tiles, top 9
+    "preset256": (300, 270, 3, 256, None),          # NJ = 768: three trips
+    "grey264": (280, 300, 1, 264, None),            # one channel past 256 lanes, left 9
+    "table_global_830": (830, 830, 3, 500, None),   # the table stays in global memory, 5 taps, last tile 500 mod 8 = 4 rows
+    "tr7_33x40": (33, 40, 3, 700, None),            # NJ = 2100 shrinks the row tile to 7; upsampling, left 74
+    "wide_12x9000": (12, 9000, 3, 256, None),       # 27 000-byte rows shrink it to 3; last tile 256 mod 3 = 1 row; too large for PIL
+    "edge_8x10880": (8, 10880, 3, 16, None),        # TR = 1, 65 512 of 65 536 bytes: the widest row that is accepted
+    "narrow_40x3_L": (40, 3, 1, 8, None),           # 3-byte rows: no aligned middle, the head is cut to the row
+    "narrow_9x5": (9, 5, 3, 8, None),               # 15-byte rows, three channels
+    "one_1x1": (1, 1, 3, 4, None),                  # every tap on the only pixel: the output is constant
+}
+GEOMETRY_EXPECTED = {
+    "preset128": (8, True, 16), "preset256": (8, True, 32), "grey264": (8, True, 33), "table_global_830": (8, False, 63),
+    "tr7_33x40": (7, False, 100), "wide_12x9000": (3, False, 86), "edge_8x10880": (1, False, 16), "narrow_40x3_L": (8, True, 1),
+    "narrow_9x5": (8, True, 1), "one_1x1": (4, True, 1),
+}
+PIL_LIMIT = 32 << 20                                 # bytes of the resized image PIL builds before the crop
+
+
+def pil_allowed(h, w, C, size):
+    """Whether the live PIL reference is made for this shape: PIL resizes the WHOLE image before the crop (ow oh C bytes)"""
+    ow, oh, _, _ = resize_crop_plan(h, w, size)
+    return ow * oh * C < PIL_LIMIT
+
+
 def case_source(name):
-    """The source bytes of a case, [h][w][C] uint8 (C = 1 keeps its axis): the same on every machine."""
-    h, w, C, _, fill = CASES[name]
+    """The source bytes of a case of CASES or GEOMETRY_CASES, [h][w][C] uint8 (C = 1 keeps its axis): the same on every machine."""
+    h, w, C, _, fill = CASES[name] if name in CASES else GEOMETRY_CASES[name]
     if fill is not None:
         return np.full((h, w, C), fill, dtype=np.uint8)
     rng = np.random.RandomState(zlib.crc32(name.encode()) & 0x7FFFFFFF)
@@ -104,6 +138,20 @@ def resize_crop(src, size):
     tmp = filter_axis0(np.ascontiguousarray(src.transpose(1, 0, 2)), hb, hc)          # [size x][h][C]
     out = filter_axis0(np.ascontiguousarray(tmp.transpose(1, 0, 2)), vb, vc)          # [size y][size x][C]
     return np.ascontiguousarray(out.transpose(2, 0, 1))
+
+
+@functools.lru_cache(maxsize=None)
+def geometry_reference(name):
+    """A case of GEOMETRY_CASES -> (source, the restatement's output, live PIL's output or None where PIL is not asked): made once
+    per process, shared by the tests and read-only"""
+    h, w, C, size, _ = GEOMETRY_CASES[name]
+    src = case_source(name)
+    out = resize_crop(src, size)
+    pil = pil_resize_crop(src, size) if pil_allowed(h, w, C, size) else None
+    for a in (src, out, pil):
+        if a is not None:
+            a.setflags(write=False)
+    return src, out, pil
 
 
 def pil_resize_crop(src, size):

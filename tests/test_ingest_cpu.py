@@ -1,7 +1,9 @@
 """The ingest ABI and its host layer without a GPU: the numpy restatement (tests/_ingest_ref.py) equals the PIL-made fixture
 (tests/golden/ingest.npz) and the installed PIL; `mdm_ingest_plan` equals the restatement's tables; include/mdm_ingest.h parses to
-its two functions and is bound without entering the four older tables; the host checks refuse what the header says they refuse;
-`resize_crop_plan`, `image_folder` and `get_dataset` follow torchvision and upstream.  No kernel is launched."""
+its three functions and is bound without entering the four older tables; the host checks refuse what the header says they refuse;
+`resize_crop_plan`, `image_folder` and `get_dataset` follow torchvision and upstream; `mdm_ingest_launch_of` (the launcher's own
+geometry, asked without a device) says that the cases of `_ingest_ref.GEOMETRY_CASES` reach the kernel instantiation, the row tile
+and the loop trips they are there for, and refuses where and as the launcher does.  No kernel is launched."""
 import ctypes
 import os
 import re
@@ -21,7 +23,9 @@ INGEST_HEADER = os.path.join(ROOT, "include", "mdm_ingest.h")
 PLAN_PARAMS = ["in_size", "out_size", "first", "count", "bounds", "coeffs"]
 RESIZE_PARAMS = ["src", "src_stride", "K", "h", "w", "C", "hbounds", "hcoeffs", "ksh", "vbounds", "vcoeffs", "ksv", "dst", "dst_stride",
                  "M", "first", "S", "stream"]
-COVERAGE = {"mdm_ingest_plan": ("test_ingest_cpu", "mdm_ingest_plan"), "mdm_ingest_resize_crop": ("test_ingest_gpu", "mdm_ingest_resize_crop")}
+LAUNCH_OF_PARAMS = ["w", "C", "S", "ksh", "out"]
+COVERAGE = {"mdm_ingest_plan": ("test_ingest_cpu", "mdm_ingest_plan"), "mdm_ingest_resize_crop": ("test_ingest_gpu", "mdm_ingest_resize_crop"),
+            "mdm_ingest_launch_of": ("test_ingest_cpu", "mdm_ingest_launch_of")}
 
 
 @pytest.fixture(scope="module")
@@ -102,7 +106,8 @@ def test_the_plan_refuses(args, word):
 # ------------------------------------------------------------------ the fifth header and the five tables
 def test_the_header_parses_to_exactly_the_two_names():
     structs, protos = _lib.parse_header(open(INGEST_HEADER).read())
-    assert structs == {} and list(protos) == ["mdm_ingest_plan", "mdm_ingest_resize_crop"]
+    assert structs == {} and list(protos) == ["mdm_ingest_plan", "mdm_ingest_resize_crop", "mdm_ingest_launch_of"]
+    assert [n for n, _ in protos["mdm_ingest_launch_of"][1]] == LAUNCH_OF_PARAMS and dict(protos["mdm_ingest_launch_of"][1])["out"] == "int32_t*"
     assert [n for n, _ in protos["mdm_ingest_plan"][1]] == PLAN_PARAMS
     assert [n for n, _ in protos["mdm_ingest_resize_crop"][1]] == RESIZE_PARAMS
     r = dict(protos["mdm_ingest_resize_crop"][1])
@@ -114,13 +119,14 @@ def test_the_header_parses_to_exactly_the_two_names():
 def test_every_ingest_symbol_is_exported_and_bound():
     lib = _lib.load()
     declared = set(re.findall(r"\b(mdm_ingest_[a-z0-9_]+)\s*\(", open(INGEST_HEADER).read()))
-    assert declared == set(_lib.INGEST_EXPORTS) == set(_lib.INGEST_PROTOS) == set(_lib.INGEST_PARAMS) and len(declared) == 2
+    assert declared == set(_lib.INGEST_EXPORTS) == set(_lib.INGEST_PROTOS) == set(_lib.INGEST_PARAMS) and len(declared) == 3
     vp, i32, i64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
     for name in _lib.INGEST_EXPORTS:
         fn = getattr(lib, name)
         assert fn.argtypes == _lib.INGEST_PROTOS[name][0] and fn.restype is i32, name
     assert _lib.INGEST_PROTOS["mdm_ingest_plan"][0] == [i32, i32, i32, i32, vp, vp]
     assert _lib.INGEST_PROTOS["mdm_ingest_resize_crop"][0] == [vp, i64, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, i64, i64, i64, i32, vp]
+    assert _lib.INGEST_PROTOS["mdm_ingest_launch_of"][0] == [i32, i32, i32, i32, vp]
     assert os.path.samefile(_lib.INGEST_HEADER_PATH, INGEST_HEADER)
 
 
@@ -172,6 +178,129 @@ def test_refusals_name_the_argument():
         rc = lib.mdm_ingest_resize_crop(*dict(RESIZE_OK, **change).values())
         text = lib.mdm_last_error().decode()
         assert rc != 0 and text.startswith("ingest_resize_crop:") and re.search(r"(?<![\w])" + re.escape(arg) + r"(?![\w])", text), (change, text)
+
+
+# ------------------------------------------------------------------ the launch geometries: GEOMETRY_CASES and mdm_ingest_launch_of
+NJ_PAST_256 = ("preset128", "preset256", "grey264", "table_global_830", "tr7_33x40", "wide_12x9000")
+NARROW = ("narrow_40x3_L", "narrow_9x5")
+GEOMETRY_PLANS = {"preset128": (128, 146, 9, 0), "grey264": (282, 264, 0, 9), "tr7_33x40": (848, 700, 0, 74), "one_1x1": (4, 4, 0, 0)}
+SHORT_LAST_TILE = {"table_global_830": 4, "wide_12x9000": 1}        # rows of the last tile where it is not a whole one
+
+
+def _ksh(h, w, size):
+    ow, _, _, left = R.resize_crop_plan(h, w, size)
+    return _lib.load().mdm_ingest_plan(w, ow, left, size, None, None)
+
+
+def _launch_of(w, C, S, ksh):
+    """mdm_ingest_launch_of -> (TR, table in LDS, LDS bytes, workgroups per image), or the refusal's text"""
+    lib = _lib.load()
+    out = (ctypes.c_int32 * 4)(-1, -1, -1, -1)
+    if lib.mdm_ingest_launch_of(w, C, S, ksh, out) != 0:
+        assert list(out) == [-1] * 4                                   # a refused query writes nothing
+        return lib.mdm_last_error().decode()
+    assert I.launch_of(w, C, S, ksh) == (out[0], bool(out[1]), out[2], out[3])
+    return out[0], bool(out[1]), out[2], out[3]
+
+
+@pytest.mark.parametrize("name", list(R.GEOMETRY_CASES))
+def test_the_restatement_equals_live_pil_on_the_geometry_cases(name):
+    h, w, C, size, _ = R.GEOMETRY_CASES[name]
+    assert R.pil_allowed(h, w, C, size) == (name != "wide_12x9000")    # the one case PIL is not asked for
+    assert not set(R.GEOMETRY_CASES) & set(R.CASES)
+    src, out, pil = R.geometry_reference(name)
+    assert src.shape == (h, w, C) and out.shape == (C, size, size) and out.dtype == np.uint8
+    if pil is not None:
+        assert int((out != pil).sum()) == 0
+    if name == "one_1x1":
+        assert all((out[c] == src[0, 0, c]).all() for c in range(C))
+
+
+@pytest.mark.parametrize("name", list(R.GEOMETRY_CASES))
+def test_the_c_plan_equals_the_restatements_tables_on_the_geometry_cases(name):
+    h, w, _, size, _ = R.GEOMETRY_CASES[name]
+    ow, oh, top, left = R.resize_crop_plan(h, w, size)
+    for in_size, out_size, first in ((w, ow, left), (h, oh, top)):
+        ks, bounds, coeffs = _c_plan(in_size, out_size, first, size)
+        rks, rb, rc = R.plan(in_size, out_size, first, size)
+        assert ks == rks and np.array_equal(bounds, rb) and np.array_equal(coeffs, rc), (name, in_size, out_size)
+        hks, hb, hc = I.axis_plan(in_size, out_size, first, size)
+        assert hks == ks and np.array_equal(hb, rb) and np.array_equal(hc, rc)
+        assert (bounds[:, 0] >= 0).all() and (bounds[:, 0] + bounds[:, 1] <= in_size).all() and (bounds[:, 1] <= ks).all()
+
+
+def test_the_geometry_cases_reach_what_they_are_there_for():
+    """asked of the launcher's own geometry function, not restated: the row tile, where the table lies and the tiles of every case"""
+    assert set(R.GEOMETRY_EXPECTED) == set(R.GEOMETRY_CASES)
+    seen = []
+    for name, (h, w, C, size, _) in R.GEOMETRY_CASES.items():
+        tr, in_lds, lds, tiles = _launch_of(w, C, size, _ksh(h, w, size))
+        assert (tr, in_lds, tiles) == R.GEOMETRY_EXPECTED[name] and tiles == -(-size // tr) and lds <= 65536, (name, tr, in_lds, lds, tiles)
+        last = size - (tiles - 1) * tr
+        assert last == SHORT_LAST_TILE.get(name, tr), (name, last)
+        assert (size * C > 256) == (name in NJ_PAST_256), name
+        assert (w * C < 16) == (name in NARROW or name == "one_1x1"), name
+        seen.append((tr, in_lds, last < tr, size * C > 256, w * C < 16))
+    for name, want in GEOMETRY_PLANS.items():
+        h, w, _, size, _ = R.GEOMETRY_CASES[name]
+        assert R.resize_crop_plan(h, w, size) == want, name
+    assert _launch_of(10880, 3, 16, 3)[:3] == (1, False, 65512)         # edge_8x10880: 24 bytes below the limit
+    # what the cases of CASES reach: one geometry
+    for name, (h, w, C, size, _) in R.CASES.items():
+        tr, in_lds, lds, tiles = _launch_of(w, C, size, _ksh(h, w, size))
+        assert tr == min(size, 8) and in_lds and size * C <= 192 and w * C >= 16, name
+        seen.append((tr, in_lds, size - (tiles - 1) * tr < tr, False, False))
+    # between them: both instantiations, the shrunk tiles, a short last tile, NJ and the row on both sides of 256 and of 16 bytes
+    assert {s[1] for s in seen} == {True, False} and {s[0] for s in seen} >= {1, 3, 7, 8}
+    assert any(s[2] for s in seen) and {s[3] for s in seen} == {True, False} and {s[4] for s in seen} == {True, False}
+
+
+def test_the_launch_query_fits_lds_and_is_monotone_in_the_table():
+    for C in (1, 3):
+        for w in (1, 5, 53, 1031, 4000, 9000, 10880 * 3 // C):
+            for S in (1, 7, 8, 64, 128, 256, 700, 1024):
+                got = [_launch_of(w, C, S, ksh) for ksh in (1, 3, 5, 40, 261, 4001)]
+                if isinstance(got[0], str):
+                    assert all(g == got[0] for g in got), (w, C, S)        # the table has no part in a refusal
+                    continue
+                for tr, in_lds, lds, tiles in got:
+                    assert 1 <= tr <= min(S, 8) and tiles == -(-S // tr) and 0 < lds <= 65536, (w, C, S)
+                    assert (tr, tiles) == got[0][::3]                       # nor in the row tile
+                flags = [g[1] for g in got]
+                assert flags == sorted(flags, reverse=True), (w, C, S, flags)   # a larger ksh never moves the table into LDS
+                assert all(a[2] > b[2] for a, b in zip(got, got[1:]) if a[1] and not b[1])
+                assert len({g[2] for g in got if not g[1]}) <= 1             # out of LDS, the table costs nothing
+    assert _launch_of(10880, 3, 16, 3) == (1, False, 65512, 16)
+    for w in (10881, 10886):
+        text = _launch_of(w, 3, 16, 3)
+        assert isinstance(text, str) and text.startswith("ingest_resize_crop:") and "LDS" in text and str(3 * w) in text, text
+
+
+LAUNCH_OF_OK = dict(w=53, C=3, S=8, ksh=11)
+LAUNCH_OF_REFUSALS = [("C", dict(C=2)), ("C", dict(C=0)), ("w", dict(w=0)), ("w", dict(w=-3)), ("S", dict(S=0)), ("ksh", dict(ksh=0)),
+                      ("LDS", dict(w=20000)), ("LDS", dict(S=30000))]
+
+
+def test_the_launch_query_refusals_name_the_argument():
+    lib = _lib.load()
+    assert list(LAUNCH_OF_OK) + ["out"] == _lib.INGEST_PARAMS["mdm_ingest_launch_of"] == LAUNCH_OF_PARAMS
+    assert _launch_of(**LAUNCH_OF_OK) == (8, True, 1600, 1)
+    for arg, change in LAUNCH_OF_REFUSALS:
+        text = _launch_of(**dict(LAUNCH_OF_OK, **change))
+        assert isinstance(text, str) and re.match(r"ingest_(launch_of|resize_crop):", text) and \
+            re.search(r"(?<![\w])" + re.escape(arg) + r"(?![\w])", text), (change, text)
+    assert lib.mdm_ingest_launch_of(*LAUNCH_OF_OK.values(), None) != 0 and "out" in lib.mdm_last_error().decode()
+
+
+def test_the_launcher_and_the_query_refuse_alike():
+    """the launcher with the never-dereferenced pointers of RESIZE_OK at geometries the query refuses: the same words"""
+    lib = _lib.load()
+    for change in (dict(w=10881, S=16, ksh=3), dict(w=10886, S=16, ksh=3), dict(w=20000), dict(w=32641, C=1, S=64), dict(S=6000)):
+        kw = dict(RESIZE_OK, src_stride=2 ** 40, dst_stride=2 ** 40, **change)
+        said = _launch_of(kw["w"], kw["C"], kw["S"], kw["ksh"])
+        assert isinstance(said, str), change
+        assert lib.mdm_ingest_resize_crop(*kw.values()) != 0
+        assert lib.mdm_last_error().decode() == said, change
 
 
 # ------------------------------------------------------------------ torchvision's sizes

@@ -12,6 +12,7 @@ import torch
 import _neighbor_ref as NR
 import _store_rows as SR
 from _bounds import Buf
+from _guard_bufs import ByteBuf
 from _store_rows import IntBuf, call, refused, same_f32
 
 pytestmark = pytest.mark.gpu
@@ -21,22 +22,6 @@ EPS = NR.EPS
 
 def _dev():
     return torch.device("cuda:0")
-
-
-class ByteBuf:
-    """uint8 `.t` [n] inside guard bands of 0xA5 (inputs only: the kernels never write bytes); `shift` moves the data off 16-byte
-    alignment"""
-
-    def __init__(self, values, device, guard=65536, shift=0):
-        self.n, self.g = values.numel(), guard + shift
-        self.raw = torch.full((self.n + 2 * guard + shift,), 0xA5, dtype=torch.uint8, device=device)
-        self.t = self.raw[self.g:self.g + self.n]
-        self.t.copy_(values.reshape(-1))
-        self.want = values.reshape(-1).clone()
-
-    def intact(self):
-        return bool((self.raw[:self.g] == 0xA5).all()) and bool((self.raw[self.g + self.n:] == 0xA5).all()) and \
-            torch.equal(self.t.cpu(), self.want)
 
 
 _TABLES = {}
