@@ -4,7 +4,8 @@ Host side (Python on PyTorch-ROCm for device memory / streams / torch.distribute
 over libmdm_hip.so (hand-written HIP kernels for gfx950, C ABI in include/mdm_hip.h, image grids in
 include/mdm_vis.h, the device-resident data set in include/mdm_data.h, image-folder ingest in
 include/mdm_ingest.h, nearest-neighbour search in include/mdm_neighbor.h, the inpainting sampler in
-include/mdm_inpaint.h, image quality in include/mdm_metric.h).
+include/mdm_inpaint.h, image quality in include/mdm_metric.h, the restoration sampler in
+include/mdm_restore.h).
 Keeps the reference's call surface: Scheduler(args), Sampler(dataset, args, Scheduler,
 dataset_hist).sample(model, timesteps), Trainer(...).train(...), model(x, t).sample.
 """
@@ -22,7 +23,7 @@ from .metrics import ImageMetrics, image_metrics, mean_fill_baseline  # noqa: F4
 from .ingest import get_dataset, image_folder, ingest_block, resize_crop_plan  # noqa: F401
 from .optim import EMA, SGD, Accelerator, Adam, AdamW, get_lr_scheduler, get_optimizer  # noqa: F401
 from .rawsets import cifar10_arrays, flowers102_samples, mnist_arrays, read_idx  # noqa: F401
-from .sampler import Sampler, inpaint_keep, inpaint_start_index  # noqa: F401
+from .sampler import Sampler, inpaint_keep, inpaint_start_index, restore_expand, restore_measure  # noqa: F401
 from .scheduler import Scheduler  # noqa: F401
 from .train_step import MonitorRing  # noqa: F401
 from .trainer import BaseTrainer, Trainer  # noqa: F401

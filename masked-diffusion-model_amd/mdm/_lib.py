@@ -10,6 +10,7 @@ include/mdm_ingest.h is the ingest ABI (image files into the device data set, `m
 include/mdm_neighbor.h is the nearest-neighbour ABI (feature rows of the stored set, `mdm_nn_*`): `NEIGHBOR_PROTOS` / `NEIGHBOR_EXPORTS`.
 include/mdm_inpaint.h is the inpainting-sampler ABI (`mdm_inpaint_*`): `INPAINT_PROTOS` / `INPAINT_EXPORTS`.
 include/mdm_metric.h is the image-quality ABI (MSE, PSNR, SSIM, `mdm_metric_*`): `METRIC_PROTOS` / `METRIC_EXPORTS`.
+include/mdm_restore.h is the restoration-sampler ABI (group-mean projection, `mdm_restore_*`): `RESTORE_PROTOS` / `RESTORE_EXPORTS`.
 
 The product path has NO fallback: if the shared library or the header is missing, or a call
 returns non-zero, a RuntimeError is raised.
@@ -36,6 +37,7 @@ INGEST_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_ingest.h")
 NEIGHBOR_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_neighbor.h")
 INPAINT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_inpaint.h")
 METRIC_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_metric.h")
+RESTORE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_restore.h")
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 _SCALARS = {"int": i32, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32}
@@ -104,10 +106,10 @@ def _read_headers(core, extra):
 
 
 _STRUCTS, _DECLS, (_VIS_DECLS, _DATA_DECLS, _INTERP_DECLS, _INGEST_DECLS, _NEIGHBOR_DECLS, _INPAINT_DECLS,
-                    _METRIC_DECLS) = _read_headers(
+                    _METRIC_DECLS, _RESTORE_DECLS) = _read_headers(
     HEADER_PATH, ((VIS_HEADER_PATH, "mdm_vis_"), (DATA_HEADER_PATH, "mdm_data_"), (INTERP_HEADER_PATH, "mdm_interp_"),
                   (INGEST_HEADER_PATH, "mdm_ingest_"), (NEIGHBOR_HEADER_PATH, "mdm_nn_"), (INPAINT_HEADER_PATH, "mdm_inpaint_"),
-                  (METRIC_HEADER_PATH, "mdm_metric_")))
+                  (METRIC_HEADER_PATH, "mdm_metric_"), (RESTORE_HEADER_PATH, "mdm_restore_")))
 
 _DESC_PTR = {}
 
@@ -138,7 +140,7 @@ def _tables(decls):
 
 # every function the core header declares ...
 _PROTOS, _PARAMS, EXPORTS = _tables(_DECLS)
-# ... and the same three tables of include/mdm_vis.h, mdm_data.h, mdm_interp.h, mdm_ingest.h, mdm_neighbor.h, mdm_inpaint.h and mdm_metric.h, kept apart: the core tables are exactly what
+# ... and the same three tables of include/mdm_vis.h, mdm_data.h, mdm_interp.h, mdm_ingest.h, mdm_neighbor.h, mdm_inpaint.h, mdm_metric.h and mdm_restore.h, kept apart: the core tables are exactly what
 # mdm_hip.h declares
 VIS_PROTOS, VIS_PARAMS, VIS_EXPORTS = _tables(_VIS_DECLS)
 DATA_PROTOS, DATA_PARAMS, DATA_EXPORTS = _tables(_DATA_DECLS)
@@ -147,8 +149,11 @@ INGEST_PROTOS, INGEST_PARAMS, INGEST_EXPORTS = _tables(_INGEST_DECLS)
 NEIGHBOR_PROTOS, NEIGHBOR_PARAMS, NEIGHBOR_EXPORTS = _tables(_NEIGHBOR_DECLS)
 INPAINT_PROTOS, INPAINT_PARAMS, INPAINT_EXPORTS = _tables(_INPAINT_DECLS)
 METRIC_PROTOS, METRIC_PARAMS, METRIC_EXPORTS = _tables(_METRIC_DECLS)
-_ALL_PROTOS = {**_PROTOS, **VIS_PROTOS, **DATA_PROTOS, **INTERP_PROTOS, **INGEST_PROTOS, **NEIGHBOR_PROTOS, **INPAINT_PROTOS, **METRIC_PROTOS}
-_ALL_PARAMS = {**_PARAMS, **VIS_PARAMS, **DATA_PARAMS, **INTERP_PARAMS, **INGEST_PARAMS, **NEIGHBOR_PARAMS, **INPAINT_PARAMS, **METRIC_PARAMS}
+RESTORE_PROTOS, RESTORE_PARAMS, RESTORE_EXPORTS = _tables(_RESTORE_DECLS)
+_ALL_PROTOS = {**_PROTOS, **VIS_PROTOS, **DATA_PROTOS, **INTERP_PROTOS, **INGEST_PROTOS, **NEIGHBOR_PROTOS, **INPAINT_PROTOS, **METRIC_PROTOS,
+               **RESTORE_PROTOS}
+_ALL_PARAMS = {**_PARAMS, **VIS_PARAMS, **DATA_PARAMS, **INTERP_PARAMS, **INGEST_PARAMS, **NEIGHBOR_PARAMS, **INPAINT_PARAMS, **METRIC_PARAMS,
+               **RESTORE_PARAMS}
 
 _lib = None
 

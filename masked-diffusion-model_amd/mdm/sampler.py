@@ -7,7 +7,8 @@ Mirrors reference code/sampler.py: `_get_latent_initial` (:46-83), `sample` (:10
 (`sampling_mask_dependency` in {independent, dependent_prev, dependent_t -- the last for
 'thresholding' with mean_option 'degraded_area' or "0", scheduler.py:480-549}, `momentum_adaptive`
 in {base_sampling, base_momentum}).  `sample_inpaint` has no upstream counterpart: the same
-loop with every prediction projected onto the given pixels (include/mdm_inpaint.h).
+loop with every prediction projected onto the given pixels (include/mdm_inpaint.h).  Nor has `sample_restore`: the
+projection is onto given block means instead -- super-resolution and colourisation (include/mdm_restore.h).
 
 What is different from the reference loop (same arithmetic, same RNG order in replay mode):
   * the whole state stays on the GPU; nothing is copied to the host inside the loop.  The
@@ -100,6 +101,62 @@ def inpaint_keep(kind, N, H, W, **kw):
     else:
         raise ValueError(f"inpaint_keep: kind={kind!r}: one of 'box', 'half', 'random'")
     return keep.contiguous()
+
+
+def _check_restore_groups(pool, gray, channels):
+    """the group description of include/mdm_restore.h: -> (k, gray as int), or the error that names the argument"""
+    if isinstance(pool, bool) or not isinstance(pool, int) or pool not in (1, 2, 4, 8):
+        raise ValueError(f"pool={pool!r}: one of 1, 2, 4, 8")
+    if not isinstance(gray, (bool, int)) or gray not in (0, 1):
+        raise ValueError(f"gray={gray!r}: True or False")
+    if pool * pool * (channels if gray else 1) == 1:
+        raise ValueError(f"pool=1 with {'gray on one channel' if gray else 'gray=False'}: groups of one element constrain nothing")
+    return pool, int(gray)
+
+
+def _check_restore_tensor(name, t, dev=None):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: a torch.Tensor is needed, not {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: dtype {t.dtype}, float32 is needed")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, the sampler runs on {dev}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    if t.dim() != 4:
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, four dimensions are needed")
+
+
+def restore_measure(x, pool, gray=False):
+    """The measurement of a batch on the device (`mdm_restore_measure`): x [N, C, H, W] fp32 -> y [N, 1 if gray else C, H / pool,
+    W / pool], the mean of every pool x pool block (over the channels too with `gray`), summed in the order mdm_restore.h states."""
+    _check_restore_tensor("x", x)
+    n, c, h, w = x.shape
+    k, g = _check_restore_groups(pool, gray, c)
+    if h % k or w % k:
+        raise ValueError(f"x: shape {tuple(x.shape)}, H and W must be multiples of pool={k}")
+    if c > 8:
+        raise ValueError(f"x: shape {tuple(x.shape)}, at most 8 channels")
+    y = torch.empty(n, 1 if g else c, h // k, w // k, dtype=torch.float32, device=x.device)
+    call("mdm_restore_measure", x=ptr(x), k=k, gray=g, N=n, C=c, H=h, W=w, y=ptr(y), stream=stream())
+    return y
+
+
+def restore_expand(y, channels, pool, gray=False):
+    """A measurement broadcast over its groups on the device (`mdm_restore_start`): y [N, 1 if gray else channels, h, w] ->
+    [N, channels, h pool, w pool], nearest upsampling with the grey value copied to every channel.  The trivial completion that
+    has the measurement (its block means are y to rounding) and the one any quality number is to be read against."""
+    _check_restore_tensor("y", y)
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
+        raise ValueError(f"channels={channels!r}: an int from 1 to 8")
+    k, g = _check_restore_groups(pool, gray, channels)
+    n, cy, h, w = y.shape
+    if cy != (1 if g else channels):
+        raise ValueError(f"y: shape {tuple(y.shape)}, {1 if g else channels} channel(s) are needed for channels={channels}, gray={bool(g)}")
+    out = torch.empty(n, channels, h * k, w * k, dtype=torch.float32, device=y.device)
+    call("mdm_restore_start", y=ptr(y), k=k, gray=g, per_channel=0, N=n, C=channels, H=h * k, W=w * k, mu=None, expand=ptr(out),
+         stream=stream())
+    return out
 
 
 class Sampler:
@@ -295,6 +352,102 @@ class Sampler:
             self.args.sample_num = hi - lo
             S.replay_rows = (lo, hi, n)                               # every later host draw: full batch, sliced (replay mode)
             return self._sample_mean_shift_momentum(model, steps, latent=x_t, inpaint=inpaint, hist_steps=len(timesteps))
+        finally:
+            self.args = full
+            S.replay_rows = None
+
+    # ---- restoration: super-resolution and colourisation (no upstream counterpart; include/mdm_restore.h) ------
+    def sample_restore(self, model, timesteps_used_epoch, measurement, pool, gray=False, start="latent"):
+        """Complete images of which only block means are given: -> (sample_0, history lists) like `sample_inpaint`.
+        `measurement` [sample_num, 1 if gray else C, H / pool, W / pool] fp32 on the device (`restore_measure` makes one): the mean
+        of every pool x pool block, taken over the channels too with `gray` -- a box-downsampled image (pool > 1), a grey one
+        (pool 1, gray) or both.
+
+        Every reverse step runs as `sample` runs it, then its prediction is projected orthogonally onto the images that have this
+        measurement -- x0_hat += measurement[g] - mean_g(x0_hat) for every group g -- and the degrades, fill means, mask
+        dependencies and momentum modes go on from the projected x0_hat.  `start`:
+          "latent"    `_get_latent_initial`, the host draws of `sample`;
+          "measured"  a constant image per sample, the mean of its measurement (per channel for mean_area 'channel-wise' without
+                      `gray`): the colour the loop otherwise draws.  The latent draw is made either way.
+        There is no "matched" start: a measurement has no hole fraction that a timestep could be matched to.
+        With a process group every rank gets the full `measurement`, runs its rows (`model` built for `local_sample_num()`) and the
+        shards are all-gathered at the end."""
+        rank, world = self._shard()
+        if world == 1:
+            return self._sample_restore(model, timesteps_used_epoch, measurement, pool, gray, start)
+        n = self.args.sample_num
+        lo, hi = shard_bounds(n, rank, world)
+        if hi == lo:
+            raise ValueError(f"sample_num={n} < world size {world}: a rank would sample nothing")
+        x0, hist = self._sample_restore(model, timesteps_used_epoch, measurement, pool, gray, start, rows=(lo, hi))
+        def gather_hist(h):             # [T+1, n_local, C, H, W], on the host when args.sample_history is True
+            g = gather_shards(h.to(x0.device).transpose(0, 1).contiguous(), n).transpose(0, 1)
+            return g if h.is_cuda else g.cpu()
+        return gather_shards(x0, n), [gather_hist(h) for h in hist]
+
+    def evaluate_restore(self, model, timesteps_used_epoch, truth, pool, gray=False, starts=("latent", "measured"), trajectory=False):
+        """Measure `truth` (`restore_measure`), restore it with every start of `starts` and compare with `truth` on the device
+        (mdm.image_metrics, whole-image slots): -> {start: ImageMetrics, "expand": ImageMetrics of `restore_expand(y)`}, device
+        tensors of shape [sample_num], nothing read to the host.  Every start runs from the host generator state and the device
+        Philox state found at the call; both are put back at the end.  `trajectory=True` (needs args.sample_history == "device"):
+        the `sample_0` history list is measured in place and the tensors of the starts are [T + 1, sample_num]."""
+        from .metrics import image_metrics
+        S = self.Scheduler
+        if trajectory and getattr(self.args, "sample_history", True) != "device":
+            raise ValueError("trajectory=True measures the history where it lies: args.sample_history == 'device' is needed")
+        _check_restore_tensor("truth", truth, S.device)
+        y = restore_measure(truth, pool, gray)
+        host_state, dev_state = torch.get_rng_state(), S.dev_rng.dev.clone()
+        out = {}
+        try:
+            for s in starts:
+                torch.set_rng_state(host_state)
+                S.dev_rng.dev.copy_(dev_state)
+                x0, hist = self.sample_restore(model, timesteps_used_epoch, y, pool, gray, start=s)
+                out[s] = image_metrics(hist[HISTORY_NAMES.index("sample_0")] if trajectory else x0, truth)
+        finally:
+            torch.set_rng_state(host_state)
+            S.dev_rng.dev.copy_(dev_state)
+        out["expand"] = image_metrics(restore_expand(y, truth.shape[1], pool, gray), truth)
+        return out
+
+    def _check_restore_args(self, measurement, pool, gray, start):
+        a, dev = self.args, self.Scheduler.device
+        if start not in ("latent", "measured"):
+            raise ValueError(f"start={start!r}: one of 'latent', 'measured' (there is no 'matched' start: a measurement has no hole)")
+        k, g = _check_restore_groups(pool, gray, a.out_channel)
+        if a.data_size % k:
+            raise ValueError(f"pool={k}: data_size={a.data_size} is no multiple of it")
+        _check_restore_tensor("measurement", measurement, dev)
+        want = (a.sample_num, 1 if g else a.out_channel, a.data_size // k, a.data_size // k)
+        if tuple(measurement.shape) != want:
+            raise ValueError(f"measurement: shape {tuple(measurement.shape)}, (sample_num, 1 if gray else C, H / pool, W / pool) = "
+                             f"{want} is needed")
+        return k, g
+
+    def _sample_restore(self, model, timesteps, measurement, pool, gray=False, start="latent", rows=None):
+        """`sample_restore` on rows [lo, hi) of the batch (`rows`; all of it by default): `measurement` and every host draw are the
+        full batch's, `model` is built for hi - lo samples."""
+        import argparse
+        k, g = self._check_restore_args(measurement, pool, gray, start)
+        full, S = self.args, self.Scheduler
+        n, c, hw = full.sample_num, full.out_channel, full.data_size
+        lo, hi = rows if rows is not None else (0, n)
+        latent = self._get_latent_initial(model)                      # the full draw in every start: the host generator moves as in `sample`
+        x_t = latent[lo:hi]
+        if start == "measured":
+            mu = torch.empty(n, c, device=S.device)
+            call("mdm_restore_start", y=ptr(measurement), k=k, gray=g, per_channel=int(full.mean_area == "channel-wise"), N=n, C=c,
+                 H=hw, W=hw, mu=ptr(mu), expand=None, stream=stream())
+            x_t = mu[lo:hi, :, None, None].expand(hi - lo, c, hw, hw)
+        restore = (measurement[lo:hi], k, g)                          # a leading-dimension slice: a contiguous view
+        if rows is None:
+            return self._sample_mean_shift_momentum(model, timesteps, latent=x_t, restore=restore)
+        try:
+            self.args = argparse.Namespace(**vars(full))
+            self.args.sample_num = hi - lo
+            S.replay_rows = (lo, hi, n)                               # every later host draw: full batch, sliced (replay mode)
+            return self._sample_mean_shift_momentum(model, timesteps, latent=x_t, restore=restore)
         finally:
             self.args = full
             S.replay_rows = None
@@ -549,6 +702,10 @@ class Sampler:
             call("mdm_inpaint_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), known=ptr(b.known),
                  keep=ptr(b.keep), keep_C=b.keep.shape[1], N=n, C=c, H=h, W=w, pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0),
                  x0_hat=ptr(b.x0_hat), stream=stream())
+        elif getattr(b, "measurement", None) is not None:   # restoration: the same reconstruction, then the group means put right
+            call("mdm_restore_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), y=ptr(b.measurement), k=b.pool,
+                 gray=b.gray, N=n, C=c, H=h, W=w, pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0), x0_hat=ptr(b.x0_hat),
+                 stream=stream())
         else:
             call("mdm_sampler_x0", dtype=pdt, pred_nhwc=ptr(pred), Cp=cp, x_in=ptr(b.x_in), s=ptr(b.s), N=n, C=c, H=h, W=w,
                  pred_nchw=ptr(b.pred_nchw), shifted0=ptr(b.shifted0), x0_hat=ptr(b.x0_hat), stream=stream())          # :146-152
@@ -612,11 +769,15 @@ class Sampler:
             return dict(amount=amount, u=S.host_uniforms(b.x_t))
         return (lambda: S.host_shift_z(S._host_full(b.ratio.cpu(), n), n, c, h, w) if b.kind != 0 else None), mask_src
 
-    def _sample_mean_shift_momentum(self, model, timesteps, latent=None, inpaint=None, hist_steps=None):
+    def _sample_mean_shift_momentum(self, model, timesteps, latent=None, inpaint=None, hist_steps=None, restore=None):
         """sampler.py:109-261.  `inpaint = (known, keep)`: the rows of this run on the device; every step then projects its
-        prediction onto them (`sample_inpaint`).  `hist_steps`: the history lists get that many slots + 1 (a 'matched' run walks
-        fewer steps than the list it was given has; the slots behind them stay zero)."""
+        prediction onto them (`sample_inpaint`).  `restore = (y, k, gray)`: the measurement rows of this run on the device; every
+        step then projects its prediction onto the images with these group means (`sample_restore`).  `hist_steps`: the history
+        lists get that many slots + 1 (a 'matched' run walks fewer steps than the list it was given has; the slots behind them
+        stay zero)."""
         from .unet import UNet
+        if inpaint is not None and restore is not None:
+            raise ValueError("inpaint and restore: one projection per run, a keep mask and a measurement do not combine")
         a, S = self.args, self.Scheduler
         dev, T = S.device, len(timesteps)
         n, c, hw = a.sample_num, a.out_channel, a.data_size
@@ -649,6 +810,8 @@ class Sampler:
             mp=torch.empty(n, c, device=dev), diff=torch.zeros_like(x_t))
         if inpaint is not None:
             b.known, b.keep = inpaint
+        if restore is not None:
+            b.measurement, b.pool, b.gray = restore
         b.draw_z, b.mask_src = self._draws(b)
         if graph:
             return self._sample_graph(model, timesteps, b), []
