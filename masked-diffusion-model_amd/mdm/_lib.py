@@ -11,6 +11,7 @@ include/mdm_neighbor.h is the nearest-neighbour ABI (feature rows of the stored 
 include/mdm_inpaint.h is the inpainting-sampler ABI (`mdm_inpaint_*`): `INPAINT_PROTOS` / `INPAINT_EXPORTS`.
 include/mdm_metric.h is the image-quality ABI (MSE, PSNR, SSIM, `mdm_metric_*`): `METRIC_PROTOS` / `METRIC_EXPORTS`.
 include/mdm_restore.h is the restoration-sampler ABI (group-mean projection, `mdm_restore_*`): `RESTORE_PROTOS` / `RESTORE_EXPORTS`.
+include/mdm_moment.h is the set-moment ABI (fp64 first and second moments of feature rows, `mdm_moment_*`): `MOMENT_PROTOS` / `MOMENT_EXPORTS`.
 
 The product path has NO fallback: if the shared library or the header is missing, or a call
 returns non-zero, a RuntimeError is raised.
@@ -38,6 +39,7 @@ NEIGHBOR_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_neighbor.
 INPAINT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_inpaint.h")
 METRIC_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_metric.h")
 RESTORE_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_restore.h")
+MOMENT_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "mdm_moment.h")
 
 vp, i32, i64, u64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 _SCALARS = {"int": i32, "int32_t": i32, "int64_t": i64, "uint64_t": u64, "float": f32}
@@ -106,10 +108,11 @@ def _read_headers(core, extra):
 
 
 _STRUCTS, _DECLS, (_VIS_DECLS, _DATA_DECLS, _INTERP_DECLS, _INGEST_DECLS, _NEIGHBOR_DECLS, _INPAINT_DECLS,
-                    _METRIC_DECLS, _RESTORE_DECLS) = _read_headers(
+                    _METRIC_DECLS, _RESTORE_DECLS, _MOMENT_DECLS) = _read_headers(
     HEADER_PATH, ((VIS_HEADER_PATH, "mdm_vis_"), (DATA_HEADER_PATH, "mdm_data_"), (INTERP_HEADER_PATH, "mdm_interp_"),
                   (INGEST_HEADER_PATH, "mdm_ingest_"), (NEIGHBOR_HEADER_PATH, "mdm_nn_"), (INPAINT_HEADER_PATH, "mdm_inpaint_"),
-                  (METRIC_HEADER_PATH, "mdm_metric_"), (RESTORE_HEADER_PATH, "mdm_restore_")))
+                  (METRIC_HEADER_PATH, "mdm_metric_"), (RESTORE_HEADER_PATH, "mdm_restore_"),
+                  (MOMENT_HEADER_PATH, "mdm_moment_")))
 
 _DESC_PTR = {}
 
@@ -140,7 +143,7 @@ def _tables(decls):
 
 # every function the core header declares ...
 _PROTOS, _PARAMS, EXPORTS = _tables(_DECLS)
-# ... and the same three tables of include/mdm_vis.h, mdm_data.h, mdm_interp.h, mdm_ingest.h, mdm_neighbor.h, mdm_inpaint.h, mdm_metric.h and mdm_restore.h, kept apart: the core tables are exactly what
+# ... and the same three tables of include/mdm_vis.h, mdm_data.h, mdm_interp.h, mdm_ingest.h, mdm_neighbor.h, mdm_inpaint.h, mdm_metric.h, mdm_restore.h and mdm_moment.h, kept apart: the core tables are exactly what
 # mdm_hip.h declares
 VIS_PROTOS, VIS_PARAMS, VIS_EXPORTS = _tables(_VIS_DECLS)
 DATA_PROTOS, DATA_PARAMS, DATA_EXPORTS = _tables(_DATA_DECLS)
@@ -150,10 +153,11 @@ NEIGHBOR_PROTOS, NEIGHBOR_PARAMS, NEIGHBOR_EXPORTS = _tables(_NEIGHBOR_DECLS)
 INPAINT_PROTOS, INPAINT_PARAMS, INPAINT_EXPORTS = _tables(_INPAINT_DECLS)
 METRIC_PROTOS, METRIC_PARAMS, METRIC_EXPORTS = _tables(_METRIC_DECLS)
 RESTORE_PROTOS, RESTORE_PARAMS, RESTORE_EXPORTS = _tables(_RESTORE_DECLS)
+MOMENT_PROTOS, MOMENT_PARAMS, MOMENT_EXPORTS = _tables(_MOMENT_DECLS)
 _ALL_PROTOS = {**_PROTOS, **VIS_PROTOS, **DATA_PROTOS, **INTERP_PROTOS, **INGEST_PROTOS, **NEIGHBOR_PROTOS, **INPAINT_PROTOS, **METRIC_PROTOS,
-               **RESTORE_PROTOS}
+               **RESTORE_PROTOS, **MOMENT_PROTOS}
 _ALL_PARAMS = {**_PARAMS, **VIS_PARAMS, **DATA_PARAMS, **INTERP_PARAMS, **INGEST_PARAMS, **NEIGHBOR_PARAMS, **INPAINT_PARAMS, **METRIC_PARAMS,
-               **RESTORE_PARAMS}
+               **RESTORE_PARAMS, **MOMENT_PARAMS}
 
 _lib = None
 

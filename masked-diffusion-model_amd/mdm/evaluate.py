@@ -234,6 +234,36 @@ class NeighborBank:
         d.gather(idx, 0, idx.numel(), out)
         return out
 
+    def moments(self):
+        """The fp64 moments of the bank's rows (mdm.moments.SetMoments, include/mdm_moment.h), streamed through `_chunks()` -- an
+        uncached bank folds one rebuilt chunk at a time -- made once and kept on the bank."""
+        from .moments import SetMoments
+        if getattr(self, "_moments", None) is None:
+            m = SetMoments(self.D, self.dataset.device)
+            for first, R, rows in self._chunks():
+                m.update(rows[:R])
+            self._moments = m
+        return self._moments
+
+    def source_moments(self, source, into=None):
+        """Fold the rows of the source images [B, C, H, W] into `into` (a new `SetMoments` when None) and return it.  The source goes
+        through the SAME map as the data -- the bank's `normalize`, `size` and `antialias` -- because a set distance needs both
+        sides in one feature space.  (`source_rows`, which leaves the source un-normalised as upstream does, serves the search.)"""
+        from .moments import SetMoments
+        d = self.dataset
+        if not isinstance(source, torch.Tensor) or source.dim() != 4 or source.shape[1] != d.C or \
+                (not self.size and tuple(source.shape[2:]) != (d.H, d.W)):
+            raise ValueError(f"source: {tuple(getattr(source, 'shape', ()))} does not match the data set's images {(d.C, d.H, d.W)}")
+        if into is None:
+            into = SetMoments(self.D, d.device)
+        elif not isinstance(into, SetMoments) or into.d != self.D:
+            raise ValueError(f"into: a SetMoments of d = {self.D} is needed")
+        src = source.to(d.device, torch.float32).contiguous()
+        B, C, H, W = (int(v) for v in src.shape)
+        out = torch.zeros(B, self.row_ld, dtype=torch.float32, device=d.device)
+        self._launch(src, 0, C * H * W, B, C, H, W, None, 0, B, self.normalize, False, out)
+        return into.update(out)
+
 
 def _full_bank(dataset):
     """the full-resolution bank of a `DeviceDataset` on a GPU, made once and kept on the data set object; None for anything else"""

@@ -239,6 +239,45 @@ class Sampler:
             return g if h.is_cuda else g.cpu()
         return gather_shards(x0, n), [gather_hist(h) for h in hist]
 
+    # ---- set-level quality (no upstream counterpart; include/mdm_moment.h, DESIGN.md finding 73) -----------------
+    def evaluate_frechet(self, model, timesteps_used_epoch, rounds=1, features="pixels", reference=None):
+        """Run `sample` `rounds` times -- the draws of that many successive `sample` calls from the host generator and the device
+        Philox state, both left where those calls leave them -- fold every round's `sample_0` into one `mdm.moments.SetMoments` on
+        the device (no image is kept) and return `mdm.moments.frechet_distance(samples, reference)`, a FrechetResult.
+          features "pixels": a row is a raw image at full resolution, d = C H W; the default `reference` is the data set's own pixel
+                             moments, read in place (uint8 through its table) once and kept on the data set object;
+                   "bank":   a row is a row of the 32 x 32 `NeighborBank` of `get_nearest_neighbor`, the samples put through the
+                             bank's own map (`NeighborBank.source_moments`); the default `reference` is `bank.moments()`.
+          reference: a `SetMoments` of the same d, e.g. `SetMoments.load` of a stats file, or None.
+        A pixel-space (or bank-space) Frechet distance, NOT FID.  rounds x sample_num <= d gives a rank-deficient sample covariance:
+        the number is defined and biased upward (`rank_deficient`).  Under sharded sampling every rank holds the gathered batch and
+        folds all of it, so every rank returns the same bits."""
+        from . import evaluate, moments
+        if features not in ("pixels", "bank"):
+            raise ValueError(f"features={features!r}: 'pixels' or 'bank'")
+        if isinstance(rounds, bool) or not isinstance(rounds, int) or rounds < 1:
+            raise ValueError(f"rounds={rounds!r}: a positive int")
+        if reference is not None and not isinstance(reference, moments.SetMoments):
+            raise TypeError(f"reference: a SetMoments or None is needed, not {type(reference).__name__}")
+        bank = None
+        if features == "bank":
+            antialias = bool(getattr(self, "nn_antialias", getattr(self.args, "nn_antialias", True)))
+            bank = getattr(self, "_nn_bank", None)
+            if bank is None or bank.antialias != antialias:
+                bank = self._nn_bank = evaluate.NeighborBank(self.dataset, size=32, antialias=antialias)
+        if reference is None:
+            reference = bank.moments() if bank is not None else moments.dataset_moments(self.dataset)
+        acc = None
+        for _ in range(rounds):
+            x0, _hist = self.sample(model, timesteps_used_epoch)
+            if bank is not None:
+                acc = bank.source_moments(x0, into=acc)
+            else:
+                if acc is None:
+                    acc = moments.SetMoments(x0[0].numel(), x0.device)
+                acc.update(x0)
+        return moments.frechet_distance(acc, reference)
+
     # ---- inpainting (no upstream counterpart; include/mdm_inpaint.h, DESIGN.md finding 70) ----------------------
     def sample_inpaint(self, model, timesteps_used_epoch, known, keep, start="latent"):
         """Complete partly given images: -> (sample_0, history lists) like `sample`.  `known` [sample_num, C, H, W] fp32 on the
